@@ -2,7 +2,7 @@
 """Headline benchmark: Zip commit + open MCoeffs/s on a 2^24-coefficient witness
 (BASELINE.json `metric`, `configs[2]`).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 A step = MultilinearZip::commit followed by MultilinearZip::open of a synthetic witness that is
@@ -19,6 +19,12 @@ multi-device context (zip_mctx_commit_open) -- what a Rust ZincProver, one proce
 under torchrun rank 0 works and the other ranks wait at the barriers.
 `--shard rows` (strong scaling, one Python process per GPU): zinc_amd.dist over torch.distributed,
 all-gather of roots and of the partial row combinations + exact on-device sum.
+
+A plain run sets up, warms up, times the K steps of the headline figure (`value`, `ms_per_step`) and prints the line.
+--full also measures what is reported beside it: the K cold steps, a short region with every kernel bracketed by
+events (`kernels_ms_per_step`, `roofline_gather`), the extra legs (`pipelined`, `full_materialisation`,
+`two_call_unchanged_api`, `--in-flight`) and the CPU oracle's `cpu_baseline`.  --dump-outputs DIR writes what the last
+timed step computed (see dump_outputs), so that two builds can be compared output for output on the same inputs.
 
 Rank 0 prints ONE JSON line.
 """
@@ -166,6 +172,42 @@ def roots_view(torch, ptr, rows, dev):
     return v
 
 
+DUMP_EDGE_BYTES = 1 << 20  # proof_head / proof_tail: the u' rows open the stream, the evaluation row closes it
+DUMP_BLOCKS, DUMP_BLOCK_BYTES = 4096, 1024  # proof_sample: that many seeded, non-overlapping blocks of the stream
+DUMP_SUM_BYTES = 1 << 20  # proof_block_sums: one byte sum per MiB, every byte of the stream covered
+
+
+def dump_outputs(out_dir, torch, proof, seed):
+    """What the timed call handed its caller -- the proof stream, `proof_len` bytes in HBM (1.74 GiB at 2^24) -- as
+    float32 / float64 .npy files of about 24 MB in all: its first and last MiB, DUMP_BLOCKS blocks at offsets drawn
+    from `seed` (saved beside them), and the byte sum of every MiB.  Byte values and sums are exact in those types."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = proof.reshape(-1)
+    if flat.is_cuda:
+        torch.cuda.synchronize()
+    total = flat.numel()
+    edge = min(total, DUMP_EDGE_BYTES)
+    block = min(DUMP_BLOCK_BYTES, total)
+    slots = total // block
+    rng = np.random.default_rng(seed)
+    starts = np.sort(rng.choice(slots, size=min(DUMP_BLOCKS, slots), replace=False)).astype(np.int64) * block
+    idx = torch.from_numpy((starts[:, None] + np.arange(block, dtype=np.int64)).reshape(-1)).to(flat.device)
+    whole = total // DUMP_SUM_BYTES * DUMP_SUM_BYTES
+    sums = flat[:whole].view(-1, DUMP_SUM_BYTES).sum(dim=1, dtype=torch.int64)
+    if whole < total:
+        sums = torch.cat([sums, flat[whole:].sum(dtype=torch.int64).reshape(1)])
+    arrays = {
+        "proof_head": flat[:edge].cpu().numpy().astype(np.float32),
+        "proof_tail": flat[total - edge:].cpu().numpy().astype(np.float32),
+        "proof_sample": flat[idx].cpu().numpy().astype(np.float32).reshape(starts.size, block),
+        "proof_sample_offsets": starts.astype(np.float64),
+        "proof_block_sums": sums.cpu().numpy().astype(np.float64),
+    }
+    del idx
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def run_mctx(args, torch, dist, rank, world, cabi, perm1, perm2, zf, coeffs, cols, q0, nv, row_len, num_rows, cw, depth, fl):
     """--shard mctx: ONE process drives the GPUs through the C ABI's multi-device context (zip_mctx_commit_open): the
     rows of one polynomial split over them (strong scaling), witness resident on the devices, every output left in
@@ -256,15 +298,23 @@ def main():
                     help="skip the extra leg that runs the same steps as jobs, two in flight (zip_commit_open_begin / "
                          "zip_job_wait); it is reported beside `value`, never as it")
     ap.add_argument("--steady-only", action="store_true",
-                    help="only the warm-up, cold and steady one-call steps: no event-bracketed second region, no extra legs "
-                         "(the run tools/profile_round.sh traces, so that rocprofv3's per-kernel averages are those of `value`)")
+                    help="with --full: only the warm-up, cold and steady one-call steps: no event-bracketed second region, no "
+                         "extra legs (the run tools/profile_round.sh traces, so that rocprofv3's per-kernel averages are those "
+                         "of `value`).  A plain run has neither anyway")
     ap.add_argument("--in-flight", type=int, default=1,
                     help="extra leg (1 GPU, reported beside `value`, never as it): this many independent commit+open jobs "
                          "in flight at once, one zip_ctx and one host thread each")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5A494E43)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside `value`: the cold steps, the event-bracketed all-kernels "
+                         "region, the extra legs and the CPU baseline.  Without it a run warms up, times --steps steps "
+                         "and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (samples and block sums of the proof "
+                         "stream, float32 / float64 .npy) to DIR")
     args = ap.parse_args()
 
-    if not args.no_cpu_baseline and int(os.environ.get("RANK", "0")) == 0:
+    if args.full and not args.no_cpu_baseline and int(os.environ.get("RANK", "0")) == 0:
         # the checker library of the cpu_baseline leg is built (if stale) BEFORE anything touches the GPU:
         # a GPU-initialised process must not fork + exec `make` on the GPU boxes
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -314,9 +364,11 @@ def main():
         # context (strong scaling of one polynomial, the roots gathered with in-process RCCL) -- what a Rust ZincProver,
         # one process making one call, would use.  Under torchrun (WORLD_SIZE = N) the default stays `polys`.
         args.shard = "mctx"
+    rows_mode = args.shard == "rows" and world > 1
+    if args.dump_outputs and (args.shard == "mctx" or rows_mode):
+        raise SystemExit("--dump-outputs: only the one-polynomial-per-process path (--shard polys) keeps its proof in one buffer")
     if args.shard == "mctx":
         return run_mctx(args, torch, dist, rank, world, cabi, perm1, perm2, zf, coeffs, cols, q0, nv, row_len, num_rows, cw, depth, fl)
-    rows_mode = args.shard == "rows" and world > 1
     if rows_mode:
         from zinc_amd.dist import RowShardedZip
 
@@ -374,23 +426,26 @@ def main():
         torch.cuda.synchronize()
         ctx.synchronize()
 
-    # `--warmup W` means what it says: W untimed steps, then K timed steps = the COLD figure (`cold` in the JSON line: a
-    # fresh process needs ~15 steps to its steady state -- first use of the 2.5 GB of pooled buffers, table uploads, clocks:
-    # tools/exp_warmup.py).  Those K steps (topped up to STEADY_AFTER if K is smaller) are the spin-up of the steady
-    # measurement that follows; `value` is the steady figure, `untimed_steps_before_value` says how many steps preceded it.
+    # `--warmup W` means what it says: W untimed steps.  A fresh process needs ~15 steps to its steady state (first use
+    # of the 2.5 GB of pooled buffers, table uploads, clocks: tools/exp_warmup.py), so STEADY_AFTER more untimed steps
+    # follow; `value` is the steady figure, `untimed_steps_before_value` says how many steps preceded it.  --full: K timed
+    # steps right after the W = the COLD figure (`cold` in the JSON line); they count towards the STEADY_AFTER.
     for _ in range(args.warmup):
         step()
     barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    barrier()
-    dt_cold = time.perf_counter() - t0
-    extra_spinup = max(0, STEADY_AFTER - args.steps)
+    cold_steps = 0
+    if args.full:
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        dt_cold = time.perf_counter() - t0
+        cold_steps = args.steps
+    extra_spinup = max(0, STEADY_AFTER - cold_steps)
     for _ in range(extra_spinup):
         step()
     barrier()
-    untimed_before = args.warmup + args.steps + extra_spinup
+    untimed_before = args.warmup + cold_steps + extra_spinup
     # HIP events on the stream the dominant kernel is launched on (its own); the other kernels of a step are timed in a
     # short second region below: events between the kernels of one stream delay every dependent launch by ~12 us
     ctx.set_profiling(0 if os.environ.get("BENCH_NO_EVENTS") else 2)  # (BENCH_NO_EVENTS=1: what do the two events cost?)
@@ -403,25 +458,29 @@ def main():
     if os.environ.get("BENCH_NO_EVENTS"):
         ktimes = {"raa_commit_kernel": (1, float("nan"))}
     clock_mhz = ctx.commit_clock_mhz()  # shader clock during the last timed commit kernel (in-kernel stamps)
+    ctx.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, proof, args.seed)
     steps_all = min(args.steps, 10)
     ktimes_all = {}
-    if not args.steady_only:
+    if args.full and not args.steady_only:
         ctx.set_profiling(True)
         for _ in range(steps_all):
             step()
         barrier()
         ktimes_all = ctx.profile_read()
-    ctx.set_profiling(False)
+        ctx.set_profiling(False)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=xdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-        t = torch.tensor([dt_cold], dtype=torch.float64, device=xdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt_cold = float(t.item())
+        if args.full:
+            t = torch.tensor([dt_cold], dtype=torch.float64, device=xdev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt_cold = float(t.item())
 
     pipelined = None
-    if args.steady_only:
+    if args.steady_only or not args.full:
         args.no_pipelined = True
     if not args.no_pipelined and world == 1 and not rows_mode and not (args.two_calls or args.no_hint):
         # The same K steps as jobs, two in flight: the next polynomial's commit kernel is queued behind the current
@@ -449,7 +508,7 @@ def main():
 
     two_call = None
     full_mat = None
-    if world == 1 and not rows_mode and not (args.two_calls or args.no_hint) and not args.steady_only:
+    if args.full and world == 1 and not rows_mode and not (args.two_calls or args.no_hint) and not args.steady_only:
         # What MultilinearZip::commit returns in the reference: the WHOLE MultilinearZipData (every encoded row, every tree
         # node: src/zip/pcs/structs.rs:33-38; benches/zip_benches.rs:118 black-boxes it) -- plain zip_commit with no hint of
         # any kind (speculation off), then zip_open.  This is what SURVEY 8d's 200 B/coeff prices; reported beside `value`.
@@ -484,7 +543,7 @@ def main():
                     "proof_identical_to_one_call": bool(torch.equal(proof, proof_ref))}
         del proof_ref
 
-    if world == 1 and not rows_mode and not (args.two_calls or args.no_hint) and not args.steady_only:
+    if args.full and world == 1 and not rows_mode and not (args.two_calls or args.no_hint) and not args.steady_only:
         # The two calls an UNCHANGED ZincProver makes (src/zinc/prover.rs:315-320): plain zip_commit -- no columns in its
         # signature -- then zip_open.  The first opening names the columns; from then on the ctx hints its plain commits
         # with that list on its own, so this leg should match `value`.  The bench's witness is DEVICE memory, for which
@@ -513,7 +572,7 @@ def main():
                     "proof_identical_to_one_call": bool(torch.equal(proof, proof_one_call))}
 
     in_flight = None
-    if args.in_flight > 1 and world == 1 and not rows_mode:
+    if args.full and args.in_flight > 1 and world == 1 and not rows_mode:
         # Independent jobs (separate provers' polynomials) overlapped: the end of one job's opening -- the last chunk's
         # gather, the fold, the host turnaround -- runs beside the next job's commit kernel.  Throughput, not latency.
         import threading
@@ -591,11 +650,8 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "untimed_steps_before_value": untimed_before,  # --warmup, then the K timed COLD steps (`cold`), topped up to 12
+            "untimed_steps_before_value": untimed_before,  # --warmup (and --full's K timed COLD steps), topped up by 12
             "ms_per_step": round(step_s * 1e3, 4),
-            # the first K steps after only --warmup untimed ones (a fresh process; `value` is the steady state after them)
-            "cold": {"steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt_cold / args.steps * 1e3, 4),
-                     "value": round(coeffs_per_step * args.steps / dt_cold / 1e6, 2), "unit": "MCoeffs/s"},
             "higher_is_better": True,
             "scaling": "strong" if rows_mode else "weak",
             "vs_baseline": None,
@@ -631,7 +687,7 @@ def main():
                                     )},
             # ... and the roofline that does bind it
             "roofline_valu": valu,
-            "roofline_gather": {"bound": "hbm", "kernel": "open_columns_kernel",
+            "roofline_gather": None if not args.full else {"bound": "hbm", "kernel": "open_columns_kernel",
                                 "algorithmic_bytes_per_step": int(gather_bytes),
                                 "sum_ms_per_step": round(g_ms / args.steps, 4),
                                 "achieved": round(gather_bytes / (g_ms / args.steps * 1e-3) / 1e9, 1) if g_ms else None,
@@ -644,6 +700,10 @@ def main():
             "kernels_ms_per_step": dict({k: round(v[1] / steps_all, 4) for k, v in sorted(ktimes_all.items())},
                                         **{dom: round(avg_ms * launches / args.steps, 4)}),
         }
+        if args.full:
+            # the first K steps after only --warmup untimed ones (a fresh process; `value` is the steady state after them)
+            out["cold"] = {"steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt_cold / args.steps * 1e3, 4),
+                           "value": round(coeffs_per_step * args.steps / dt_cold / 1e6, 2), "unit": "MCoeffs/s"}
         if full_mat:
             out["full_materialisation"] = full_mat
         if two_call:
@@ -652,7 +712,7 @@ def main():
             out["pipelined"] = pipelined
         if in_flight:
             out["in_flight"] = in_flight
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(nv, args.seed)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -7,7 +7,7 @@ REPS=${1:-3}
 OLD=${2:-zinc_amd/lib/libzip_hip_prev.so}
 one() {  # label, env...
     local label=$1; shift
-    env "$@" python3 bench.py --num-vars $NV --no-cpu-baseline --no-pipelined --steps 20 --warmup 5 2>/dev/null | python3 -c "
+    env "$@" python3 bench.py --full --num-vars $NV --no-cpu-baseline --no-pipelined --steps 20 --warmup 5 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read());k=d['kernels_ms_per_step']
 t=d.get('two_call_unchanged_api') or {}

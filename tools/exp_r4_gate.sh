@@ -1,4 +1,4 @@
-run() { echo -n "$* : "; env "$@" python3 bench.py --num-vars ${NV:-24} --no-cpu-baseline --no-pipelined --steps 20 --warmup 5 2>/dev/null | python3 -c "
+run() { echo -n "$* : "; env "$@" python3 bench.py --full --num-vars ${NV:-24} --no-cpu-baseline --no-pipelined --steps 20 --warmup 5 2>/dev/null | python3 -c "
 import json,sys;d=json.loads(sys.stdin.read());k=d['kernels_ms_per_step'];t=d.get('two_call_unchanged_api') or {};print(d['ms_per_step'], 'commit',k.get('raa_commit_kernel'),'gather',k.get('open_columns_kernel'),'combine',k.get('combine_rows_kernel'), 'wait', k.get('wait_counter_kernel'),'two_call',t.get('ms_per_step'), t.get('proof_identical_to_one_call'))"; }
 for rep in 1 2; do
 run A=1

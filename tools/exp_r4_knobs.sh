@@ -2,7 +2,7 @@
 # GPU box, round 4: the knobs that lost in round 3 only because of the gather's requests, re-measured with the
 # row-interleaved layout.  One bench line per setting, default at both ends and in the middle.
 NV=${NV:-24}
-run() { echo -n "$* : "; env "$@" python3 bench.py --num-vars $NV --no-cpu-baseline --no-pipelined --steps 20 --warmup 5 2>/dev/null | python3 -c "
+run() { echo -n "$* : "; env "$@" python3 bench.py --full --num-vars $NV --no-cpu-baseline --no-pipelined --steps 20 --warmup 5 2>/dev/null | python3 -c "
 import json,sys;d=json.loads(sys.stdin.read());k=d['kernels_ms_per_step'];print(d['ms_per_step'], 'commit',k.get('raa_commit_kernel'),'gather',k.get('open_columns_kernel'),'combine',k.get('combine_rows_kernel'), 'wait', k.get('wait_counter_kernel'))"; }
 run A=1
 run ZIP_HIP_GATHER_PRIO=0

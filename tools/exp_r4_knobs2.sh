@@ -1,4 +1,4 @@
-run() { echo -n "$* : "; env "$@" python3 bench.py --num-vars 24 --no-cpu-baseline --no-pipelined --steps 20 --warmup 5 2>/dev/null | python3 -c "
+run() { echo -n "$* : "; env "$@" python3 bench.py --full --num-vars 24 --no-cpu-baseline --no-pipelined --steps 20 --warmup 5 2>/dev/null | python3 -c "
 import json,sys;d=json.loads(sys.stdin.read());k=d['kernels_ms_per_step'];print(d['ms_per_step'], 'commit',k.get('raa_commit_kernel'),'gather',k.get('open_columns_kernel'),'combine',k.get('combine_rows_kernel'), 'wait', k.get('wait_counter_kernel'))"; }
 tools/ubench_signal
 run A=1

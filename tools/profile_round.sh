@@ -15,10 +15,10 @@ say() { echo "$(date +%T) $*" >> $P; }
 make -C oracle > /dev/null 2>&1 || true
 # (--steady-only: warm-up, cold and steady one-call steps, nothing else; the summaries keep the steady launches only, so
 # that AverageNs of the dominant kernel is the `avg_launch_ms` of the traced run's JSON line)
-say trace24; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady-only > $OUT/bench_trace.log 2>&1
-say trace24-nohint; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_nohint -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --steady-only --no-hint > $OUT/bench_trace_nohint.log 2>&1
-say trace26; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace26 -- python3 bench.py --num-vars 26 --steps 8 --warmup 2 --no-cpu-baseline --steady-only > $OUT/bench_trace26.log 2>&1
-say trace20; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace20 -- python3 bench.py --num-vars 20 --steps 20 --warmup 5 --no-cpu-baseline --steady-only > $OUT/bench_trace20.log 2>&1
+say trace24; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady-only > $OUT/bench_trace.log 2>&1
+say trace24-nohint; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_nohint -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --steady-only --no-hint > $OUT/bench_trace_nohint.log 2>&1
+say trace26; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace26 -- python3 bench.py --full --num-vars 26 --steps 8 --warmup 2 --no-cpu-baseline --steady-only > $OUT/bench_trace26.log 2>&1
+say trace20; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace20 -- python3 bench.py --full --num-vars 20 --steps 20 --warmup 5 --no-cpu-baseline --steady-only > $OUT/bench_trace20.log 2>&1
 python3 tools/pmc_summary.py --tag "$TAG" --trace $OUT/trace --bench-log $OUT/bench_trace.log
 python3 tools/pmc_summary.py --tag "$TAG" --name-suffix _nohint --trace $OUT/trace_nohint --bench-log $OUT/bench_trace_nohint.log
 python3 tools/pmc_summary.py --tag "$TAG" --name-suffix _2pow26 --trace $OUT/trace26 --bench-log $OUT/bench_trace26.log
