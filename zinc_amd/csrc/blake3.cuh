@@ -15,7 +15,7 @@
 
 // The compression in a fixed instruction order that alternates gfx950's double-rate VOP2 and single-rate VOP3
 // integer opcodes (tools/gen_blake3_sched.py, profiles/round3_valu_issue.md): 3.4 instead of 4.0 issue cycles per
-// instruction.  -DZIPK_B3_COMPILER_SCHED leaves the order to hipcc (A/B measurements).
+// instruction.  (The order left to hipcc, kept for A/B measurements, was removed: profiles/EXPERIMENTS.md.)
 #include "blake3_sched.inc"
 
 namespace zipk {
@@ -80,23 +80,8 @@ __device__ __forceinline__ void blake3_block(const uint32_t (&m)[16], uint32_t b
 }
 
 // One compression of a 64-byte message / of a 32-byte message (words 8..15 zero), in the scheduled order.
-__device__ __forceinline__ void blake3_block64(const uint32_t (&m)[16], uint32_t (&h)[8]) {
-#ifdef ZIPK_B3_COMPILER_SCHED
-    blake3_block(m, 64u, h);
-#else
-    blake3_sched_node(m, h);
-#endif
-}
-__device__ __forceinline__ void blake3_block32(const uint32_t (&m8)[8], uint32_t (&h)[8]) {
-#ifdef ZIPK_B3_COMPILER_SCHED
-    uint32_t m[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) m[i] = i < 8 ? m8[i] : 0u;
-    blake3_block(m, 32u, h);
-#else
-    blake3_sched_half(m8, h);
-#endif
-}
+__device__ __forceinline__ void blake3_block64(const uint32_t (&m)[16], uint32_t (&h)[8]) { blake3_sched_node(m, h); }
+__device__ __forceinline__ void blake3_block32(const uint32_t (&m8)[8], uint32_t (&h)[8]) { blake3_sched_half(m8, h); }
 
 // Parent node = BLAKE3(left.bytes || right.bytes), a plain 64-byte message
 // (NOT BLAKE3's parent-node mode): src/zip/pcs/utils.rs:107-112.

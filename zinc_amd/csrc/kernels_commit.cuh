@@ -146,9 +146,6 @@ __device__ __forceinline__ i128 block_exclusive_scan_i96(i128 total, i128 *wave_
 }
 
 __device__ __forceinline__ void store_hash(uint32_t *dst, const uint32_t (&h)[8]) {
-#ifdef ZIPK_EXP_NOSTORE  // timing build (hipcc -DZIPK_EXP_NOSTORE -o other.so; ZIP_HIP_LIB_PATH=other.so tools/exp_scans_only.py or bench.py): the kernel without its tree stores
-    if (h[0] != 0x12345678u || h[1] != 0x9ABCDEF0u) return;
-#endif
     uint4 *d = reinterpret_cast<uint4 *>(dst);
     d[0] = make_uint4(h[0], h[1], h[2], h[3]);
     d[1] = make_uint4(h[4], h[5], h[6], h[7]);
@@ -282,9 +279,6 @@ struct StridedLeaves {
         if (MASKED && !(smask & (1u << E0))) return;
         const uint32_t j = base + E0 * T + tid;
         const uint32_t s = (uint32_t)((int32_t)d2 >> 31);
-#ifdef ZIPK_EXP_NOSTORE
-        if (d0 != 0x12345678u || d1 != 0x9ABCDEF0u) return;
-#endif
         if (MODE == kStorePacked) {
             const uint32_t pos = pbase<E0>() + lanes_below(__builtin_amdgcn_ballot_w64(true));
             *reinterpret_cast<uint4 *>(pk_v + (size_t)pos * 64) = make_uint4(d0, d1, d2, s);
@@ -389,11 +383,7 @@ __device__ __forceinline__ void bfly_hash(Src &src, uint32_t (&h)[8]) {
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             const uint32_t snd = up ? A[i] : B[i];
-#ifdef ZIPK_EXP_NOXCHG  // timing experiment: the butterfly without its lane exchanges (wrong trees)
-            const uint32_t rcv = snd ^ 0x5A5A5A5Au;
-#else
             const uint32_t rcv = __shfl_xor(snd, 1 << (LVL - 1), 64);
-#endif
             m[i] = up ? rcv : A[i];      // left child
             m[8 + i] = up ? B[i] : rcv;  // right child
         }
@@ -500,10 +490,8 @@ struct ChunkFinisher {
         if (!a.chunk_done) return;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) {
-#ifndef ZIPK_EXP_NOFENCE  // timing experiment only (the gather may then read stale lines)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the write-back has landed before the count moves
-#endif
             __hip_atomic_fetch_add(&a.chunk_done[index], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
@@ -554,10 +542,8 @@ struct ChunkFinisher {
         // the oldest wave of a SIMD with 12 + 3 compressions per lane and chunk and the load latencies between them --
         // more than its ~45 us lead: it became the last wave of that row; twelve or sixteen take the work to the
         // youngest waves, which have no lead to spend (step 1.477 with 8 against 1.491 / 1.527 / 1.544 ms with 4 / 12 / 16).
-#ifndef ZIPK_FIN_WAVES
-#define ZIPK_FIN_WAVES 8u
-#endif
-        const uint32_t W = T >= 64u * ZIPK_FIN_WAVES ? ZIPK_FIN_WAVES : T >= 256u ? 4u : (T + 63u) / 64u;
+        constexpr uint32_t kFinWaves = 8u;
+        const uint32_t W = T >= 64u * kFinWaves ? kFinWaves : T >= 256u ? 4u : (T + 63u) / 64u;
         if (wave >= W) return;
         const uint32_t cw = a.cw, depth = 31u - __builtin_clz(cw);
         uint32_t lvl = p_lvl, j = 0, owner = 0;
@@ -601,7 +587,6 @@ struct ChunkFinisher {
         const uint32_t tid = lane + 64u * wave;
         const uint32_t w_in0 = cw >> (p_lvl - 1u);           // nodes per row at the level below p_lvl
         const uint32_t n_in0 = p_nrows * w_in0;
-#ifndef ZIPK_NO_LDS_TOP
         if (p_lvl <= depth && (n_in0 + n_in0 / 2u) * 32u <= lds_bytes && n_in0 >= 2u) {
             constexpr uint32_t NW = kNodeWords<ILV>;
             pending = false;
@@ -640,7 +625,6 @@ struct ChunkFinisher {
             if (wave == 0u) publish(a, p_index, lane);
             return;
         }
-#endif
         after_hash(a, wave, lane, T);
     }
 
@@ -661,13 +645,8 @@ struct ChunkFinisher {
         // A chunk with a next row hands ALL its upper levels to after_hash() of that row: no barrier here, the waves keep
         // their stagger (every wave drains its stores before the next row's last scan barrier: top_of_row()).  The LAST
         // chunk (and a tree with nothing above the butterflies) pays the head's stage now, all lanes at work, and
-        // after_loop() the rest.  (-DZIPK_HEAD_AT_END: every chunk the round-3 way, for A/B runs.)
-#ifdef ZIPK_HEAD_AT_END
-        const bool now = true;
-#else
+        // after_loop() the rest.  (The round-3 way, every chunk paying its head here, was removed: EXPERIMENTS.md.)
         const bool now = last || lvl > depth;
-#endif
-#ifndef ZIPK_EXP_NOFINISH  // timing experiment (tools/wg_spread.py): what do the upper levels cost?
         if (now) {
             __syncthreads();  // every wave's nodes of level first_level - 1 are in L2
             if (lvl <= depth) {  // the head: one stage with every lane at work
@@ -676,10 +655,6 @@ struct ChunkFinisher {
                 lvl += nl;
             }
         }
-#else
-        __syncthreads();
-        lvl = depth + 1;
-#endif
         if (depth == 0 && tid == 0) {  // a one-leaf tree: the root is the leaf hash
             for (uint32_t ri = 0; ri < nrows_c; ri++) {
                 const uint32_t r = round_slot(blockIdx.x, gridDim.x, a.classes) + (first + ri) * gridDim.x;
@@ -765,7 +740,7 @@ __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
     // the re-read indices waited for every store of the previous row's hash phase to be acknowledged, on the critical
     // path of every row: a timing build without the stores runs 0.095 ms faster, and with the indices in registers the
     // kernel takes 1.271 instead of 1.289 ms alone, 1.376-1.382 instead of 1.410-1.419 ms in the step, the step
-    // 1.528-1.537 instead of 1.564-1.574 ms (alternated four times).  (-DZIPK_PIDX_REREAD: the round-3 form, for A/B runs.)
+    // 1.528-1.537 instead of 1.564-1.574 ms (alternated four times).  (The round-3 form was removed: EXPERIMENTS.md.)
     // The unpacking is kept inside the row loop (`^ z`, an opaque 0): hoisted, it is 16 more registers (109).
     uint32_t pidx[E];
     auto load_pidx = [&](uint32_t t) {
@@ -780,9 +755,7 @@ __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
             pidx[e] = v1 | (v2 << 16);
         }
     };
-#ifndef ZIPK_PIDX_REREAD
     load_pidx(tid0);
-#endif
     // ... the lane's store mask under an opening hint ...
     const uint32_t smask = (MASKED && active) ? store_mask<E>(a.need, cw, 0u, a.nact, tid0) : 0xFFFFFFFFu;
     // ... and (packed openings) the wave's base ranks, wave-uniform
@@ -841,16 +814,9 @@ __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
             const int64_t *nin = a.evals + (size_t)(row + gridDim.x) * row_len;
 #pragma unroll
             for (int k = 0; k < NPF; k++) nxt[k] = nin[k * T + tid];
-#ifdef ZIPK_EXP_NONXT  // timing experiment: no prefetch of the next witness row (every row computes on stale data)
-#pragma unroll
-            for (int k = 0; k < NPF; k++) nxt[k] = (int64_t)(k + z);
-#endif
         }
 
         i128 v[E];
-#ifdef ZIPK_PIDX_REREAD
-        load_pidx(tid);  // (`tid` is opaque: the loads stay inside the loop)
-#endif
         // ---- pass 1: repeat + permute(pi1) + accumulate ------------------------
         if (active) {
 #pragma unroll
@@ -915,10 +881,6 @@ __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
         fin.top_of_row();
         lds_barrier();
         ZIPK_PH(ph_a);
-#ifdef ZIPK_EXP_SCANS_ONLY  // timing build (-DZIPK_EXP_SCANS_ONLY, tools/exp_scans_only.py): a row without its hash phase and chunk ends
-        if (tid0 == 0 && a.roots) a.roots[row * 8] = (uint32_t)t2lo[0];
-        continue;
-#endif
         if (active) {
             StridedLeaves<E, MODE, true> src;
             src.out_row = out_row;

@@ -200,7 +200,6 @@ struct WideAcc {
     // between a VALU write of a carry register and the VALU read of it: the second product and one s_nop fill them.
     template <int J>
     __device__ __forceinline__ void mad2(uint32_t x, uint32_t y0, uint32_t y1) {
-#ifndef ZIPK_COMBINE_C_ARITH
         uint64_t carry0;
         asm("v_mad_u64_u32 %0, %4, %5, %6, %0\n\t"
             "v_mad_u64_u32 %1, vcc, %5, %7, %1\n\t"
@@ -210,14 +209,6 @@ struct WideAcc {
             : "+v"(lo[J]), "+v"(lo[J + 1]), "+v"(top[J]), "+v"(top[J + 1]), "=&s"(carry0)
             : "s"(x), "v"(y0), "v"(y1)
             : "vcc");
-#else
-        const uint64_t p0 = (uint64_t)x * y0, p1 = (uint64_t)x * y1;
-        const uint64_t s0 = lo[J] + p0, s1 = lo[J + 1] + p1;
-        top[J] += s0 < p0 ? 1u : 0u;
-        top[J + 1] += s1 < p1 ? 1u : 0u;
-        lo[J] = s0;
-        lo[J + 1] = s1;
-#endif
     }
     template <int J>
     __device__ __forceinline__ void add(uint64_t x) {
@@ -256,10 +247,7 @@ __device__ __forceinline__ void mad_words(WideAcc<N> &acc, const uint32_t (&x)[N
     }
 }
 
-#ifndef ZIPK_COMBINE_UNROLL
-#define ZIPK_COMBINE_UNROLL 4
-#endif
-constexpr int kCombineUnroll = ZIPK_COMBINE_UNROLL;
+constexpr int kCombineUnroll = 4;
 template <int FL, bool DO_INT, bool DO_FIELD, bool QUIRK>
 __global__ void __launch_bounds__(256) combine_rows_kernel(CombineArgs a) {
     if (a.prio) __builtin_amdgcn_s_setprio(3);
@@ -753,88 +741,6 @@ __global__ void __launch_bounds__(256) open_columns_stream_kernel(OpenColsArgs a
         *reinterpret_cast<oc_u128_a8 *>(dst) = o;
     }
 }
-
-// The openings with as few MEMORY INSTRUCTIONS as they can be made with (round 3, second attempt).  What a gather costs
-// the VALU-bound commit kernel beside it is its vector-memory and LDS instructions (~35 SIMD cycles of hashing each,
-// EXPERIMENTS.md), not its VALU ones: the first "lean" kernel (fewest VALU instructions, but split loads, an 8-byte
-// header store and four dword stores for a sign word: 32 memory instructions per wave and 32 rows) slowed the commit
-// kernel MORE than open_columns_kernel with its LDS image (16).  Here every lane that has a role issues exactly ONE
-// 16-byte load and ONE 16-byte store per row, nothing else: 8 memory instructions per wave and 32 rows.
-//   h < 2 depth      half (h & 1) of the level-(h >> 1) sibling: 16 bytes from the tree / the packed block to the record
-//   h == 2 depth     the record's first 16 bytes: be64(depth), then the first 8 bytes of the level-0 sibling -- it loads
-//                    what lane 0 loads (one request in the TA) and stores [header | low half]; lane 0 writes the same 8
-//                    bytes again
-//   h == 2 depth + 1 the value's low 16 bytes      h == 2 depth + 2: its high 16 bytes (a compact entry's sign word
-//                    four times: three register moves)
-// No LDS, no barrier; 8-byte-aligned records: global_store_dwordx4 at dword alignment; the walk over the rows is one
-// 64-bit add each for the source and the destination pointer; four rows in flight per lane.
-template <int SLOTS>
-__global__ void __launch_bounds__(256) open_columns_lean_kernel(OpenColsArgs a) {
-    constexpr uint32_t K = 4;               // Int<4> column values (checked by zip_ctx_create)
-    constexpr uint32_t RPP = 256 / SLOTS;   // rows per pass of the block
-    if (a.prio) __builtin_amdgcn_s_setprio(2);
-    const uint32_t ci = a.order ? a.order[blockIdx.x] : blockIdx.x;
-    const uint32_t col = a.cols[ci];
-    const uint32_t d = a.depth, cw2 = 2u * a.cw;
-    const uint32_t rec_bytes = 8 + 32 * d;
-    const size_t col_bytes = (size_t)a.num_rows * (8 * K + rec_bytes);
-    uint8_t *base = a.out + (size_t)ci * col_bytes;
-    const uint32_t r0 = a.row_lo + blockIdx.y * a.rows_per_block;
-    const uint32_t r1 = min(r0 + a.rows_per_block, a.row_hi);
-    const uint32_t nrows = r1 - r0;
-    const uint32_t h = threadIdx.x & (SLOTS - 1), rsub = threadIdx.x / SLOTS;
-    if (h > 2 * d + 2) return;
-    const bool is_hdr = h == 2 * d, is_val = h > 2 * d;
-    const uint32_t half = is_val ? h - 2 * d - 1 : is_hdr ? 0u : (h & 1u);
-    const uint32_t lvl = (is_hdr || is_val) ? 0u : h >> 1;
-    const uint32_t row = r0 + rsub;
-    const bool val_hi_compact = is_val && half && a.compact_rows;
-    // source: a tree node (or its packed copy), or the column's row entry
-    const uint8_t *src;
-    size_t src_step;
-    if (is_val) {
-        if (a.compact_rows) {
-            src = reinterpret_cast<const uint8_t *>(a.rows + ((size_t)row * a.cw + col) * 2);
-            src_step = (size_t)RPP * a.cw * 16;
-        } else {
-            src = reinterpret_cast<const uint8_t *>(a.rows + ((size_t)row * a.cw + col) * K + half * 2);
-            src_step = (size_t)RPP * a.cw * 8 * K;
-        }
-    } else {
-        const uint32_t node = cw2 - (cw2 >> lvl) + ((col >> lvl) ^ 1u);
-        src = reinterpret_cast<const uint8_t *>(a.layers + ((size_t)row * cw2 + node) * 4) + half * 16u;
-        src_step = (size_t)RPP * cw2 * 32;
-    }
-    uint8_t *dst = is_val ? base + (size_t)row * 8 * K + half * 16
-                          : base + (size_t)a.num_rows * 8 * K + (size_t)row * rec_bytes + (is_hdr ? 0u : 8u + h * 16u);
-    const size_t dst_step = is_val ? (size_t)RPP * 8 * K : (size_t)RPP * rec_bytes;
-    const uint64_t hdr = __builtin_bswap64((uint64_t)d);
-    const uint32_t hdr_lo = (uint32_t)hdr, hdr_hi = (uint32_t)(hdr >> 32);
-    const uint32_t full = nrows / RPP, rest = nrows % RPP;  // wave-uniform: the loops below are scalar loops
-    auto passes = [&](auto n_tag) {
-        constexpr int N = decltype(n_tag)::value;
-        uint4 v[N];
-#pragma unroll
-        for (int k = 0; k < N; k++) v[k] = *reinterpret_cast<const uint4 *>(src + k * src_step);
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            uint4 o = v[k];
-            if (is_hdr) o = make_uint4(hdr_lo, hdr_hi, v[k].x, v[k].y);
-            if (val_hi_compact) o = make_uint4(v[k].w, v[k].w, v[k].w, v[k].w);
-            oc_u128_a8 w;
-            w.x = ((uint64_t)o.y << 32) | o.x;
-            w.y = ((uint64_t)o.w << 32) | o.z;
-            *reinterpret_cast<oc_u128_a8 *>(dst + k * dst_step) = w;
-        }
-        src += N * src_step;
-        dst += N * dst_step;
-    };
-    uint32_t p = 0;
-    for (; p + 4 <= full; p += 4) passes(std::integral_constant<int, 4>{});
-    for (; p < full; p++) passes(std::integral_constant<int, 1>{});
-    if (rsub < rest) passes(std::integral_constant<int, 1>{});
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------
 // The openings of a PACKED commitment (zip_commit_hinted / zip_commit_open, round 4): everything an opening reads is

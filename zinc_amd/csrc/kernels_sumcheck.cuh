@@ -341,14 +341,15 @@ __global__ void __launch_bounds__(256) sumcheck_round_kernel(SumcheckRoundArgs<F
 }
 
 // ---- degree 3 (the first sumcheck of ZincProver: (M0 z * M1 z - M2 z) * eq) with FOUR LANES PER POINT ------------------
-// sumcheck_round_kernel<4, 4, 3> holds four (2 FL + 1)-limb accumulators and both table entries of four MLEs per thread:
-// 210 VGPRs, two waves per SIMD -- and with ONE wave per SIMD it takes 1.7x as long (tools/exp_sumcheck_occupancy.py): it
-// is bound by the latency of its dependent multiply chains, not by the VALU.  Here the four evaluation points 0..3 of a
-// hypercube point b are the four lanes of a quad: a lane keeps ONE accumulator and the K values at ITS point
-// (v0, v1, v1 + step, v1 + 2 step: the same canonical residues the reference's running sum produces, prover.rs:128-150),
-// <= 128 VGPRs, four waves per SIMD.  The lanes of a quad read the same table entries (one cache line, one request); in a
-// folding round lane k folds MLE k (fix_variables, dense.rs:142-168) and the quad shares the folded pairs with DPP
-// quad_perm broadcasts, so no multiplication is done twice.  Same partials layout and last-block fold as above.
+// sumcheck_round_kernel<4, 4, 3> holds four (2 FL + 1)-limb accumulators and both table entries of four MLEs per
+// thread: 210 VGPRs, two waves per SIMD -- and with ONE wave per SIMD it takes 1.7x as long (measured by padding its
+// LDS, a path since removed: EXPERIMENTS.md): it is bound by the latency of its dependent multiply chains, not by the
+// VALU.  Here the four evaluation points 0..3 of a hypercube point b are the four lanes of a quad: a lane keeps ONE
+// accumulator and the K values at ITS point (v0, v1, v1 + step, v1 + 2 step: the same canonical residues the
+// reference's running sum produces, prover.rs:128-150), <= 128 VGPRs, four waves per SIMD.  The lanes of a quad read the
+// same table entries (one cache line, one request); in a folding round lane k folds MLE k (fix_variables,
+// dense.rs:142-168) and the quad shares the folded pairs with DPP quad_perm broadcasts, so no multiplication is done
+// twice.  Same partials layout and last-block fold as above.
 template <int KK>
 __device__ __forceinline__ uint64_t quad_bcast(uint64_t x) {
     constexpr int CTRL = KK * 0x55;  // quad_perm:[KK, KK, KK, KK]

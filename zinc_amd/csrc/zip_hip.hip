@@ -10,6 +10,7 @@
 #include <chrono>
 #include <thread>
 
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +40,15 @@ typedef unsigned __int128 u128;
 // ------------------------------------------------------------------ small utils
 bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
 uint32_t ilog2(uint64_t x) { return 63u - (uint32_t)__builtin_clzll(x); }
+
+// An integer knob from the environment: `def` when it is unset, not a number or outside [lo, hi].
+long env_long(const char *name, long def, long lo, long hi) {
+    const char *e = getenv(name);
+    if (!e) return def;
+    char *end = nullptr;
+    const long v = strtol(e, &end, 10);
+    return end == e || v < lo || v > hi ? def : v;
+}
 
 struct KernelStat {
     uint32_t launches = 0;
@@ -92,8 +102,8 @@ struct HintPlan {
 // caller then keeps its device witness valid and unchanged until the handle is freed).  ZIP_HIP_SPECULATE=0 / 1
 // sets the process-wide default to 0 / 2.
 static inline int speculation_default_flag() {
-    const char *e = getenv("ZIP_HIP_SPECULATE");
-    return !e ? 1 : atoi(e) == 0 ? 0 : 2;
+    const long v = env_long("ZIP_HIP_SPECULATE", -1, 0, 1);
+    return v < 0 ? 1 : v == 0 ? 0 : 2;
 }
 
 struct zip_ctx {
@@ -106,7 +116,7 @@ struct zip_ctx {
     // chunk, and `stream` everything else (row combinations, column openings, copies).  Per-chunk
     // events let the memory-bound column gather of chunk k overlap the VALU-bound hashing of
     // chunk k+1.
-    hipStream_t stream = nullptr, s_commit = nullptr, s_upper = nullptr, s_aux = nullptr, s_gather2 = nullptr;
+    hipStream_t stream = nullptr, s_commit = nullptr, s_upper = nullptr;
     uint32_t n_chunks = 1;
     uint32_t num_cus = 256;
     uint32_t *timeout_flag_h = nullptr, *timeout_flag_d = nullptr;  // pinned: a pipeline wait gave up
@@ -267,7 +277,7 @@ int32_t fail(zip_ctx *ctx, int32_t code, const char *fmt, ...) {
 // of a 2 ms commit + open, half of a late sumcheck round.  So: poll the completion signal (hipStreamQuery /
 // hipEventQuery read it from memory) for up to ZIP_HIP_SPIN_US microseconds (default 4000; 0 = never), then block.
 static long spin_budget_us() {
-    static const long us = getenv("ZIP_HIP_SPIN_US") ? atol(getenv("ZIP_HIP_SPIN_US")) : 4000;
+    static const long us = env_long("ZIP_HIP_SPIN_US", 4000, 0, LONG_MAX);
     return us;
 }
 // hipErrorNotReady may be left behind as the thread's "last error" by a poll: the launch checks must not find it --
@@ -582,7 +592,7 @@ void parallel_memcpy(void *dst, const void *src, size_t bytes) {
         memcpy(dst, src, bytes);
         return;
     }
-    static const unsigned n_env = getenv("ZIP_HIP_COPY_THREADS") ? (unsigned)atoi(getenv("ZIP_HIP_COPY_THREADS")) : 0u;
+    static const unsigned n_env = (unsigned)env_long("ZIP_HIP_COPY_THREADS", 0, 0, INT_MAX);
     unsigned n = std::thread::hardware_concurrency();
     n = n_env ? std::min(n_env, 64u) : n ? std::min(n, 8u) : 4u;
     const size_t per = (((bytes + n - 1) / n) + 4095) & ~(size_t)4095;  // n * per >= bytes (a truncating bytes / n lost a tail of < n bytes)
@@ -812,20 +822,16 @@ int32_t launch_commit(zip_ctx *ctx, const CommitArgs &a, uint32_t threads, uint3
     return ZIP_OK;
 }
 
-// raa_commit16_kernel (t2 compacted into LDS, T threads x 16 entries): cw = 16384 with T = 1024, cw = 8192 with T = 512
-template <uint32_t T, bool HASH, int MODE = kStoreAll>
-int32_t launch_commit16_t(zip_ctx *ctx, const CommitArgs &a, uint32_t grid, hipStream_t st) {
+// raa_commit16_kernel (t2 compacted into LDS, T threads x 16 entries): cw = 16384 with T = 1024
+template <bool HASH, int MODE = kStoreAll>
+int32_t launch_commit16(zip_ctx *ctx, const CommitArgs &a, uint32_t grid, hipStream_t st) {
+    constexpr uint32_t T = 1024;
     auto kern = raa_commit16_kernel<T, HASH, MODE>;
     if (int32_t rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), c16_lds_bytes(T))) return rc;
     LaunchTimer t(ctx, HASH ? "raa_commit_kernel" : "raa_encode_kernel", st);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(T), c16_lds_bytes(T), st, a);
     HIP_TRY(ctx, hipGetLastError());
     return ZIP_OK;
-}
-template <bool HASH, int MODE = kStoreAll>
-int32_t launch_commit16(zip_ctx *ctx, const CommitArgs &a, uint32_t grid, hipStream_t st) {
-    return a.cw == 16384 ? launch_commit16_t<1024, HASH, MODE>(ctx, a, grid, st)
-                         : launch_commit16_t<512, HASH, MODE>(ctx, a, grid, st);
 }
 
 struct CommitGeom {
@@ -835,13 +841,9 @@ struct CommitGeom {
 CommitGeom commit_geom(uint32_t cw, uint32_t row_len) {
     CommitGeom g{};
     if (cw == 16384) { g.e = 16; g.threads = 1024; g.lds = c16_lds_bytes(1024); return g; }
-    // cw = 8192, opt-in (ZIP_HIP_WIDE=1): two 512-thread workgroups of the 16-entry kernel per CU instead of one
-    // 1024-thread workgroup of the 8-entry kernel.  Measured, round 2: 1.57 ms against 1.53 ms alone at 2^24; round 3
-    // (fixed BLAKE3 order, deferred chunk ends): 1.29 against 1.35 ms ALONE -- the second workgroup does fill the
-    // other's scan passes now -- but 1.99-2.17 against 1.76-1.79 ms per STEP with any chunk schedule and any of the three
-    // gather kernels: it leaves the gathers 7 KB of LDS, and beside them it runs at 1.52-1.98 ms (EXPERIMENTS.md).
-    static const bool wide = getenv("ZIP_HIP_WIDE") && atoi(getenv("ZIP_HIP_WIDE")) == 1;
-    if (cw == 8192 && row_len == 4096 && wide) { g.e = 16; g.threads = 512; g.lds = c16_lds_bytes(512); return g; }
+    // (cw = 8192 as two 512-thread workgroups of the 16-entry kernel per CU was measured and removed: 1.29 against
+    // 1.35 ms alone at 2^24, but 1.99-2.17 against 1.76-1.79 ms per step -- it leaves the gathers 7 KB of LDS,
+    // EXPERIMENTS.md.)
     if (cw >= 512) { g.e = 8; g.threads = cw / 8; }
     else if (cw == 256) { g.e = 4; g.threads = 64; }
     else if (cw == 128) { g.e = 2; g.threads = 64; }
@@ -877,8 +879,7 @@ constexpr size_t kHintTables = 8192, kHintBytes = kHintTables + 8 * (8192 / 32) 
 // kernel recovers it as a per-wave base (wave_tab) + the number of storing lanes of the class below it.  For the
 // 8-entries-per-thread kernel that enumeration is plain index order.
 static bool packed_enabled() {
-    const char *e = getenv("ZIP_HIP_PACKED");  // (read per call: the tests flip it)
-    return !(e && atoi(e) == 0);
+    return env_long("ZIP_HIP_PACKED", 1, 0, 1) != 0;  // (read per call: the tests flip it)
 }
 static void plan_packed(HintPlan &P) {
     const uint32_t cw = P.cw, wv = (cw + 31) / 32, w1 = (cw / 2 + 31) / 32;
@@ -1068,23 +1069,16 @@ struct CombineOut {
     uint8_t *row_be = nullptr;      // device
 };
 
-// The per-chunk partial sums of one combination.  Scratch's invariant is "every consumer is enqueued on
-// ctx->stream"; a combination launched on ANOTHER stream (zip_open's `tail` placement on s_aux) therefore
-// keeps its blocks in a CombineScratch of the caller's scope, whose destructor first waits for that stream --
-// on the early error returns too -- before the blocks go back to the pool.
+// The per-chunk partial sums of one combination: a caller that runs the two phases apart keeps them here between
+// the calls.  Like every Scratch, its consumers are all enqueued on ctx->stream.
 struct CombineScratch {
-    zip_ctx *ctx;
-    hipStream_t drain = nullptr;  // stream the kernels using the blocks were enqueued on, if not ctx->stream
     Scratch pint, pa, pb;
-    explicit CombineScratch(zip_ctx *c) : ctx(c), pint(c), pa(c), pb(c) {}
-    ~CombineScratch() {
-        if (drain) (void)stream_wait(drain);
-    }
+    explicit CombineScratch(zip_ctx *c) : pint(c), pa(c), pb(c) {}
 };
 
 // coeffs_d / q0_d: DEVICE pointers (already staged)
 template <int FL>
-int32_t run_combine_fl(zip_ctx *ctx, hipStream_t st, const int64_t *evals_d, const int64_t *coeffs_dv,
+int32_t run_combine_fl(zip_ctx *ctx, const int64_t *evals_d, const int64_t *coeffs_dv,
                        const uint64_t *q0_dv, const HostField *hf, bool do_int, bool do_field, const CombineOut &out,
                        CombineScratch *ext, int phase) {
     // phase 0: both kernels; 1: only the pass over the witness (partial sums into `ext`); 2: only the fold of the
@@ -1100,9 +1094,9 @@ int32_t run_combine_fl(zip_ctx *ctx, hipStream_t st, const int64_t *evals_d, con
     const uint32_t rpc = (R + chunks - 1) / chunks;
     chunks = (R + rpc - 1) / rpc;
 
+    const hipStream_t st = ctx->stream;
     CombineScratch own(ctx);
     CombineScratch &cs = ext ? *ext : own;
-    if (st != ctx->stream) cs.drain = st;
     Scratch &pint = cs.pint, &pa = cs.pa, &pb = cs.pb;
     int32_t rc;
     CombineArgs a{};
@@ -1110,8 +1104,7 @@ int32_t run_combine_fl(zip_ctx *ctx, hipStream_t st, const int64_t *evals_d, con
     a.num_rows = R;
     a.row_len = C;
     a.rows_per_chunk = rpc;
-    static const int combine_prio = getenv("ZIP_HIP_COMBINE_PRIO") ? atoi(getenv("ZIP_HIP_COMBINE_PRIO")) : 1;
-    a.prio = (uint32_t)combine_prio;
+    a.prio = 1;
     a.quirk_mod = hf ? hf->quirk_mod : 0;
     if (do_int) {
         if (phase != 2 && (rc = pint.get((size_t)chunks * C * 3 * 8))) return rc;
@@ -1172,13 +1165,12 @@ int32_t run_combine_fl(zip_ctx *ctx, hipStream_t st, const int64_t *evals_d, con
 
 int32_t run_combine(zip_ctx *ctx, const int64_t *evals_d, const int64_t *coeffs_dv, const uint64_t *q0_dv,
                     const HostField *hf, bool do_int, bool do_field, const CombineOut &out,
-                    hipStream_t st = nullptr, CombineScratch *ext = nullptr, int phase = 0) {
-    if (!st) st = ctx->stream;
+                    CombineScratch *ext = nullptr, int phase = 0) {
     const uint32_t fl = hf ? hf->fl : 4;
     switch (fl) {
-        case 2: return run_combine_fl<2>(ctx, st, evals_d, coeffs_dv, q0_dv, hf, do_int, do_field, out, ext, phase);
-        case 3: return run_combine_fl<3>(ctx, st, evals_d, coeffs_dv, q0_dv, hf, do_int, do_field, out, ext, phase);
-        default: return run_combine_fl<4>(ctx, st, evals_d, coeffs_dv, q0_dv, hf, do_int, do_field, out, ext, phase);
+        case 2: return run_combine_fl<2>(ctx, evals_d, coeffs_dv, q0_dv, hf, do_int, do_field, out, ext, phase);
+        case 3: return run_combine_fl<3>(ctx, evals_d, coeffs_dv, q0_dv, hf, do_int, do_field, out, ext, phase);
+        default: return run_combine_fl<4>(ctx, evals_d, coeffs_dv, q0_dv, hf, do_int, do_field, out, ext, phase);
     }
 }
 
@@ -1242,7 +1234,8 @@ int32_t run_open_columns(zip_commitment *c, const uint32_t *cols_dv, uint32_t n_
     // Rows per workgroup: 32, or fewer where the LDS image of 32 path records would not fit beside the persistent
     // commit workgroups of this geometry -- the gather is meant to run BESIDE them (at cw = 16384 the commit kernel
     // leaves 11.5 KB per CU and 32 records are 14.6 KB: the gathers then only started when the commit ended).
-    static const uint32_t knob_rpb = getenv("ZIP_HIP_GATHER_RPB") ? (uint32_t)atoi(getenv("ZIP_HIP_GATHER_RPB")) : 0u;
+    // (ZIP_HIP_GATHER_RPB: a test hook; each path below takes it only within its own range)
+    static const uint32_t knob_rpb = (uint32_t)env_long("ZIP_HIP_GATHER_RPB", 0, 2, 4096);
     uint32_t rpb = 32u;
     const size_t rec = 8 + 32 * (size_t)ctx->depth;  // bytes of one record in the LDS image
     size_t free_lds = 0;
@@ -1261,16 +1254,15 @@ int32_t run_open_columns(zip_commitment *c, const uint32_t *cols_dv, uint32_t n_
         // 2^24, round 3) -- unless another job is in flight on the ctx (zip_commit_open_begin: the NEXT job's commit kernel
         // is then resident when this gather runs, and 40 KB of LDS would wait for that kernel to end).  The row-interleaved
         // gather of a packed handle is the other way round: alone, 32 rows per workgroup take 0.094 ms per launch, 64
-        // 0.106, 96 0.120, 128 0.166 (tools/exp_r4_alone_gather.sh), and the step ends 27 us sooner with 32 for the last
-        // chunk too (1.559-1.561 against 1.580-1.594 ms, alternated three times): no bump there.
+        // 0.106, 96 0.120, 128 0.166 (measured by a script since removed: EXPERIMENTS.md), and the step ends 27 us
+        // sooner with 32 for the last chunk too (1.559-1.561 against 1.580-1.594 ms, alternated three times): no bump.
         if (alone && !c->packed && rpb == 32 && row_hi - row_lo >= 96 && 96 * rec <= 48u * 1024u && !(ctx->job_busy[0] || ctx->job_busy[1])) rpb = 96;
     }
     a.rows_per_block = (row_hi - row_lo) < rpb ? (row_hi - row_lo) : rpb;
-    static const int knob_prio = getenv("ZIP_HIP_GATHER_PRIO") ? atoi(getenv("ZIP_HIP_GATHER_PRIO")) : 1;
-    a.prio = (uint32_t)knob_prio;
+    a.prio = 1;
     // Where the commit kernel leaves little LDS (cw = 16384: 16 records per workgroup):
     // the kernel without an LDS image.  ZIP_HIP_GATHER_STREAM=1 / 0 forces it on / off.
-    static const int knob_stream = getenv("ZIP_HIP_GATHER_STREAM") ? atoi(getenv("ZIP_HIP_GATHER_STREAM")) : -1;
+    static const long knob_stream = env_long("ZIP_HIP_GATHER_STREAM", -1, 0, 1);
     const bool stream = knob_stream >= 0 ? knob_stream == 1 : rpb < 32;
     if (c->packed) {
         // a packed commitment: everything row-interleaved in groups of four (open_columns_ilv_kernel); blocks of whole
@@ -1298,23 +1290,9 @@ int32_t run_open_columns(zip_commitment *c, const uint32_t *cols_dv, uint32_t n_
         HIP_TRY(ctx, hipGetLastError());
         return ZIP_OK;
     }
-    // ZIP_HIP_GATHER_LEAN=1: the kernel with the fewest VALU instructions (many rows per workgroup, no LDS, no data
-    // selects).  Opt-in: beside the commit kernel it is the slower choice -- 1.92-2.01 against 1.80-1.85 ms per step,
-    // the commit kernel 1.64-1.72 instead of 1.57 ms: what a gather costs the hashing waves is its VECTOR-MEMORY
-    // instructions (it has four times as many as the LDS-image kernel below), not its VALU ones (EXPERIMENTS.md).
-    static const int knob_lean = getenv("ZIP_HIP_GATHER_LEAN") ? atoi(getenv("ZIP_HIP_GATHER_LEAN")) : 0;
-    if (knob_lean && ctx->depth >= 1 && 2 * ctx->depth + 3 <= 64) {
-        const uint32_t want = (knob_rpb >= 2 && knob_rpb <= 4096) ? knob_rpb : 128u;
-        a.rows_per_block = (row_hi - row_lo) < want ? (row_hi - row_lo) : want;
-        const dim3 grid(n_cols, (row_hi - row_lo + a.rows_per_block - 1) / a.rows_per_block), block(256);
-        LaunchTimer t(ctx, "open_columns_kernel", st);
-        if (2 * ctx->depth + 3 <= 32)
-            hipLaunchKernelGGL(open_columns_lean_kernel<32>, grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL(open_columns_lean_kernel<64>, grid, block, 0, st, a);
-        HIP_TRY(ctx, hipGetLastError());
-        return ZIP_OK;
-    }
+    // (A gather with the fewest memory instructions, many rows per workgroup and no LDS, was measured and removed:
+    // beside the commit kernel it was the slower choice, 1.92-2.01 against 1.80-1.85 ms per step -- what a gather costs
+    // the hashing waves is its VECTOR-MEMORY instructions, not its VALU ones (EXPERIMENTS.md).)
     if (stream && ctx->depth >= 1 && 2 * ctx->depth + 3 <= 64) {
         const uint32_t want = (knob_rpb >= 2 && knob_rpb <= 4096) ? knob_rpb : 32u;
         a.rows_per_block = (row_hi - row_lo) < want ? (row_hi - row_lo) : want;
@@ -1348,24 +1326,13 @@ int32_t run_open_columns_pipelined(zip_commitment *c, const uint32_t *cols_dv, u
         return run_open_columns(c, cols_dv, n_cols, out_d, 0, ctx->rows_local, 0, nullptr, /*alone=*/true);
     }
     if (c->zeroed) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, c->zeroed, 0));
-    // The gathers of consecutive chunks do not depend on each other, only each on ITS chunk.  ZIP_HIP_GATHER_STREAMS=2
-    // alternates them between two streams, so that the next chunk's wait + gather is already in place when a gather
-    // ends (two dependent launches in one stream cost ~28 us per chunk boundary).  Measured (round 3): WORSE, 1.96-2.00
-    // against 1.88 ms per step on one box -- gathers that overlap each other take longer in sum (1.9 against 1.26 ms of
-    // kernel time per step) and slow the commit kernel more.  One stream is the default.
-    static const bool two_streams = getenv("ZIP_HIP_GATHER_STREAMS") && atoi(getenv("ZIP_HIP_GATHER_STREAMS")) == 2;
-    hipStream_t gs[2] = {ctx->stream, (two_streams && ctx->s_gather2 && c->bounds.size() > 2) ? ctx->s_gather2 : ctx->stream};
-    if (gs[1] != gs[0]) {
-        hipEvent_t fork = take_dep_event(ctx);
-        c->aux.push_back(fork);
-        HIP_TRY(ctx, hipEventRecord(fork, ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(gs[1], fork, 0));
-    }
+    // The gathers of consecutive chunks do not depend on each other, only each on ITS chunk, but they stay on one
+    // stream: alternating two streams was measured WORSE (round 3), 1.96-2.00 against 1.88 ms per step on one box --
+    // gathers that overlap each other take longer in sum and slow the commit kernel more (path removed: EXPERIMENTS.md).
     // test hook: an unreachable target and a 1 ms limit exercise the recovery path of a timed-out wait
     // (a value > 1 is the limit in ticks of the 100 MHz clock: short enough and the gathers run BEFORE their rows exist)
-    const char *force_env = getenv("ZIP_HIP_FORCE_WAIT_TIMEOUT");
-    const bool force_timeout = force_env != nullptr;
-    const unsigned long long force_ticks = (force_env && atoll(force_env) > 1) ? (unsigned long long)atoll(force_env) : 100000ull;
+    const bool force_timeout = getenv("ZIP_HIP_FORCE_WAIT_TIMEOUT") != nullptr;
+    const unsigned long long force_ticks = (unsigned long long)env_long("ZIP_HIP_FORCE_WAIT_TIMEOUT", 100000, 2, LONG_MAX);
     auto wait_for = [&](hipStream_t st, uint32_t *counter, uint32_t target) -> int32_t {
         LaunchTimer t(ctx, "wait_counter_kernel", st);
         hipLaunchKernelGGL(wait_counter_kernel, dim3(1), dim3(64), 0, st, counter, force_timeout ? 0xFFFFFFFFu : target, 0u,
@@ -1374,18 +1341,11 @@ int32_t run_open_columns_pipelined(zip_commitment *c, const uint32_t *cols_dv, u
         return ZIP_OK;
     };
     for (size_t k = 0; k + 1 < c->bounds.size(); k++) {
-        hipStream_t st = gs[k & 1];
-        int32_t rc = wait_for(st, c->chunk_done + k, c->expected[k]);
+        int32_t rc = wait_for(ctx->stream, c->chunk_done + k, c->expected[k]);
         if (rc) return rc;
-        rc = run_open_columns(c, cols_dv, n_cols, out_d, c->bounds[k], c->bounds[k + 1], 0, st,
+        rc = run_open_columns(c, cols_dv, n_cols, out_d, c->bounds[k], c->bounds[k + 1], 0, ctx->stream,
                               /*alone=*/k + 2 == c->bounds.size());
         if (rc) return rc;
-    }
-    if (gs[1] != gs[0]) {
-        hipEvent_t join = take_dep_event(ctx);
-        c->aux.push_back(join);
-        HIP_TRY(ctx, hipEventRecord(join, gs[1]));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, join, 0));
     }
     return ZIP_OK;
 }
@@ -1629,17 +1589,12 @@ int32_t launch_sumcheck_round(zip_sumcheck *s, const SumcheckRoundArgs<FL> &a, u
         // 1.45 ms at 2^24): it stays on the one-thread-per-point kernel.  Degree 2 (ZincProver's second sumcheck) leaves
         // the fourth lane of a quad idle: slower in the big rounds (0.96 against 0.57 ms in round 2 of 2^24), faster from
         // 2^16 points down (the last rounds: 32 against 49 us).  ZIP_HIP_SUMCHECK_QUAD=0 / 2: never / every round.
-        const char *knob = getenv("ZIP_HIP_SUMCHECK_QUAD");  // (per call: the tests flip it)
-        const int mode = knob ? atoi(knob) : 1;
+        const long mode = env_long("ZIP_HIP_SUMCHECK_QUAD", 1, 0, 2);  // (per call: the tests flip it)
         const bool pays = a.fold && (DEG == 3 || a.half <= 65536u);
         if (mode == 2 || (mode == 1 && pays)) return launch_sumcheck_quad<FL, K, DEG>(s, a, fd);
     }
-    size_t lds = (size_t)256 * (DEG + 1) * FL * 8;
-    // (occupancy experiment, tools/exp_sumcheck_occupancy.py: extra dynamic LDS so that fewer workgroups fit a CU)
-    if (const char *pad = getenv("ZIP_HIP_SUMCHECK_LDS_PAD")) {
-        lds += (size_t)atoi(pad);
-        if (int32_t rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(sumcheck_round_kernel<FL, K, DEG>), lds)) return rc;
-    }
+    // (extra dynamic LDS to lower the occupancy was an experiment, since removed: EXPERIMENTS.md)
+    const size_t lds = (size_t)256 * (DEG + 1) * FL * 8;
     // a big round runs as exactly the workgroups that are resident together (grid-stride loop inside): a grid of
     // 8 per CU with 3 resident left a third wave of workgroups two thirds full
     if (blocks > ctx->num_cus) {
@@ -1928,12 +1883,9 @@ int32_t zip_ctx_create(const zip_params *p, zip_ctx **out) {
         // fill whatever wave slots / LDS the big commit workgroups leave free
         int prio_lo = 0, prio_hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);  // numerically lower = higher priority
-        if (getenv("ZIP_HIP_NO_PRIORITY")) prio_hi = prio_lo;
         if (hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio_lo) != hipSuccess ||
             hipStreamCreateWithPriority(&ctx->s_commit, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-            hipStreamCreateWithPriority(&ctx->s_upper, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-            hipStreamCreateWithPriority(&ctx->s_aux, hipStreamNonBlocking, prio_lo) != hipSuccess ||
-            hipStreamCreateWithPriority(&ctx->s_gather2, hipStreamNonBlocking, prio_lo) != hipSuccess) {
+            hipStreamCreateWithPriority(&ctx->s_upper, hipStreamNonBlocking, prio_hi) != hipSuccess) {
             rc = ZIP_ERR_HIP;
             break;
         }
@@ -1962,11 +1914,7 @@ int32_t zip_ctx_create(const zip_params *p, zip_ctx **out) {
         }
         // pipeline chunks: the persistent commit kernel publishes its rows in this many groups
         // (0 = chosen per commit from the number of rounds; ZIP_HIP_CHUNKS overrides)
-        ctx->n_chunks = 0;
-        if (const char *env = getenv("ZIP_HIP_CHUNKS")) {
-            const long v = strtol(env, nullptr, 10);
-            if (v >= 1 && v <= 64) ctx->n_chunks = (uint32_t)v;
-        }
+        ctx->n_chunks = (uint32_t)env_long("ZIP_HIP_CHUNKS", 0, 1, 64);
         const size_t pb = (size_t)p->codeword_len * 4;
         if (hipMalloc((void **)&ctx->perm1_d, pb) != hipSuccess || hipMalloc((void **)&ctx->perm2_d, pb) != hipSuccess) {
             rc = ZIP_ERR_ALLOC;
@@ -1991,8 +1939,6 @@ void zip_ctx_destroy(zip_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->s_commit) (void)stream_wait(ctx->s_commit);
     if (ctx->s_upper) (void)stream_wait(ctx->s_upper);
-    if (ctx->s_aux) (void)stream_wait(ctx->s_aux);
-    if (ctx->s_gather2) (void)stream_wait(ctx->s_gather2);
     if (ctx->stream) (void)stream_wait(ctx->stream);
     ctx->hint_plan.reset();  // (its device block goes back to the pool that is torn down next)
     *ctx->alive = false;
@@ -2011,8 +1957,6 @@ void zip_ctx_destroy(zip_ctx *ctx) {
     for (auto e : ctx->dep_event_pool) (void)hipEventDestroy(e);
     if (ctx->s_commit) (void)hipStreamDestroy(ctx->s_commit);
     if (ctx->s_upper) (void)hipStreamDestroy(ctx->s_upper);
-    if (ctx->s_aux) (void)hipStreamDestroy(ctx->s_aux);
-    if (ctx->s_gather2) (void)hipStreamDestroy(ctx->s_gather2);
     if (ctx->stage_big) (void)hipHostFree(ctx->stage_big);
     for (auto *h : ctx->hint_free) (void)hipHostFree(h);
     for (auto *h : ctx->job_stage)
@@ -2045,8 +1989,6 @@ int32_t zip_ctx_synchronize(zip_ctx *ctx) {
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
     if (ctx->s_commit) HIP_TRY(ctx, stream_wait(ctx->s_commit));
     if (ctx->s_upper) HIP_TRY(ctx, stream_wait(ctx->s_upper));
-    if (ctx->s_aux) HIP_TRY(ctx, stream_wait(ctx->s_aux));
-    if (ctx->s_gather2) HIP_TRY(ctx, stream_wait(ctx->s_gather2));
     HIP_TRY(ctx, stream_wait(ctx->stream));
     return check_timeout(ctx);
 }
@@ -2211,7 +2153,7 @@ static int32_t commit_impl(zip_ctx *ctx, const int64_t *evals, size_t n_evals, z
         // profiles/EXPERIMENTS.md), so the gain is the one gather that overlaps.  Default two; ZIP_HIP_CLASSES=1: off.
         uint32_t classes = 1;
         {
-            const int knob_classes = getenv("ZIP_HIP_CLASSES") ? atoi(getenv("ZIP_HIP_CLASSES")) : 0;  // (per call: the tests flip it)
+            const long knob_classes = env_long("ZIP_HIP_CLASSES", 0, 1, 64);  // (per call: the tests flip it)
             const uint32_t per_cu = commit_wgs_per_cu(geom);
             if (with_merkle && hint_cols && commit_supports_hint(cw) && rounds == 1 && R == G && per_cu >= 2 && G % 8 == 0 &&
                 !ctx->n_chunks && knob_classes != 1) {
@@ -2393,7 +2335,7 @@ int32_t zip_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, zip_mem_k
     if (c->hinted && !c->evals && c->evals_ref) {  // a DEVICE witness of the caller's: its digest, beside the commit kernel
         if (pool_alloc(ctx, 16, (void **)&c->digest_d) == ZIP_OK) {
             const size_t n = (size_t)ctx->rows_local * ctx->p.row_len;
-            if (launch_witness_digest(ctx, c->evals_ref, n, c->digest_d, ctx->s_upper) == ZIP_OK) {  // (not s_aux: the fold of the row combinations waits there)
+            if (launch_witness_digest(ctx, c->evals_ref, n, c->digest_d, ctx->s_upper) == ZIP_OK) {
                 c->digest_done = take_dep_event(ctx);
                 (void)hipEventRecord(c->digest_done, ctx->s_upper);
             }
@@ -2748,13 +2690,10 @@ size_t zip_proof_len(const zip_ctx *ctx, uint32_t n_cols, uint32_t field_limbs) 
 // outlive the launches), open_finish waits for it; open_device is the two together.
 struct OpenState {
     Scratch small;
-    // declared last = destroyed first: on every path the combination enqueued on s_aux has drained before `small`
-    // (its inputs) and its own partial sums go back to the pool
-    CombineScratch cscr;
     const uint32_t *cols_dv = nullptr;
     uint32_t n_cols = 0;
     uint8_t *openings_d = nullptr;
-    explicit OpenState(zip_ctx *c) : small(c), cscr(c) {}
+    explicit OpenState(zip_ctx *c) : small(c) {}
 };
 constexpr size_t kJobStageBytes = (size_t)1 << 20;
 
@@ -2770,7 +2709,6 @@ static int32_t open_enqueue(zip_commitment *c, const int64_t *evals_d, const int
     o.uprime = single ? nullptr : reinterpret_cast<uint64_t *>(out_d);
     o.row_be = out_d + u_bytes + col_bytes;
     Scratch &small = st.small;
-    CombineScratch &cscr = st.cscr;
     SmallInputs si;
     if (!single) {
         si.src[0] = coeffs;
@@ -2780,9 +2718,8 @@ static int32_t open_enqueue(zip_commitment *c, const int64_t *evals_d, const int
     si.bytes[1] = (size_t)ctx->rows_local * hf.fl * 8;
     si.src[2] = cols;
     si.bytes[2] = (size_t)n_cols * 4;
-    static const bool sorted_gather = !(getenv("ZIP_HIP_GATHER_ORDER") && atoi(getenv("ZIP_HIP_GATHER_ORDER")) == 0);
     std::vector<uint32_t> order;
-    if (sorted_gather && n_cols > 1) {
+    if (n_cols > 1) {
         order.resize(n_cols);
         gather_order(cols, n_cols, order.data());
         si.src[3] = order.data();
@@ -2810,61 +2747,17 @@ static int32_t open_enqueue(zip_commitment *c, const int64_t *evals_d, const int
     st.cols_dv = reinterpret_cast<const uint32_t *>(sb + si.off[2]);
     st.n_cols = n_cols;
     st.openings_d = out_d + u_bytes;
-    // The two row combinations do not depend on the commitment.  Where to put them (ZIP_HIP_COMBINE):
-    //   first (default) both kernels on the main stream ahead of the gathers -- the stream would otherwise idle until
-    //                   the commit kernel publishes its first chunk, and with s_setprio they are not starved by the
-    //                   hashing waves: 0.07 + 0.02 ms there (round 3's kernels: 64 / 77 VGPRs and 9 KB of LDS, both
-    //                   fit beside the commit workgroups).  1.676 / 1.718 / 1.725 against 1.710 / 1.732 / 1.735 ms
-    //                   per step for `split`, alternated on one box;
-    //   split           the pass over the witness first, the fold of its partial sums LAST on its own stream once the
-    //                   commit kernel has ended (the default while the fold needed 126 VGPRs and could not start
-    //                   before);
-    //   tail            both on their own stream, held back until the commit kernel has ended: beside the gather of
-    //                   the last chunk (round 1's default);
-    //   last            after the gathers, alone;
-    //   aux             on their own stream from the start.
-    static const char *combine_env = getenv("ZIP_HIP_COMBINE");
-    static const int place = !combine_env ? 0 : !strcmp(combine_env, "aux") ? 1 : !strcmp(combine_env, "first") ? 0 :
-                             !strcmp(combine_env, "last") ? 2 : !strcmp(combine_env, "tail") ? 3 :
-                             !strcmp(combine_env, "split") ? 4 : 0;
+    // The two row combinations do not depend on the commitment: both kernels go on the main stream ahead of the
+    // gathers -- the stream would otherwise idle until the commit kernel publishes its first chunk, and with s_setprio
+    // they are not starved by the hashing waves: 0.07 + 0.02 ms there (round 3's kernels: 64 / 77 VGPRs and 9 KB of
+    // LDS, both fit beside the commit workgroups).  1.676 / 1.718 / 1.725 against 1.710 / 1.732 / 1.735 ms per step
+    // for the fold of the partial sums last, alternated on one box.  (The other placements -- the fold last, both on
+    // a stream of their own, held back until the commit kernel ends, or after the gathers -- were removed:
+    // EXPERIMENTS.md.)
     const int64_t *coeffs_dv = reinterpret_cast<const int64_t *>(sb + si.off[0]);
     const uint64_t *q0_dv = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
-    hipEvent_t staged = take_dep_event(ctx), combined = take_dep_event(ctx);
-    c->aux.push_back(staged);
-    c->aux.push_back(combined);
-    if (place == 0) {
-        if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o))) return rc;
-    } else if (place == 4) {
-        if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o, nullptr, &cscr, 1))) return rc;
-        HIP_TRY(ctx, hipEventRecord(staged, ctx->stream));  // the partial sums exist
-    } else if (place == 1 || place == 3) {
-        HIP_TRY(ctx, hipEventRecord(staged, ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, staged, 0));
-        // tail: held back until the commit kernel has ended, so that it runs beside the gather of the LAST
-        // chunk (memory-bound, nothing left to hash) instead of beside the commit
-        if (place == 3 && c->done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, c->done, 0));
-        if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o, ctx->s_aux, &cscr))) return rc;
-        HIP_TRY(ctx, hipEventRecord(combined, ctx->s_aux));
-    }
-    if ((rc = run_open_columns_pipelined(c, reinterpret_cast<const uint32_t *>(sb + si.off[2]), n_cols,
-                                         out_d + u_bytes)))
-        return rc;
-    if (place == 2) {
-        if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o))) return rc;
-    } else if (place == 4 && c->done) {
-        // the fold of the partial sums on its own stream, as soon as the commit kernel has ended (only then do its
-        // 126 VGPRs fit on a CU): beside the gather of the last chunk instead of behind it
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, staged, 0));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_aux, c->done, 0));
-        if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o, ctx->s_aux, &cscr, 2))) return rc;
-        HIP_TRY(ctx, hipEventRecord(combined, ctx->s_aux));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, combined, 0));
-    } else if (place == 4) {
-        if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o, nullptr, &cscr, 2))) return rc;
-    } else if (place == 1 || place == 3) {
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, combined, 0));
-    }
-    return ZIP_OK;
+    if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o))) return rc;
+    return run_open_columns_pipelined(c, st.cols_dv, n_cols, st.openings_d);
 }
 // synchronises: the small host inputs (coeffs, cols, q0) have been consumed, every launch has run
 static int32_t open_finish(zip_commitment *c, OpenState &st, bool force_regather = false) {
@@ -2959,9 +2852,9 @@ int32_t zip_open_shard(zip_commitment *c, const int64_t *evals_d, const int64_t 
     o.row_limbs = row_part_d;
     const int64_t *coeffs_dv = reinterpret_cast<const int64_t *>(sb + si.off[0]);
     const uint64_t *q0_dv = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
-    if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o, nullptr, &cscr, 1))) return rc;
+    if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o, &cscr, 1))) return rc;
     if ((rc = run_open_columns_pipelined(c, cols_dv, n_cols, wire_d))) return rc;
-    if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o, nullptr, &cscr, 2))) return rc;
+    if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o, &cscr, 2))) return rc;
     return recover_gather_timeout(c, cols_dv, n_cols, wire_d);  // (synchronises the stream)
 }
 
@@ -3092,14 +2985,11 @@ int32_t zip_job_wait(zip_job *j, uint8_t *roots_out) {
         // on s_upper, ordered after this job's commit only: the main stream may already hold the NEXT job's whole open
         if (!(rc = wait_ready(j->c, ctx->s_upper))) rc = copy_d2h_bounced(ctx, roots_out, j->c->roots, j->c->roots_bytes, ctx->s_upper);
     }
-    // everything of this job on the main and the fold stream has run: nothing to drain, nothing to wait for
+    // everything of this job on the main stream has run: nothing to drain, nothing to wait for
     const std::string keep = ctx->last_error;
     j->c->gather_order = nullptr;
     j->c->gather_tab = nullptr;
-    if (!rc) {
-        j->st->cscr.drain = nullptr;
-        j->c->consumers_done = true;
-    }
+    if (!rc) j->c->consumers_done = true;
     delete j->st;
     zip_commitment_free(j->c);
     ctx->dep_event_pool.push_back(j->finished);
@@ -3431,12 +3321,12 @@ int32_t zip_mctx_commit_open(zip_mctx *m, const int64_t *evals, const int64_t *c
         // the pass over the witness first (beside the commit's first chunk), the openings, the fold of the partial
         // sums last -- the order zip_open uses
         if ((rc = run_combine(ctx, ev_d, reinterpret_cast<const int64_t *>(sb + si.off[0]),
-                              reinterpret_cast<const uint64_t *>(sb + si.off[1]), &hf, !single, true, o, nullptr,
+                              reinterpret_cast<const uint64_t *>(sb + si.off[1]), &hf, !single, true, o,
                               cscr.back().get(), 1)))
             return finish(mfail(m, rc, "combine", ctx));
         if ((rc = run_open_columns_pipelined(com[s], cols_dv[s], n_cols, m->slice[s]))) return finish(mfail(m, rc, "openings", ctx));
         if ((rc = run_combine(ctx, ev_d, reinterpret_cast<const int64_t *>(sb + si.off[0]),
-                              reinterpret_cast<const uint64_t *>(sb + si.off[1]), &hf, !single, true, o, nullptr,
+                              reinterpret_cast<const uint64_t *>(sb + si.off[1]), &hf, !single, true, o,
                               cscr.back().get(), 2)))
             return finish(mfail(m, rc, "combine", ctx));
         if (hipEventRecord(m->combined[s], ctx->stream) != hipSuccess) return finish(mfail(m, ZIP_ERR_HIP, "event record failed"));
