@@ -63,7 +63,9 @@ typedef struct {
     uint32_t num_vars;     /* log2(poly_size) */
     uint32_t row_len;      /* next_pow2(isqrt(poly_size))            code_raa.rs:43  */
     uint32_t num_rows;     /* next_pow2(poly_size / row_len)         structs.rs:82   */
-    uint32_t codeword_len; /* row_len * rep                          code_raa.rs:113 */
+    uint32_t codeword_len; /* row_len * rep                          code_raa.rs:113
+                            * supported: codeword_len <= 65536 (num_vars <= 30 at rep 2, <= 28 at rep 4);
+                            * larger codewords exceed the 96-bit lanes: ZIP_ERR_UNSUPPORTED */
     uint32_t rep;          /* repetition factor (power of two)       code.rs:235-237 */
     uint32_t n_limbs;      /* ZipTypes::N limbs, must be 1           traits/types.rs:225-240 */
     uint32_t k_limbs;      /* ZipTypes::K limbs, must be 4 */
@@ -128,8 +130,8 @@ void zip_commitment_free(zip_commitment *c);
  * Whatever else is later asked of the handle -- an opening of any other column list (codeword_len >= 512: of
  * anything but exactly `cols`, in that order), zip_commit_download, the rows / layers device pointers -- first
  * re-runs the commit in full from the witness, transparently; for that a DEVICE
- * `evals` must stay valid and unchanged until the handle is freed.  Geometries below codeword_len 512 ignore
- * the hint. */
+ * `evals` must stay valid and unchanged until the handle is freed.  Geometries below codeword_len 512 and above
+ * 16384 ignore the hint (a hinted or packed commit above 16384 is not built): they store everything. */
 /* zip_commit and the opening hint: a ctx whose zip_open / zip_open_stream has named a column list hints its NEXT plain
  * zip_commit calls (with_merkle != 0) with that list on its own -- in the prover's flow (commit, then open on a fresh
  * PcsTranscript: src/zinc/prover.rs:315-320) the columns never change, so the two unchanged calls run at the hinted

@@ -74,6 +74,8 @@ struct CommitArgs {
     // its end into clock[0..3] -- the shader clock the chip actually held during THIS launch (the VALU roofline
     // of bench.py is priced at that clock, not at a datasheet figure)
     unsigned long long *clock;
+    // raa_commit_slab_kernel (cw 32768 / 65536): [gridDim.x][cw] 16-byte entries, one slab per workgroup
+    uint4 *slab;
 #ifdef ZIPK_DEBUG_STAMPS
     // tools/wg_spread.py, tools/ubench_pipeline.hip: kStampRec words per workgroup (100 MHz wall clock):
     // [0] start [1] end [2] XCC id | HW_ID << 8 [3..5] time in the scan passes / hash phase / chunk ends [6] rows done
@@ -91,10 +93,10 @@ __device__ __forceinline__ i128 shfl_up_i96(i128 x, int off) {
     return (i128)(((u128)(uint64_t)hi << 64) | ((u128)d1 << 32) | d0);
 }
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory
-// counter (s_waitcnt vmcnt(0)), i.e. waits for every outstanding global STORE of the wave to be
-// acknowledged; between the passes of a row only LDS data is exchanged, and waiting on the row
-// and hash stores there makes the kernel sensitive to memory latency for nothing.
+// Workgroup barrier that orders LDS traffic only: between the passes of a row only LDS data is exchanged.
+// (On gfx950 __syncthreads() compiles to the same s_waitcnt lgkmcnt(0) + s_barrier: outside threadgroup-split mode
+// its workgroup-scope fences emit no vmcnt wait, as the waves of a workgroup share the CU's vector L1 -- it does NOT
+// wait for the wave's outstanding global stores.  vmem_barrier() below is the barrier that does.)
 __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
@@ -1151,6 +1153,166 @@ __global__ void __launch_bounds__(T, 4) raa_commit16_kernel(CommitArgs a) {
         }
     }
     fin.after_loop(a, wave0, tid0 & 63u, T, smem + 512, (uint32_t)(E * PS * 9u));  // (t2lo + t2dh)
+    stamp_clock(a, 1);
+}
+
+// ---------------------------------------------------------------------------------------
+// cw = 32768 / 65536 (2^27 .. 2^30 at rep 2, 2^25 .. 2^28 at rep 4): 1024 threads x E = cw / 1024 entries.
+// Even the low words of t2 (256 / 512 KB) exceed a CU's LDS, so the first accumulation goes through a SLAB in
+// global memory that the workgroup owns (CommitArgs.slab: cw 16-byte entries, entry j at (j % E) * 1024 + j / E,
+// so that the stores of one wave instruction are contiguous).  A slab holds the thread-LOCAL inclusive sums L[j]
+// (|L| < 2^70); the exclusive prefix P1 of every thread stays in LDS (16 KB), and pass 2 reads t1[i] =
+// slab[i] + P1[i / E].  Values stay within the 96-bit lanes (the width bound of src/zip/code_raa.rs:53-72 is
+// 64 + 2 log2 cw = 96 at cw 65536).
+//   pass 1    gather row[pi1[j] mod row_len] from global memory (the row is L2-resident), local sums -> slab,
+//             block scan of the thread totals -> P1
+//   barrier   vmem_barrier(): s_waitcnt vmcnt(0) + s_barrier -- the slab stores of every wave are complete before
+//             any wave gathers them (the waves of a workgroup share the CU's L1: workgroup scope suffices)
+//   pass 2a   gather t1[pi2[j]] for the thread totals only, block scan -> P2
+//   pass 2b   E / 8 phases: gather the same eight t1 again, running sum from P2, then the output phase of
+//             raa_commit16_kernel (8x8 lane-group transpose, butterfly over levels 0..3 in registers)
+// Levels 4 .. depth go through ChunkFinisher as in the other kernels (vmem_barrier also drains what a chunk end
+// stored before the finishing waves read it back).  The next row's pass 1 rewrites the slab only after the barrier at
+// the top of its row, which every wave reaches after it has consumed its last slab reads of this row.
+// ---------------------------------------------------------------------------------------
+constexpr uint32_t kSlabThreads = 1024;
+constexpr size_t cslab_lds_bytes() {  // wave totals | P1 [1024] x 16 B | running sums [1024] x 16 B | finisher flags
+    return 512 + (size_t)kSlabThreads * 32 + 4 * kFinisherFlagWords;
+}
+
+// Workgroup barrier that also drains the vector-memory counter: every wave's global stores are complete before any
+// wave passes.  (__syncthreads() alone does not wait for them on gfx950: its workgroup-scope fences emit no vmcnt wait
+// outside threadgroup-split mode.)
+__device__ __forceinline__ void vmem_barrier() {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+
+// one 96-bit slab entry (w0, w1, w2, -), sign-extended
+__device__ __forceinline__ i128 slab_get(const uint4 &u) {
+    const int64_t hi = (int64_t)(int32_t)u.z;
+    return (i128)(((u128)(uint64_t)hi << 64) | ((u128)u.y << 32) | u.x);
+}
+
+template <int E, bool HASH>
+__global__ void __launch_bounds__(kSlabThreads, 4) raa_commit_slab_kernel(CommitArgs a) {
+    constexpr uint32_t T = kSlabThreads;
+    constexpr int LOGE = (E == 32) ? 5 : 6;
+    static_assert((1 << LOGE) == E, "E must be 32 or 64");
+    extern __shared__ __align__(16) unsigned char smem[];
+    const uint32_t tid0 = threadIdx.x;
+    const uint32_t cw = a.cw, row_len = a.row_len;  // E T, E T / rep
+    stamp_clock(a, 0);
+
+    i128 *wave_tot = reinterpret_cast<i128 *>(smem);
+    i128 *pre1 = reinterpret_cast<i128 *>(smem + 512);  // [T]: P1 of every thread
+    // [T]: the thread's running sum of pass 2b waits here during the hash phase of a phase (in registers it pushed the
+    // kernel past 128 VGPRs into scratch memory)
+    i128 *runp = pre1 + T;
+    uint4 *slab = a.slab + (size_t)blockIdx.x * cw;
+
+    uint32_t round = 0;
+    ChunkCursor cc;
+    ChunkFinisher<HASH> fin;
+    fin.init(reinterpret_cast<uint32_t *>(runp + T), tid0);
+    const uint32_t wave0 = __builtin_amdgcn_readfirstlane(tid0 >> 6);
+    for (uint32_t row = round_slot(blockIdx.x, gridDim.x, a.classes); row < a.num_rows; row += gridDim.x, round++) {
+        const uint32_t z = opaque_zero(row);
+        const uint32_t tid = tid0 + z;
+        const int64_t *in = a.evals + (size_t)row * row_len;
+        // every wave has consumed its last slab and P1 reads of the previous row.  (This barrier drains no stores: what
+        // ChunkFinisher::top_of_row asks for -- a chunk end's stores complete before after_hash reads them back -- is
+        // done by the vmem_barrier between this row's passes, which every wave passes before its after_hash.)
+        if (round) __syncthreads();
+
+        // ---- pass 1: repeat + permute(pi1) + accumulate, local sums to the slab ----
+        i128 s = 0;
+        {
+            const uint4 *q1 = reinterpret_cast<const uint4 *>(a.perm1 + (size_t)tid * E);
+#pragma unroll 2
+            for (int k = 0; k < E / 4; k++) {
+                const uint4 p = q1[k];
+                const uint32_t idx[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    s += (i128)in[idx[i] & (row_len - 1)];
+                    const u128 u = (u128)s;
+                    slab[(size_t)(4 * k + i) * T + tid] = make_uint4((uint32_t)u, (uint32_t)(u >> 32), (uint32_t)(u >> 64), 0u);
+                }
+            }
+        }
+        pre1[tid] = block_exclusive_scan_i96(s, wave_tot, 0);
+        vmem_barrier();  // the slab stores and P1 of every wave are complete
+
+        // ---- pass 2a: permute(pi2), thread totals ----
+        const uint4 *q2 = reinterpret_cast<const uint4 *>(a.perm2 + (size_t)tid * E);
+        s = 0;
+#pragma unroll 2
+        for (int k = 0; k < E / 4; k++) {
+            const uint4 p = q2[k];
+            const uint32_t idx[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const uint32_t j = idx[i];
+                s += slab_get(slab[(size_t)(j & (E - 1)) * T + (j >> LOGE)]) + pre1[j >> LOGE];
+            }
+        }
+        runp[tid] = block_exclusive_scan_i96(s, wave_tot, 1);
+
+        // ---- pass 2b + output: E / 8 phases of 8 consecutive entries per thread ----
+#pragma unroll 1
+        for (uint32_t q = 0; q < (uint32_t)E / 8u; q++) {
+            // (^ opaque 0 per phase: loop-invariant addresses hoisted out of the phase loop cost registers across the
+            // butterfly, which has none to spare)
+            const uint32_t tq = tid + opaque_zero(q);
+            uint32_t x0[8], x1[8], x2[8];
+            {
+                i128 run = runp[tq];
+                const uint4 *q2q = reinterpret_cast<const uint4 *>(a.perm2 + (size_t)tq * E) + 2 * q;
+                const uint4 pa = q2q[0], pb = q2q[1];
+                const uint32_t idx[8] = {pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, pb.z, pb.w};
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    const uint32_t j = idx[e];
+                    run += slab_get(slab[(size_t)(j & (E - 1)) * T + (j >> LOGE)]) + pre1[j >> LOGE];
+                    const u128 u = (u128)run;
+                    x0[e] = (uint32_t)u;
+                    x1[e] = (uint32_t)(u >> 32);
+                    x2[e] = (uint32_t)(u >> 64);
+                }
+                runp[tq] = run;
+            }
+            transpose8(x0, tq);
+            transpose8(x1, tq);
+            transpose8(x2, tq);
+            StridedLeaves<8> src;
+            src.out_row = a.rows + (size_t)row * cw * (a.compact_rows ? 2 : 4);
+            src.compact = a.compact_rows;
+            src.tree = HASH ? tree_of<false>(a.layers, cw, row) : nullptr;
+            src.cw = cw;
+            src.T = E;  // entry of step s = E s + src.tid: entry 8 q + (lane % 8) of the thread of lane 8 (lane / 8) + s
+            src.tid = (tq & ~7u) * (uint32_t)E + q * 8u + (tq & 7u);
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                src.w0[e] = x0[e];
+                src.w1[e] = x1[e];
+                src.w2[e] = x2[e];
+            }
+            if (HASH) {
+                uint32_t top[8];
+                bfly_hash<3, 0>(src, top);
+            } else {
+                store_rows_only<8, 0>(src);
+            }
+        }
+        fin.after_hash(a, wave0, tid0 & 63u, T);
+        const bool last = row + gridDim.x >= a.num_rows;
+        if (cc.ends_with(a, round, last)) {
+            fin.chunk_end(a, 4u, cc, round, last, tid, T);
+            cc.advance(round);
+        }
+    }
+    fin.after_loop(a, wave0, tid0 & 63u, T, smem + 512, (uint32_t)(T * 32u));  // (P1 + running sums)
     stamp_clock(a, 1);
 }
 

@@ -141,8 +141,13 @@ struct zip_ctx {
     // are gone, its openings then wait for the whole commit instead)
     uint32_t *ring_d = nullptr;
     uint32_t ring_next = 0, ring_epoch = 0;
+    // raa_commit_slab_kernel (cw 32768 / 65536): one slab of cw 16-byte entries per workgroup (CommitArgs.slab),
+    // allocated at the first such commit; every commit kernel of the ctx runs on s_commit, one after the other
+    uint4 *slab_d = nullptr;
+    size_t slab_bytes = 0;
     // zip_commit_open_begin: pinned staging of the jobs in flight (kJobSlots), and which slots are taken
     unsigned char *job_stage[2] = {nullptr, nullptr};
+    size_t job_stage_cap[2] = {0, 0};  // bytes of job_stage[slot] (job_stage_bytes: grows with the rows and the field)
     bool job_busy[2] = {false, false};
     // bumped by every recovery from a timed-out pipeline wait (recover_gather_timeout).  A job enqueued BEFORE a recovery
     // that another job ran cannot tell any more whether its own waits gave up too (the flag is cleared): it re-gathers.
@@ -834,12 +839,25 @@ int32_t launch_commit16(zip_ctx *ctx, const CommitArgs &a, uint32_t grid, hipStr
     return ZIP_OK;
 }
 
+// raa_commit_slab_kernel (first accumulation through a global slab per workgroup): cw = 32768 / 65536, 1024 threads x
+// cw / 1024 entries
+template <bool HASH>
+int32_t launch_commit_slab(zip_ctx *ctx, const CommitArgs &a, uint32_t grid, hipStream_t st) {
+    auto kern = a.cw == 65536 ? raa_commit_slab_kernel<64, HASH> : raa_commit_slab_kernel<32, HASH>;
+    if (int32_t rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), cslab_lds_bytes())) return rc;
+    LaunchTimer t(ctx, HASH ? "raa_commit_kernel" : "raa_encode_kernel", st);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kSlabThreads), cslab_lds_bytes(), st, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return ZIP_OK;
+}
+
 struct CommitGeom {
     uint32_t e, threads;
     size_t lds;
 };
 CommitGeom commit_geom(uint32_t cw, uint32_t row_len) {
     CommitGeom g{};
+    if (cw >= 32768) { g.e = cw / kSlabThreads; g.threads = kSlabThreads; g.lds = cslab_lds_bytes(); return g; }
     if (cw == 16384) { g.e = 16; g.threads = 1024; g.lds = c16_lds_bytes(1024); return g; }
     // (cw = 8192 as two 512-thread workgroups of the 16-entry kernel per CU was measured and removed: 1.29 against
     // 1.35 ms alone at 2^24, but 1.99-2.17 against 1.76-1.79 ms per step -- it leaves the gathers 7 KB of LDS,
@@ -853,6 +871,7 @@ CommitGeom commit_geom(uint32_t cw, uint32_t row_len) {
 }
 // resident workgroups per CU of the commit kernel (threads and LDS)
 uint32_t commit_wgs_per_cu(const CommitGeom &g) {
+    if (g.e > 16) return 1;  // the slab kernel: 1024 threads at up to 128 VGPRs fill a CU's register files
     uint32_t by_threads = 2048 / g.threads, by_lds = (uint32_t)((160u * 1024u) / g.lds);
     uint32_t k = by_threads < by_lds ? by_threads : by_lds;
     if (k > 8) k = 8;
@@ -860,7 +879,9 @@ uint32_t commit_wgs_per_cu(const CommitGeom &g) {
 }
 
 // geometries whose commit kernel has a hint-masked variant (smaller ones store everything: the hint is dropped)
-bool commit_supports_hint(uint32_t cw) { return cw >= 512; }
+// (and above cw 16384 neither: the slab kernel stores everything, and kHintBytes and the u16 rank tables are sized for
+// cw <= 16384 -- a hinted or packed commit there is not built)
+bool commit_supports_hint(uint32_t cw) { return cw >= 512 && cw <= 16384; }
 // one pinned / device block per hinted commit: the bitmaps (<= 5.6 KB for cw <= 16384) at offset 0, the
 // column -> openings tables of zip_commit_open (first[cw] | next[n_cols], u16) at kHintTables
 // (packed openings: the wave table at kHintTables, the ranks of the hinted openings at kPackedRanksAt)
@@ -996,6 +1017,8 @@ int32_t dispatch_commit(zip_ctx *ctx, CommitArgs a, uint32_t grid, hipStream_t s
     }
     a.pk = nullptr;
     switch (g.e) {
+        case 64:
+        case 32: return launch_commit_slab<HASH>(ctx, a, grid, st);
         case 16: return launch_commit16<HASH>(ctx, a, grid, st);
         case 8: return launch_commit<8, HASH>(ctx, a, g.threads, grid, st);
         case 4: return launch_commit<4, HASH>(ctx, a, g.threads, grid, st);
@@ -1850,7 +1873,8 @@ int32_t zip_ctx_create(const zip_params *p, zip_ctx **out) {
         const uint32_t width = 64 * p->n_limbs + nv_even + 2 * ilog2(p->rep);
         if (width > 64 * p->k_limbs) return ZIP_ERR_INVALID_PARAM;
     }
-    if (p->codeword_len > 16384) return ZIP_ERR_UNSUPPORTED;  // 96-bit lanes + one workgroup per row
+    // 96-bit lanes (the width bound is 64 + 2 log2 cw at these geometries) + one workgroup per row
+    if (p->codeword_len > 65536) return ZIP_ERR_UNSUPPORTED;
     if (!p->perm1 || !p->perm2) return ZIP_ERR_NULL;
     const uint32_t rows_local = p->row_count ? p->row_count : p->num_rows;
     if ((uint64_t)p->row_begin + rows_local > p->num_rows) return ZIP_ERR_INVALID_PARAM;
@@ -1962,6 +1986,7 @@ void zip_ctx_destroy(zip_ctx *ctx) {
     for (auto *h : ctx->job_stage)
         if (h) (void)hipHostFree(h);
     if (ctx->ring_d) (void)hipFree(ctx->ring_d);
+    if (ctx->slab_d) (void)hipFree(ctx->slab_d);
     if (ctx->pinned_base) (void)hipHostFree(ctx->pinned_base);
     if (ctx->recycle && ctx->bounce[0] && ctx->bounce[1] && ctx->device >= 0 && ctx->device < kMaxDevices) {
         RecycleBin &bin = g_recycle[ctx->device];
@@ -2278,6 +2303,27 @@ static int32_t commit_impl(zip_ctx *ctx, const int64_t *evals, size_t n_evals, z
                 for (uint32_t k = 0; k < nch; k++) c->expected[k] = G / classes;
         }
         if (e != hipSuccess) { rc = fail(ctx, ZIP_ERR_HIP, "commit setup failed: %s", hipGetErrorString(e)); break; }
+        if (geom.e > 16) {  // raa_commit_slab_kernel: a slab per workgroup, kept by the ctx
+            const size_t need = (size_t)G * cw * 16;
+            if (ctx->slab_bytes < need) {
+                // (an earlier commit kernel may still read the old slab)
+                if (ctx->slab_d && (e = stream_wait(ctx->s_commit)) != hipSuccess) {
+                    rc = fail(ctx, ZIP_ERR_HIP, "commit setup failed: %s", hipGetErrorString(e));
+                    break;
+                }
+                if (ctx->slab_d) (void)hipFree(ctx->slab_d);
+                ctx->slab_d = nullptr;
+                ctx->slab_bytes = 0;
+                if (hipMalloc((void **)&ctx->slab_d, need) != hipSuccess) {
+                    ctx->slab_d = nullptr;
+                    (void)hipGetLastError();
+                    rc = fail(ctx, ZIP_ERR_ALLOC, "hipMalloc(%zu) of the commit slabs failed", need);
+                    break;
+                }
+                ctx->slab_bytes = need;
+            }
+            a.slab = ctx->slab_d;
+        }
         rc = with_merkle ? dispatch_commit<true>(ctx, a, G, ctx->s_commit) : dispatch_commit<false>(ctx, a, G, ctx->s_commit);
         if (rc) break;
         c->args = a;
@@ -2696,10 +2742,21 @@ struct OpenState {
     explicit OpenState(zip_ctx *c) : small(c) {}
 };
 constexpr size_t kJobStageBytes = (size_t)1 << 20;
+// What open_enqueue stages for one job (its SmallInputs, each rounded to 256 bytes as stage_small lays them out: the
+// proximity coefficients, q0, the columns, their gather order and the packed gather table -- counted whether or not
+// the commit turns out packed), at least kJobStageBytes.  2^30 with a 4-limb field: 32768 rows x 40 bytes = 1.3 MB.
+static size_t job_stage_bytes(const zip_ctx *ctx, uint32_t n_cols, uint32_t fl) {
+    auto r = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const bool single = ctx->p.num_rows == 1;
+    size_t t = (single ? 0 : r((size_t)ctx->rows_local * 8)) + r((size_t)ctx->rows_local * fl * 8) + r((size_t)n_cols * 4);
+    if (n_cols > 1) t += r((size_t)n_cols * 4);
+    if (n_cols <= 65536) t += r((size_t)n_cols * 16);
+    return std::max(t, kJobStageBytes);
+}
 
 static int32_t open_enqueue(zip_commitment *c, const int64_t *evals_d, const int64_t *coeffs, const uint32_t *cols,
                             uint32_t n_cols, const uint64_t *q0_mont, const HostField &hf, uint8_t *out_d, OpenState &st,
-                            unsigned char *own_stage = nullptr) {
+                            unsigned char *own_stage = nullptr, size_t own_cap = 0) {
     zip_ctx *ctx = c->ctx;
     int32_t rc;
     const bool single = ctx->p.num_rows == 1;
@@ -2741,7 +2798,7 @@ static int32_t open_enqueue(zip_commitment *c, const int64_t *evals_d, const int
         si.bytes[4] = wg_tab.size() * 4;
     }
     unsigned char *sb;
-    if ((rc = stage_small(ctx, si, small, &sb, own_stage, own_stage ? kJobStageBytes : 0))) return rc;
+    if ((rc = stage_small(ctx, si, small, &sb, own_stage, own_cap))) return rc;
     c->gather_order = order.empty() ? nullptr : reinterpret_cast<const uint32_t *>(sb + si.off[3]);  // (lives in `small`)
     c->gather_tab = wg_tab.empty() ? nullptr : reinterpret_cast<const uint4 *>(sb + si.off[4]);
     st.cols_dv = reinterpret_cast<const uint32_t *>(sb + si.off[2]);
@@ -2927,10 +2984,20 @@ int32_t zip_commit_open_begin(zip_ctx *ctx, const int64_t *evals_d, size_t n_eva
     if ((rc = check_cols(ctx, cols, n_cols))) return rc;
     int slot = !ctx->job_busy[0] ? 0 : !ctx->job_busy[1] ? 1 : -1;
     if (slot < 0) return fail(ctx, ZIP_ERR_INVALID_PARAM, "two jobs are already in flight on this ctx: zip_job_wait one first");
-    if (!ctx->job_stage[slot] &&
-        hipHostMalloc((void **)&ctx->job_stage[slot], kJobStageBytes, hipHostMallocDefault) != hipSuccess) {
+    // the slot's staging block holds this job's small inputs: sized BEFORE the commit is enqueued (a free slot's block
+    // is idle -- its last job has been waited for)
+    const size_t stage_need = job_stage_bytes(ctx, n_cols, hf.fl);
+    if (ctx->job_stage[slot] && ctx->job_stage_cap[slot] < stage_need) {
+        (void)hipHostFree(ctx->job_stage[slot]);
         ctx->job_stage[slot] = nullptr;
-        return fail(ctx, ZIP_ERR_ALLOC, "hipHostMalloc(%zu) failed", kJobStageBytes);
+        ctx->job_stage_cap[slot] = 0;
+    }
+    if (!ctx->job_stage[slot]) {
+        if (hipHostMalloc((void **)&ctx->job_stage[slot], stage_need, hipHostMallocDefault) != hipSuccess) {
+            ctx->job_stage[slot] = nullptr;
+            return fail(ctx, ZIP_ERR_ALLOC, "hipHostMalloc(%zu) failed", stage_need);
+        }
+        ctx->job_stage_cap[slot] = stage_need;
     }
     zip_job *j = new (std::nothrow) zip_job();
     if (!j) return ZIP_ERR_ALLOC;
@@ -2942,7 +3009,9 @@ int32_t zip_commit_open_begin(zip_ctx *ctx, const int64_t *evals_d, size_t n_eva
     }
     j->st = new (std::nothrow) OpenState(ctx);
     if (!j->st) rc = ZIP_ERR_ALLOC;
-    if (!rc) rc = open_enqueue(j->c, evals_d, coeffs, cols, n_cols, q0_mont, hf, proof_out_d, *j->st, ctx->job_stage[slot]);
+    if (!rc)
+        rc = open_enqueue(j->c, evals_d, coeffs, cols, n_cols, q0_mont, hf, proof_out_d, *j->st, ctx->job_stage[slot],
+                          ctx->job_stage_cap[slot]);
     if (!rc) {
         j->finished = take_dep_event(ctx);
         if (hipEventRecord(j->finished, ctx->stream) != hipSuccess) rc = fail(ctx, ZIP_ERR_HIP, "hipEventRecord failed");
