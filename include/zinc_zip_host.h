@@ -36,6 +36,11 @@ uint64_t zinc_transcript_get_u64(zinc_transcript *t);
 void zinc_transcript_get_integer_challenges(zinc_transcript *t, size_t n, int64_t *out);
 /* get_challenge::<RandomField<limbs>>: Montgomery limbs of the challenge */
 int32_t zinc_transcript_get_challenge(zinc_transcript *t, const uint64_t *modulus, uint32_t limbs, uint64_t *out);
+/* The Keccak-256 sponge in transit (the fields of zip_keccak_state, zip_hip.h): st = the 25 state words after every
+ * full block, buf[0 .. *buflen) = the bytes absorbed since (136 bytes of room; zero beyond *buflen on export).
+ * ZINC_ERR_NULL for a NULL argument; import: ZINC_ERR_INVALID_PARAM when buflen >= 136. */
+int32_t zinc_transcript_export(const zinc_transcript *t, uint64_t *st, uint8_t *buf, uint32_t *buflen);
+int32_t zinc_transcript_import(zinc_transcript *t, const uint64_t *st, const uint8_t *buf, uint32_t buflen);
 
 /* field helpers (src/field/config.rs, src/conversion.rs, src/sumcheck/utils.rs) */
 int32_t zinc_field_constants(const uint64_t *modulus, uint32_t limbs, uint64_t *r, uint64_t *r2, uint64_t *inv);

@@ -39,6 +39,8 @@ extern "C" {
 #endif
 
 #define ZIP_HIP_ABI_VERSION 3 /* 3: zip_ctx_set_speculation, zip_open_shard, zip_mctx_roots, zip_mctx_roots_path */
+/* (zip_keccak_state and zip_sumcheck_prove came later and are purely additive: no existing entry point or structure
+ * changed, so the version stays 3; a caller that needs them looks the symbol up.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -332,6 +334,33 @@ int32_t zip_sumcheck_round_begin(zip_sumcheck *s, const uint64_t *r_prev);
 int32_t zip_sumcheck_round_end(zip_sumcheck *s, uint64_t *evaluations_out);
 const char *zip_sumcheck_last_error(const zip_sumcheck *s);
 void zip_sumcheck_free(zip_sumcheck *s);
+
+/* A KeccakTranscript (src/transcript.rs) in transit: Keccak-256 sponge, rate 136.
+ * st: the state after every full block absorbed so far; buf[0 .. buflen): the bytes absorbed since, buflen < 136.
+ * On input bytes at and beyond buflen are ignored; on output they are zero. */
+typedef struct {
+    uint64_t st[25];
+    uint8_t buf[136];
+    uint32_t buflen;
+} zip_keccak_state;
+
+/* MLSumcheck::prove_as_subprotocol (src/sumcheck.rs:56-112) in ONE call on a fresh handle (no round played yet):
+ * absorbs nvars and degree (:64-76), then for every round computes the message, absorbs it (absorb_slice),
+ * squeezes the challenge (get_challenge, transcript.rs:88-133), absorbs it and folds with it.  For this loop, and
+ * only for it, the library owns the transcript.  The last rounds -- from tables of 2^n entries on, n =
+ * ZIP_HIP_SUMCHECK_TAIL or as many as fit the LDS of one workgroup -- run in ONE kernel with the sponge on the
+ * device; the rounds before use the kernels of zip_sumcheck_round and the library steps the sponge on the host.
+ *   transcript      HOST, in/out: the caller's transcript before / after the sumcheck
+ *   msgs_out        HOST, num_vars * (degree + 1) * field->limbs limbs (ProverMsg.evaluations per round)
+ *   randomness_out  HOST, num_vars * field->limbs limbs (ProverState.randomness), Montgomery
+ * ZIP_ERR_INVALID_PARAM (nothing reaches the device): a round already played or in flight on the handle, a second
+ * zip_sumcheck_prove, buflen >= 136.  Afterwards the handle is finished: zip_sumcheck_round* return
+ * "Prover is not active". */
+int32_t zip_sumcheck_prove(zip_sumcheck *s, zip_keccak_state *transcript, uint64_t *msgs_out, uint64_t *randomness_out);
+/* Process-wide, monotonic: rounds played through the round kernels (zip_sumcheck_round_begin, from whichever entry
+ * point) and launches of the tail kernel.  Every path gives the same bytes; tests and tools read the path taken here.
+ * Either pointer may be NULL. */
+void zip_sumcheck_launch_counts(uint64_t *round_kernel_rounds, uint64_t *tail_kernel_launches);
 
 /* ---- the field loops of SpartanProver::prove around its sumchecks (BASELINE configs[4]) ---------
  * A zip_ccs holds the constraint matrices of a CCS (Statement_Z.constraints, src/ccs/ccs_z.rs:155-158,

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "zip_mctx_create", "zip_mctx_destroy", "zip_mctx_last_error", "zip_mctx_shards", "zip_mctx_shard_ctx", "zip_mctx_set_witness",
     "zip_mctx_commit_open", "zip_mctx_shard_openings", "zip_mctx_ends", "zip_mctx_roots", "zip_mctx_roots_path", "zip_verify", "zip_mle_eval", "zip_commitment_mle_eval", "zip_field_map_int256",
     "zip_open_stream", "zip_sumcheck_init", "zip_sumcheck_round", "zip_sumcheck_round_begin", "zip_sumcheck_round_end", "zip_sumcheck_last_error", "zip_sumcheck_free",
+    "zip_sumcheck_prove", "zip_sumcheck_launch_counts",
     "zip_ccs_create", "zip_ccs_free", "zip_ccs_last_error", "zip_ccs_set_z", "zip_ccs_eq_table",
     "zip_ccs_second_table", "zip_ccs_table", "zip_ccs_download", "zip_ccs_eval_matrices",
 )
@@ -108,6 +109,26 @@ VERIFY_MERKLE, VERIFY_MALFORMED, VERIFY_OVERFLOW = 4, 5, 6
 class SumcheckComb(C.Structure):
     """zip_sumcheck_comb: (sum_t coeff[t] * prod_{j in term_mask[t]} vals[j]) * vals[-1]"""
     _fields_ = [("n_terms", C.c_uint32), ("term_mask", C.c_uint32 * 8), ("coeff", (C.c_uint64 * 8) * 8)]
+
+
+class KeccakState(C.Structure):
+    """zip_keccak_state: a KeccakTranscript in transit (Keccak-256 sponge: the state after every full block, and the
+    bytes absorbed since)"""
+    _fields_ = [("st", C.c_uint64 * 25), ("buf", C.c_uint8 * 136), ("buflen", C.c_uint32)]
+
+    @classmethod
+    def make(cls, st=None, buf=b""):
+        k = cls()
+        if st is not None:
+            for i, w in enumerate(st):
+                k.st[i] = int(w)
+        for i, b in enumerate(bytes(buf)):
+            k.buf[i] = b
+        k.buflen = len(buf)
+        return k
+
+    def pending(self) -> bytes:
+        return bytes(self.buf[: self.buflen])
 
 
 def make_comb(term_masks, coeffs_limbs):
@@ -195,6 +216,9 @@ def lib():
     L.zip_sumcheck_round.argtypes = [vp, u64p, u64p]
     L.zip_sumcheck_round_begin.argtypes = [vp, u64p]
     L.zip_sumcheck_round_end.argtypes = [vp, u64p]
+    L.zip_sumcheck_prove.argtypes = [vp, C.POINTER(KeccakState), u64p, u64p]
+    L.zip_sumcheck_launch_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.zip_sumcheck_launch_counts.restype = None
     L.zip_sumcheck_last_error.argtypes = [vp]
     L.zip_sumcheck_last_error.restype = C.c_char_p
     L.zip_sumcheck_free.argtypes = [vp]
@@ -729,12 +753,19 @@ def merkle_trees(leaves, depth, device=0):
     return out
 
 
+def sumcheck_launch_counts():
+    """(rounds played through the round kernels, launches of the sumcheck tail kernel) in this process so far"""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    lib().zip_sumcheck_launch_counts(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
 class Sumcheck:
     """Device prover state of one sumcheck (zip_sumcheck_*): product of the MLEs, or the CCS form `comb`.  mles: list of CUDA int64/uint64 tensors
     (read in place) or one numpy array [K, 2^nv, limbs] (copied)."""
 
     def __init__(self, mles, num_vars, degree, field: ZipField, device=0, comb: "SumcheckComb" = None):
-        self.field, self.degree = field, degree
+        self.field, self.degree, self.num_vars = field, degree, num_vars
         if isinstance(mles, np.ndarray):
             self._keep = np.ascontiguousarray(mles, dtype=np.uint64)
             ptrs = [self._keep[k].ctypes.data for k in range(self._keep.shape[0])]
@@ -758,6 +789,17 @@ class Sumcheck:
         if rc != ZIP_OK:
             raise ZipError(rc, "zip_sumcheck_round", lib().zip_sumcheck_last_error(self._h).decode())
         return out
+
+    def prove(self, state: "KeccakState"):
+        """zip_sumcheck_prove: the whole MLSumcheck::prove_as_subprotocol on a fresh handle.  `state` is the caller's
+        transcript before the sumcheck and is updated in place.  Returns (msgs [nv, degree + 1, limbs],
+        randomness [nv, limbs])."""
+        msgs = np.zeros((self.num_vars, self.degree + 1, self.field.limbs), dtype=np.uint64)
+        rand = np.zeros((self.num_vars, self.field.limbs), dtype=np.uint64)
+        rc = lib().zip_sumcheck_prove(self._h, C.byref(state), msgs.ctypes.data, rand.ctypes.data)
+        if rc != ZIP_OK:
+            raise ZipError(rc, "zip_sumcheck_prove", lib().zip_sumcheck_last_error(self._h).decode())
+        return msgs, rand
 
     def free(self):
         if getattr(self, "_h", None):

@@ -28,6 +28,7 @@
 #include "kernels_open.cuh"
 #include "kernels_verify.cuh"
 #include "kernels_sumcheck.cuh"
+#include "kernels_sumcheck_tail.cuh"
 #include "kernels_spartan.cuh"
 #include "rccl_dyn.h"
 
@@ -226,6 +227,8 @@ struct zip_sumcheck {
     zip_ctx *ctx = nullptr;  // private plumbing context (stream, pool, error text)
     uint32_t n_mles = 0, num_vars = 0, degree = 0, fl = 0, round = 0;
     bool pending = false;  // a round has been enqueued (zip_sumcheck_round_begin) and not yet collected
+    bool proved = false;   // zip_sumcheck_prove has run: the handle is finished
+    uint64_t *tail_out_d = nullptr;  // what sumcheck_tail_kernel writes out (kTailOutBytes)
     const uint64_t *input[4] = {};  // the tables of round 1 (device; owned when `owned`)
     bool owned = false;
     uint64_t *buf[2][4] = {};       // ping-pong fold targets: 2^(nv-1) and 2^(nv-2) entries
@@ -1696,6 +1699,100 @@ int32_t sumcheck_round_fl(zip_sumcheck *s, const uint64_t *r_prev, const HostFie
         case 3: return sumcheck_round_k<FL, 3>(s, a, blocks, fd);
         default: return sumcheck_round_k<FL, 4>(s, a, blocks, fd);
     }
+}
+
+// ---- zip_sumcheck_prove: the transcript of MLSumcheck::prove_as_subprotocol inside the library ---------------------------
+// Messages, challenges and the sponge of at most kTailMaxLog tail rounds
+constexpr size_t kTailOutBytes = ((size_t)kTailMaxLog * (kSumcheckMaxDegree + 2) * 4 + 25 + kKeccakRateWords + 1) * 8;
+
+// Process-wide launch counts of the sumcheck prover (zip_sumcheck_launch_counts: tests and tools tell from them which
+// path a call took -- every path gives the same bytes)
+std::atomic<uint64_t> g_sumcheck_round_launches{0}, g_sumcheck_tail_launches{0};
+
+// the largest n for which K tables of 2^n entries and the kernel's static LDS fit one workgroup
+uint32_t tail_lds_bound(uint32_t n_mles, uint32_t fl) {
+    uint32_t n = 0;
+    while (n < kTailMaxLog && ((size_t)n_mles << (n + 1)) * fl * 8 + kTailFixedLds <= kTailLdsTotal) n++;
+    return n;
+}
+
+template <int FL>
+int32_t sumcheck_prove_fl(zip_sumcheck *s, zip_keccak_state *transcript, uint64_t *msgs_out, uint64_t *randomness_out,
+                          const HostField &hf) {
+    zip_ctx *ctx = s->ctx;
+    const uint32_t nv = s->num_vars, ne = s->degree + 1;
+    // (the sponge on this thread: TrSponge, keccak_dev.cuh -- the serial form of what the tail kernel does)
+    TrSponge sp;
+    memcpy(sp.st, transcript->st, sizeof sp.st);
+    {
+        uint8_t pending[kKeccakRate] = {0};
+        memcpy(pending, transcript->buf, transcript->buflen);
+        memcpy(sp.blk, pending, kKeccakRate);  // little-endian host
+    }
+    sp.buflen = transcript->buflen;
+    const TrField<FL> tf = tr_make_field<FL>(hf.modulus, hf.r2, hf.inv);
+    uint64_t v[2][FL];
+    tr_map_u128<FL>(tf, nv, 0, v[0]);  // sumcheck.rs:64-76
+    tr_map_u128<FL>(tf, s->degree, 0, v[1]);
+    tr_sponge_absorb_fields<FL>(sp, tf, &v[0][0], 2);
+    // The tail plays the last n rounds (tables of 2^n entries in its first).  ZIP_HIP_SUMCHECK_TAIL=n: 0 = no tail
+    // kernel; more than fits the LDS for this shape: as much as fits.  (Per call: the tests flip it.)
+    const uint32_t bound = tail_lds_bound(s->n_mles, FL);
+    const uint32_t knob = (uint32_t)env_long("ZIP_HIP_SUMCHECK_TAIL", bound, 0, kTailMaxLog);
+    const uint32_t n_tail = std::min(std::min(knob, bound), nv);
+    uint64_t r[FL] = {};
+    for (uint32_t round = 0; round < nv - n_tail; round++) {  // the kernels and launch logic of zip_sumcheck_round
+        uint64_t *msg = msgs_out + (size_t)round * ne * FL;
+        if (int32_t rc = zip_sumcheck_round_begin(s, round ? r : nullptr)) return rc;
+        if (int32_t rc = zip_sumcheck_round_end(s, msg)) return rc;
+        tr_sponge_round<FL>(sp, tf, msg, ne, r);  // absorb_slice, get_challenge, absorb the challenge (sumcheck.rs:100-103)
+        memcpy(randomness_out + (size_t)round * FL, r, 8 * FL);
+    }
+    if (n_tail) {
+        SumcheckTailArgs<FL> a{};
+        const uint32_t first = nv - n_tail + 1;  // 1-based round
+        a.n_mles = s->n_mles;
+        a.degree = s->degree;
+        a.fold_first = first > 1;
+        a.log_len = n_tail;
+        a.n_terms = s->n_terms;
+        for (uint32_t t = 0; t < s->n_terms; t++) {
+            a.term_mask[t] = s->term_mask[t];
+            for (int i = 0; i < FL; i++) a.coeff[t][i] = s->coeff[t][i];
+        }
+        for (uint32_t k = 0; k < s->n_mles; k++)  // what round `first` of zip_sumcheck_round would read
+            a.src[k] = first <= 2 ? s->input[k] : s->buf[(first - 3) & 1][k];
+        for (int i = 0; i < FL; i++) a.r[i] = r[i];
+        memcpy(a.st, sp.st, sizeof a.st);
+        memcpy(a.blk, sp.blk, sizeof a.blk);
+        a.buflen = sp.buflen;
+        a.tf = tf;
+        a.out = s->tail_out_d;
+        const size_t lds = ((size_t)s->n_mles << n_tail) * FL * 8;
+        auto kern = sumcheck_tail_kernel<FL>;
+        if (int32_t rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
+        {
+            LaunchTimer t(ctx, "sumcheck_tail_kernel");
+            hipLaunchKernelGGL(kern, dim3(1), dim3(kTailThreads), lds, ctx->stream, a, to_dev<FL>(hf));
+            HIP_TRY(ctx, hipGetLastError());
+            g_sumcheck_tail_launches++;
+        }
+        const size_t n_msg = (size_t)n_tail * ne * FL, n_ch = (size_t)n_tail * FL, n_words = n_msg + n_ch + 25 + kKeccakRateWords + 1;
+        uint64_t host[kTailOutBytes / 8];
+        HIP_TRY(ctx, hipMemcpyAsync(host, s->tail_out_d, n_words * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, stream_wait(ctx->stream));
+        memcpy(msgs_out + (size_t)(nv - n_tail) * ne * FL, host, n_msg * 8);
+        memcpy(randomness_out + (size_t)(nv - n_tail) * FL, host + n_msg, n_ch * 8);
+        const uint64_t *so = host + n_msg + n_ch;
+        memcpy(sp.st, so, sizeof sp.st);
+        memcpy(sp.blk, so + 25, sizeof sp.blk);
+        sp.buflen = (uint32_t)so[25 + kKeccakRateWords];
+        s->round = nv;
+    }
+    memcpy(transcript->st, sp.st, sizeof sp.st);
+    memcpy(transcript->buf, sp.blk, sizeof transcript->buf);  // zero beyond buflen
+    transcript->buflen = sp.buflen;
+    return ZIP_OK;
 }
 
 // ------------------------------------------------------------------ Spartan pieces
@@ -3852,6 +3949,7 @@ int32_t zip_sumcheck_init(int32_t device, const uint64_t *const *mles, zip_mem_k
         if ((rc = pool_alloc(ctx, (size_t)s->max_blocks * (degree + 1) * elem, (void **)&s->partials))) break;
         if ((rc = pool_alloc(ctx, (size_t)(degree + 1) * elem, (void **)&s->evals_d))) break;
         if ((rc = pool_alloc(ctx, 16, (void **)&s->done_d))) break;
+        if ((rc = pool_alloc(ctx, kTailOutBytes, (void **)&s->tail_out_d))) break;
         if (hipMemsetAsync(s->done_d, 0, 16, ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
         if (stream_wait(ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
         bounce_release(ctx);                  // the tables are up: nothing else of this handle goes through them
@@ -3887,6 +3985,7 @@ int32_t zip_sumcheck_round_begin(zip_sumcheck *s, const uint64_t *r_prev) {
         default: rc = sumcheck_round_fl<4>(s, r_prev, hf); break;
     }
     if (rc) return rc;
+    g_sumcheck_round_launches++;
     s->round++;
     s->pending = true;
     return ZIP_OK;
@@ -3923,6 +4022,37 @@ int32_t zip_sumcheck_round(zip_sumcheck *s, const uint64_t *r_prev, uint64_t *ev
     if (!s || !evaluations_out) return ZIP_ERR_NULL;
     const int32_t rc = zip_sumcheck_round_begin(s, r_prev);
     return rc ? rc : zip_sumcheck_round_end(s, evaluations_out);
+}
+
+int32_t zip_sumcheck_prove(zip_sumcheck *s, zip_keccak_state *transcript, uint64_t *msgs_out, uint64_t *randomness_out) {
+    if (!s || !transcript || !msgs_out || !randomness_out) return ZIP_ERR_NULL;
+    zip_ctx *ctx = s->ctx;
+    if (s->proved) return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_sumcheck_prove has already run on this handle");
+    if (s->pending || s->round > 0)
+        return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_sumcheck_prove needs a fresh handle: a round has been played or is in flight");
+    if (transcript->buflen >= kKeccakRate)
+        return fail(ctx, ZIP_ERR_INVALID_PARAM, "transcript buflen %u is not below the Keccak-256 rate (136)", transcript->buflen);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HostField hf;
+    hf.fl = s->fl;
+    memcpy(hf.modulus, s->modulus, sizeof hf.modulus);
+    memcpy(hf.r, s->mont_r, sizeof hf.r);
+    memcpy(hf.r2, s->mont_r2, sizeof hf.r2);
+    hf.inv = s->mont_inv;
+    s->proved = true;  // whatever happens from here on, the handle does not start over
+    int32_t rc;
+    switch (s->fl) {
+        case 2: rc = sumcheck_prove_fl<2>(s, transcript, msgs_out, randomness_out, hf); break;
+        case 3: rc = sumcheck_prove_fl<3>(s, transcript, msgs_out, randomness_out, hf); break;
+        default: rc = sumcheck_prove_fl<4>(s, transcript, msgs_out, randomness_out, hf); break;
+    }
+    if (rc) s->round = s->num_vars;
+    return rc;
+}
+
+void zip_sumcheck_launch_counts(uint64_t *rounds, uint64_t *tails) {
+    if (rounds) *rounds = g_sumcheck_round_launches.load();
+    if (tails) *tails = g_sumcheck_tail_launches.load();
 }
 
 const char *zip_sumcheck_last_error(const zip_sumcheck *s) { return s && s->ctx ? s->ctx->last_error.c_str() : ""; }

@@ -63,6 +63,29 @@ int32_t zinc_transcript_get_challenge(zinc_transcript *t, const uint64_t *modulu
     });
 }
 
+int32_t zinc_transcript_export(const zinc_transcript *t, uint64_t *st, uint8_t *buf, uint32_t *buflen) {
+    if (!t || !st || !buf || !buflen) return ZINC_ERR_NULL;
+    zip_keccak_state k;
+    t->t.export_state(&k);
+    std::memcpy(st, k.st, sizeof k.st);
+    std::memcpy(buf, k.buf, sizeof k.buf);
+    *buflen = k.buflen;
+    return ZINC_OK;
+}
+int32_t zinc_transcript_import(zinc_transcript *t, const uint64_t *st, const uint8_t *buf, uint32_t buflen) {
+    if (!t || !st || !buf) return ZINC_ERR_NULL;
+    if (buflen >= 136) {
+        g_err = "zinc_transcript_import: buflen is not below the Keccak-256 rate (136)";
+        return ZINC_ERR_INVALID_PARAM;
+    }
+    zip_keccak_state k{};
+    std::memcpy(k.st, st, sizeof k.st);
+    std::memcpy(k.buf, buf, buflen);
+    k.buflen = buflen;
+    t->t.import_state(k);
+    return ZINC_OK;
+}
+
 int32_t zinc_field_constants(const uint64_t *modulus, uint32_t limbs, uint64_t *r, uint64_t *r2, uint64_t *inv) {
     return guarded([&] {
         const FieldConfig f = FieldConfig::make(modulus, limbs);

@@ -226,6 +226,20 @@ std::array<uint8_t, 32> Keccak256::finalize() const {
     return out;
 }
 
+void Keccak256::export_state(zip_keccak_state *out) const {
+    std::memcpy(out->st, st_, sizeof st_);
+    std::memset(out->buf, 0, sizeof out->buf);
+    std::memcpy(out->buf, buf_, buflen_);
+    out->buflen = buflen_;
+}
+
+void Keccak256::import_state(const zip_keccak_state &in) {
+    if (in.buflen >= 136) throw std::logic_error("Keccak256::import_state: buflen is not below the rate (136)");
+    std::memcpy(st_, in.st, sizeof st_);
+    std::memcpy(buf_, in.buf, in.buflen);
+    buflen_ = in.buflen;
+}
+
 // ============================================================================ multi-limb helpers
 namespace {
 
@@ -984,10 +998,16 @@ sumcheck::ProverOutput prove_as_subprotocol_impl(KeccakTranscript &transcript, c
                                                  uint32_t nvars, uint32_t degree, const zip_sumcheck_comb *comb,
                                                  const FieldConfig &config, int device,
                                                  zip_mem_kind kind = ZIP_MEM_HOST) {
-    // sumcheck.rs:64-76 (FIELD_LIMBS > 1: the u128 map)
-    transcript.absorb_random_field(config, map_to_field_u128(config, nvars, 0));
-    transcript.absorb_random_field(config, map_to_field_u128(config, degree, 0));
     sumcheck::ProverOutput out;
+    // ZIP_HIP_SUMCHECK_ONECALL=1 (read per call: the tests flip it): the whole loop is ONE zip_sumcheck_prove call --
+    // the library borrows the sponge, the tail of the rounds runs in one kernel (zip_hip.h).  Default (and =0): the
+    // per-round loop with the transcript here, until the end-to-end legs say otherwise (profiles/sumcheck_onecall.md).
+    const char *onecall_env = std::getenv("ZIP_HIP_SUMCHECK_ONECALL");
+    const bool per_round = nvars == 0 || !(onecall_env && onecall_env[0] == '1' && !onecall_env[1]);
+    if (per_round) {  // sumcheck.rs:64-76 (FIELD_LIMBS > 1: the u128 map); zip_sumcheck_prove absorbs them itself
+        transcript.absorb_random_field(config, map_to_field_u128(config, nvars, 0));
+        transcript.absorb_random_field(config, map_to_field_u128(config, degree, 0));
+    }
     if (nvars == 0) return out;  // :77-92: empty proof
     const zip_field zf = config.to_abi();
     zip_sumcheck *raw = nullptr;
@@ -995,6 +1015,25 @@ sumcheck::ProverOutput prove_as_subprotocol_impl(KeccakTranscript &transcript, c
     if (rc) throw ZipError(rc == ZIP_ERR_INVALID_PARAM ? ZipError::InvalidPcsParam : ZipError::Device,
                            std::string("zip_sumcheck_init: ") + zip_strerror(rc));
     std::unique_ptr<zip_sumcheck, void (*)(zip_sumcheck *)> s(raw, zip_sumcheck_free);
+    if (!per_round) {
+        zip_keccak_state st;
+        transcript.export_state(&st);
+        const size_t ne = degree + 1, fl = config.limbs;
+        std::vector<uint64_t> msgs((size_t)nvars * ne * fl), rand((size_t)nvars * fl);
+        rc = zip_sumcheck_prove(s.get(), &st, msgs.data(), rand.data());
+        if (rc) throw ZipError(ZipError::Device, std::string("zip_sumcheck_prove: ") + zip_sumcheck_last_error(s.get()));
+        transcript.import_state(st);
+        for (uint32_t round = 0; round < nvars; round++) {
+            std::vector<Limbs> msg(ne);
+            for (size_t e = 0; e < ne; e++)
+                for (size_t i = 0; i < fl; i++) msg[e][i] = msgs[((size_t)round * ne + e) * fl + i];
+            out.proof.msgs.push_back(std::move(msg));
+            Limbs r{};
+            for (size_t i = 0; i < fl; i++) r[i] = rand[(size_t)round * fl + i];
+            out.randomness.push_back(r);
+        }
+        return out;
+    }
     std::vector<uint64_t> evals((size_t)(degree + 1) * config.limbs);
     Limbs r{};
     for (uint32_t round = 0; round < nvars; round++) {  // :97-106

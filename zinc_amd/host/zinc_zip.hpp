@@ -82,6 +82,9 @@ class Keccak256 {
     void update(const uint8_t *data, size_t len);
     void update(std::initializer_list<uint8_t> bytes) { update(bytes.begin(), bytes.size()); }
     std::array<uint8_t, 32> finalize() const;  // of a clone: the hasher keeps absorbing
+    // the sponge in transit (zip_keccak_state): the state after every full block, and the bytes absorbed since
+    void export_state(zip_keccak_state *out) const;
+    void import_state(const zip_keccak_state &in);  // throws std::logic_error when buflen >= 136
 
   private:
     static void permute(uint64_t st[25]);
@@ -132,6 +135,9 @@ class KeccakTranscript {
         get_integer_challenge(1, &w);
         return w;
     }
+    // zip_sumcheck_prove borrows the transcript for one sumcheck: hand the sponge over, take it back
+    void export_state(zip_keccak_state *out) const { hasher_.export_state(out); }
+    void import_state(const zip_keccak_state &in) { hasher_.import_state(in); }
 
   private:
     Keccak256 hasher_;

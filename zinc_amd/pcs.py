@@ -15,6 +15,7 @@ OK, ERR_INVALID_PARAM, ERR_PANIC, ERR_DEVICE, ERR_NULL, ERR_INVALID_OPEN, ERR_SP
 EXPORTED_SYMBOLS = (
     "zinc_last_error", "zinc_transcript_new", "zinc_transcript_free", "zinc_transcript_absorb",
     "zinc_transcript_get_u64", "zinc_transcript_get_integer_challenges", "zinc_transcript_get_challenge",
+    "zinc_transcript_export", "zinc_transcript_import",
     "zinc_field_constants", "zinc_field_mul", "zinc_map_to_field_i64", "zinc_build_eq_x_r",
     "zinc_shuffle_seeded_perm", "zinc_kat_seed_from_u64", "zinc_raa_code_new", "zinc_zip_setup", "zinc_zip_params_free",
     "zinc_zip_params_geometry", "zinc_zip_commit", "zinc_zip_data_free", "zinc_pcs_transcript_new",
@@ -71,6 +72,8 @@ def lib():
         L.zinc_transcript_get_u64.restype = C.c_uint64
         L.zinc_transcript_get_integer_challenges.argtypes = [vp, C.c_size_t, vp]
         L.zinc_transcript_get_challenge.argtypes = [vp, vp, C.c_uint32, vp]
+        L.zinc_transcript_export.argtypes = [vp, vp, vp, vp]
+        L.zinc_transcript_import.argtypes = [vp, vp, vp, C.c_uint32]
         L.zinc_field_constants.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.zinc_field_mul.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.zinc_map_to_field_i64.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp]
@@ -208,6 +211,22 @@ class KeccakTranscript:
         out = np.zeros(field.limbs, np.uint64)
         _check(lib().zinc_transcript_get_challenge(self._h, field._m.ctypes.data, field.limbs, out.ctypes.data))
         return out
+
+    def state(self):
+        """The Keccak-256 sponge in transit: (st [25] uint64: the state after every full block, buf: the bytes
+        absorbed since) -- the fields of zip_keccak_state, what cabi.Sumcheck.prove borrows."""
+        st, buf, n = np.zeros(25, np.uint64), np.zeros(136, np.uint8), C.c_uint32(0)
+        _check(lib().zinc_transcript_export(self._h, st.ctypes.data, buf.ctypes.data, C.addressof(n)))
+        return st, buf[: n.value].tobytes()
+
+    def set_state(self, state):
+        st, buf = state
+        st = np.ascontiguousarray(st, dtype=np.uint64)
+        if st.shape != (25,):
+            raise ValueError("the Keccak state has 25 words")
+        room = np.zeros(136, np.uint8)
+        room[: min(len(buf), 136)] = np.frombuffer(bytes(buf[:136]), np.uint8)
+        _check(lib().zinc_transcript_import(self._h, st.ctypes.data, room.ctypes.data, len(buf)))
 
 
 def kat_seed_from_u64(seed: int, n_words: int):
