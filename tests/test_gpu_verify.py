@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import _oracle as orc
+from _verify_cases import honest_tuple
 
 pytestmark = pytest.mark.gpu
 
@@ -24,22 +25,7 @@ def cabi():
 
 
 def _instance(num_vars, modulus, fl, seed=0, small=False):
-    z = orc.Zip(num_vars)
-    f = orc.make_field(modulus, fl)
-    n = 1 << num_vars
-    if small:
-        evals = np.random.default_rng(seed).integers(-128, 128, size=n, dtype=np.int64)
-    else:
-        evals = orc.splitmix64(0x5A494E43 + seed, n).copy()
-        evals[: min(n, 3)] = np.array([-(2**63), 2**63 - 1, -1], dtype=np.int64)[: min(n, 3)]
-    point = orc.point_to_field(f, np.random.default_rng(seed + 1).integers(-50, 50, size=num_vars, dtype=np.int64))
-    rows, layers, roots = z.commit(evals)
-    proof, cols, coeffs = z.open(f, evals, rows, layers, point, orc.new_transcript())
-    lr = z.num_rows.bit_length() - 1
-    q0 = orc.build_eq_x_r(f, point[num_vars - lr:]) if lr else None
-    q1 = orc.build_eq_x_r(f, point[: num_vars - lr]) if num_vars - lr else None
-    ev = z.mle_eval(f, evals, point)
-    return z, f, evals, point, roots, proof, cols, coeffs, q0, q1, ev
+    return honest_tuple(num_vars, None, modulus, fl, seed, small)
 
 
 def _verify(cabi, ctx, z, fl, modulus, roots, proof, cols, coeffs, q0, q1, ev):
