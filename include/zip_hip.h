@@ -40,7 +40,8 @@ extern "C" {
 
 #define ZIP_HIP_ABI_VERSION 3 /* 3: zip_ctx_set_speculation, zip_open_shard, zip_mctx_roots, zip_mctx_roots_path */
 /* (zip_keccak_state and zip_sumcheck_prove came later and are purely additive: no existing entry point or structure
- * changed, so the version stays 3; a caller that needs them looks the symbol up.) */
+ * changed, so the version stays 3; a caller that needs them looks the symbol up.  Likewise zip_sumcheck_init taking
+ * up to 8 tables instead of 4: a widening, every call that was valid means what it meant.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -310,9 +311,10 @@ int32_t zip_verify(zip_ctx *ctx, const uint8_t *roots, const uint8_t *proof, zip
  * caller keeps the
  * transcript (MLSumcheck::prove_as_subprotocol, src/sumcheck.rs:56-112: absorb the evaluations, squeeze
  * the challenge, absorb it, hand it to the next round).
- *   mles      n_mles (1..4) tables of 2^num_vars field elements, Montgomery limbs, variable 0 = least
+ *   mles      n_mles (1..8) tables of 2^num_vars field elements, Montgomery limbs, variable 0 = least
  *             significant index bit; HOST tables are copied, DEVICE tables are read in place (never
- *             written) and must outlive the handle
+ *             written) and must outlive the handle.  (A CCS with t matrices needs t + 1: t <= 7.)
+ *   comb      a term_mask with a bit at or above n_mles is ZIP_ERR_INVALID_PARAM
  *   degree    1..4: the round polynomial is returned as its values at 0..degree (ProverMsg.evaluations)
  *   r_prev    the verifier's challenge for the previous round (NULL in round 1): the tables are folded
  *             with it (fix_variables, src/poly_f/mle/dense.rs:142-168) in the same pass

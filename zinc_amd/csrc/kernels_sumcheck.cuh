@@ -21,7 +21,7 @@
 
 namespace zipk {
 
-constexpr int kSumcheckMaxMles = 4;
+constexpr int kSumcheckMaxMles = 8;  // 1..4: the kernels below; 5..8: kernels_sumcheck_wide.cuh
 constexpr int kSumcheckMaxDegree = 4;
 
 template <int FL>

@@ -29,6 +29,7 @@
 #include "kernels_verify.cuh"
 #include "kernels_sumcheck.cuh"
 #include "kernels_sumcheck_tail.cuh"
+#include "kernels_sumcheck_wide.cuh"
 #include "kernels_spartan.cuh"
 #include "rccl_dyn.h"
 
@@ -229,9 +230,9 @@ struct zip_sumcheck {
     bool pending = false;  // a round has been enqueued (zip_sumcheck_round_begin) and not yet collected
     bool proved = false;   // zip_sumcheck_prove has run: the handle is finished
     uint64_t *tail_out_d = nullptr;  // what sumcheck_tail_kernel writes out (kTailOutBytes)
-    const uint64_t *input[4] = {};  // the tables of round 1 (device; owned when `owned`)
+    const uint64_t *input[kSumcheckMaxMles] = {};  // the tables of round 1 (device; owned when `owned`)
     bool owned = false;
-    uint64_t *buf[2][4] = {};       // ping-pong fold targets: 2^(nv-1) and 2^(nv-2) entries
+    uint64_t *buf[2][kSumcheckMaxMles] = {};  // ping-pong fold targets: 2^(nv-1) and 2^(nv-2) entries
     uint64_t *partials = nullptr, *evals_d = nullptr;
     uint32_t *done_d = nullptr;          // arrival counter of the round kernel
     unsigned char *evals_pinned = nullptr;  // host-mapped slot the round message is written to (or null: evals_d + a copy)
@@ -1648,6 +1649,41 @@ int32_t launch_sumcheck_round(zip_sumcheck *s, const SumcheckRoundArgs<FL> &a, u
     return ZIP_OK;
 }
 
+// 5..8 MLEs: eight lanes per hypercube point (sumcheck_round_wide_kernel), every degree and every round; 32 points per
+// workgroup.  The grid is capped like the others (exactly the workgroups that are resident together, grid-stride loop
+// inside) and a small grid folds its partials itself.  ZIP_HIP_SUMCHECK_QUAD does not apply here.
+template <int FL, int K>
+int32_t launch_sumcheck_wide(zip_sumcheck *s, SumcheckRoundArgs<FL> a, const FieldDev<FL> &fd) {
+    zip_ctx *ctx = s->ctx;
+    const size_t lds = (size_t)256 * FL * 8;
+    const uint64_t want = (a.half * kSumcheckWideLanes + 255) / 256;
+    uint32_t blocks = (uint32_t)std::min<uint64_t>(want ? want : 1, s->max_blocks);
+    if (blocks > ctx->num_cus) {
+        static std::mutex mu;
+        static std::map<std::pair<const void *, int>, int> occ;
+        const void *kern = reinterpret_cast<const void *>(sumcheck_round_wide_kernel<FL, K>);
+        std::lock_guard<std::mutex> g(mu);
+        int &per_cu = occ[std::make_pair(kern, ctx->device)];
+        if (per_cu == 0 &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sumcheck_round_wide_kernel<FL, K>, 256, lds) != hipSuccess)
+            per_cu = 0;
+        if (per_cu > 0) blocks = std::min<uint32_t>(blocks, ctx->num_cus * (uint32_t)per_cu);
+    }
+    a.done = blocks <= 64 ? s->done_d : nullptr;
+    {
+        LaunchTimer t(ctx, "sumcheck_round_wide_kernel");
+        hipLaunchKernelGGL((sumcheck_round_wide_kernel<FL, K>), dim3(blocks), dim3(256), lds, ctx->stream, a, fd);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (!a.done) {
+        LaunchTimer t(ctx, "sumcheck_reduce_kernel");
+        hipLaunchKernelGGL(sumcheck_reduce_kernel<FL>, dim3(1), dim3(256), 0, ctx->stream, a.partials, blocks, a.degree + 1, a.evals_out, fd,
+                           a.host_flag, a.seq);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return ZIP_OK;
+}
+
 template <int FL, int K>
 int32_t sumcheck_round_k(zip_sumcheck *s, const SumcheckRoundArgs<FL> &a, uint32_t blocks, const FieldDev<FL> &fd) {
     switch (s->degree) {
@@ -1697,7 +1733,11 @@ int32_t sumcheck_round_fl(zip_sumcheck *s, const uint64_t *r_prev, const HostFie
         case 1: return sumcheck_round_k<FL, 1>(s, a, blocks, fd);
         case 2: return sumcheck_round_k<FL, 2>(s, a, blocks, fd);
         case 3: return sumcheck_round_k<FL, 3>(s, a, blocks, fd);
-        default: return sumcheck_round_k<FL, 4>(s, a, blocks, fd);
+        case 4: return sumcheck_round_k<FL, 4>(s, a, blocks, fd);
+        case 5: return launch_sumcheck_wide<FL, 5>(s, a, fd);
+        case 6: return launch_sumcheck_wide<FL, 6>(s, a, fd);
+        case 7: return launch_sumcheck_wide<FL, 7>(s, a, fd);
+        default: return launch_sumcheck_wide<FL, 8>(s, a, fd);
     }
 }
 
@@ -3895,6 +3935,9 @@ int32_t zip_sumcheck_init(int32_t device, const uint64_t *const *mles, zip_mem_k
     if (n_mles < 1 || n_mles > (uint32_t)kSumcheckMaxMles || degree < 1 || degree > (uint32_t)kSumcheckMaxDegree ||
         num_vars < 1 || num_vars > 30)
         return ZIP_ERR_INVALID_PARAM;  // nvars == 0: "Attempt to prove a constant." (prover.rs:47-49)
+    if (comb)  // a term that refers to an MLE that does not exist
+        for (uint32_t t = 0; t < comb->n_terms; t++)
+            if (comb->term_mask[t] >> n_mles) return ZIP_ERR_INVALID_PARAM;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ZIP_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
@@ -3920,11 +3963,9 @@ int32_t zip_sumcheck_init(int32_t device, const uint64_t *const *mles, zip_mem_k
         if (comb) {
             s->n_terms = comb->n_terms;
             for (uint32_t t = 0; t < comb->n_terms; t++) {
-                if (comb->term_mask[t] >> n_mles) { rc = fail(ctx, ZIP_ERR_INVALID_PARAM, "term %u refers to an MLE that does not exist", t); break; }
                 s->term_mask[t] = comb->term_mask[t];
                 memcpy(s->coeff[t], comb->coeff[t], sizeof s->coeff[t]);
             }
-            if (rc) break;
         }
         const size_t n = (size_t)1 << num_vars, elem = (size_t)hf.fl * 8;
         for (uint32_t k = 0; k < n_mles && rc == ZIP_OK; k++) {
