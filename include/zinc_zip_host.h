@@ -101,6 +101,32 @@ int32_t zinc_zip_open(const zinc_zip_params *pp, const int64_t *evals, size_t n_
                       const zinc_zip_data *data, const uint64_t *point, size_t point_len, const uint64_t *modulus,
                       uint32_t limbs, zinc_pcs_transcript *transcript);
 
+/* ---- batch_commit / batch_open (commit.rs:134-142, open_z.rs:43-58) -------------------------
+ * polys[i]: n_evals[i] evaluations with poly_num_vars[i] variables.
+ * zinc_zip_batch_commit: one device batch, one commit launch for all polynomials (libzip_hip's zip_batch_commit);
+ * out[i] is polynomial i's MultilinearZipData (a member of the batch; free each with zinc_zip_data_free, in any order),
+ * roots_out n_polys * num_rows * 32 bytes (may be NULL).  Geometries the device batch does not serve, and
+ * ZIP_HIP_BATCH=0, take the loop over zinc_zip_commit: same results.
+ * zinc_zip_batch_open: points[i] = poly_num_vars[i] field elements (Montgomery limbs).  When datas[] are the members
+ * 0 .. n_polys-1 of one batch, in order: all evaluation rows in one device call, the transcript walk below, all proof
+ * streams in one device call; otherwise (or with ZIP_HIP_BATCH=0) the loop over zinc_zip_open.  Stream and
+ * Fiat-Shamir state end up the same. */
+int32_t zinc_zip_batch_commit(const zinc_zip_params *pp, const int64_t *const *polys, const size_t *n_evals,
+                              const uint32_t *poly_num_vars, size_t n_polys, uint8_t *roots_out, zinc_zip_data **out);
+int32_t zinc_zip_batch_open(const zinc_zip_params *pp, const int64_t *const *polys, const size_t *n_evals,
+                            const uint32_t *poly_num_vars, const zinc_zip_data *const *datas, const uint64_t *const *points,
+                            size_t n_polys, const uint64_t *modulus, uint32_t limbs, zinc_pcs_transcript *transcript);
+/* The Fiat-Shamir walk of batch_open once the evaluation rows are known -- host only, what a Rust shim runs between
+ * zip_batch_open_eval and zip_batch_open.  Per polynomial, in the reference's order: get_integer_challenges over
+ * num_rows (only if num_rows > 1, open_z.rs:104), n_cols times squeeze_challenge_idx over codeword_len (:116-120),
+ * then the absorption of its evaluation row (pcs_transcript.rs:107-113).
+ *   eval_rows   n_polys * row_len * limbs Montgomery limbs (zip_batch_open_eval's output)
+ *   coeffs_out  n_polys * num_rows (untouched when num_rows == 1; may then be NULL)
+ *   cols_out    n_polys * n_cols */
+int32_t zinc_zip_batch_open_challenges(uint32_t num_rows, uint32_t row_len, uint32_t codeword_len, uint32_t n_cols,
+                                       const uint64_t *modulus, uint32_t limbs, zinc_pcs_transcript *transcript,
+                                       const uint64_t *eval_rows, size_t n_polys, int64_t *coeffs_out, uint32_t *cols_out);
+
 /* PcsTranscript::from_proof (src/zip/pcs_transcript.rs:28-35): the reading side */
 zinc_pcs_transcript *zinc_pcs_transcript_from_proof(const uint8_t *proof, size_t len);
 size_t zinc_pcs_transcript_position(const zinc_pcs_transcript *t);

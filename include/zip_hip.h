@@ -41,7 +41,8 @@ extern "C" {
 #define ZIP_HIP_ABI_VERSION 3 /* 3: zip_ctx_set_speculation, zip_open_shard, zip_mctx_roots, zip_mctx_roots_path */
 /* (zip_keccak_state and zip_sumcheck_prove came later and are purely additive: no existing entry point or structure
  * changed, so the version stays 3; a caller that needs them looks the symbol up.  Likewise zip_sumcheck_init taking
- * up to 8 tables instead of 4: a widening, every call that was valid means what it meant.) */
+ * up to 8 tables instead of 4: a widening, every call that was valid means what it meant.  The batch entry points,
+ * zip_batch_commit and the five beside it, are additive in the same way.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -248,6 +249,51 @@ int32_t zip_commit_open_begin(zip_ctx *ctx, const int64_t *evals_d, size_t n_eva
                               const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont, const zip_field *field,
                               uint8_t *proof_out_d, zip_job **job);
 int32_t zip_job_wait(zip_job *job, uint8_t *roots_out);
+
+/* ---- batches: many small polynomials in one launch ----------------------------------
+ * The reference's batch_commit / batch_open (commit.rs:134-142, open_z.rs:43-58) for polynomials that do not fill the
+ * machine one at a time (2^12: 64 one-wave workgroups): all polynomials of a batch share the ctx's geometry and
+ * permutations, every row has its own Merkle tree, so B polynomials of R rows are B * R rows to ONE commit launch, and
+ * the open is one launch set with the polynomial as a grid dimension.  The number of launches does not depend on B.
+ * Unsharded ctx, codeword_len <= 16384, 1 <= n_polys <= 65535, n_polys * num_rows < 2^32.
+ *
+ * zip_batch_commit: MultilinearZip::commit (with Merkle trees) of n_polys polynomials.
+ *   evals      polynomial-major, n_polys * num_rows * row_len values, contiguous.  A HOST witness is copied and the
+ *              batch keeps the device copy; a DEVICE witness is read in place and must outlive the handle and its
+ *              members (the rule of zip_sumcheck_init's tables).  The later calls take no witness argument.
+ *   roots_out  HOST, n_polys * num_rows * 32 bytes, may be NULL
+ * Roots, rows and layers of polynomial i are byte-identical to those of a plain zip_commit of polynomial i.
+ * Errors, before anything reaches the device: ZIP_ERR_NULL (ctx, evals, out), ZIP_ERR_INVALID_PARAM (n_polys 0 or
+ * above 65535, row-sharded ctx), ZIP_ERR_UNSUPPORTED (codeword_len above 16384 -- not launch-bound, the jobs above
+ * serve them --, n_polys * num_rows beyond 32 bits), ZIP_ERR_SHAPE (n_evals).
+ *
+ * zip_batch_member: a zip_commitment for polynomial `index` that borrows the batch's storage -- a plain, complete,
+ * unhinted handle like an uploaded one, good for zip_open, zip_open_columns, zip_open_stream, zip_commit_download,
+ * zip_commitment_device_ptrs, zip_commitment_mle_eval and zip_commitment_free.  Members and the batch are freed in any
+ * order; the storage lives until the last of them is.  index >= size: ZIP_ERR_INVALID_PARAM.
+ *
+ * zip_batch_open_eval: prove_evaluation_phase (open_z.rs:62-91) of every polynomial.
+ *   q0_mont    HOST, n_polys * num_rows * limbs: one eq tensor per polynomial (the points differ); NULL when num_rows == 1
+ *   rows_out   n_polys * row_len * limbs Montgomery limbs; polynomial i's part equals zip_open_eval of polynomial i
+ *
+ * zip_batch_open: n_polys proof streams; stream i starts at byte i * zip_proof_len (a multiple of 8, not of 16) of
+ * proofs_out and is byte-identical to zip_open of polynomial i with coeffs[i], cols[i], q0[i] -- the concatenation is what
+ * batch_open leaves in a shared PcsTranscript stream.  In `open` only write_field_elements absorbs
+ * (pcs_transcript.rs:107-113), and the evaluation row depends on the witness and the point alone: a caller first takes
+ * all rows (zip_batch_open_eval), walks its transcript on the host -- per polynomial: squeeze the coefficients, squeeze
+ * the columns, absorb the row --, then makes this one call.
+ *   coeffs     HOST, n_polys * num_rows (NULL when num_rows == 1)
+ *   cols       HOST, n_polys * n_cols, duplicates allowed; an index >= codeword_len is ZIP_ERR_INVALID_PARAM */
+typedef struct zip_batch zip_batch;
+int32_t zip_batch_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uint32_t n_polys, zip_mem_kind evals_kind,
+                         uint8_t *roots_out, zip_batch **out);
+uint32_t zip_batch_size(const zip_batch *b); /* 0 for NULL */
+void zip_batch_free(zip_batch *b);           /* NULL is a no-op */
+int32_t zip_batch_member(zip_batch *b, uint32_t index, zip_commitment **out);
+int32_t zip_batch_open_eval(zip_batch *b, const uint64_t *q0_mont, const zip_field *field, uint64_t *rows_out,
+                            zip_mem_kind out_kind);
+int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont,
+                       const zip_field *field, uint8_t *proofs_out, zip_mem_kind out_kind);
 
 /* ---- streaming proof writer -------------------------------
  * zip_open with the stream delivered to `sink` in order, piece by piece (u', then groups of opened

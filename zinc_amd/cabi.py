@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
     "zip_sumcheck_prove", "zip_sumcheck_launch_counts",
     "zip_ccs_create", "zip_ccs_free", "zip_ccs_last_error", "zip_ccs_set_z", "zip_ccs_eq_table",
     "zip_ccs_second_table", "zip_ccs_table", "zip_ccs_download", "zip_ccs_eval_matrices",
+    "zip_batch_commit", "zip_batch_size", "zip_batch_free", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open",
 )
 
 
@@ -237,6 +238,16 @@ def lib():
     L.zip_ccs_download.argtypes = [vp, C.c_int, C.c_uint32, u64p]
     L.zip_commitment_free.argtypes = [vp]
     L.zip_commitment_free.restype = None
+    L.zip_batch_commit.argtypes = [vp, i64p, C.c_size_t, C.c_uint32, C.c_int, u8p, C.POINTER(vp)]
+    L.zip_batch_size.argtypes = [vp]
+    L.zip_batch_size.restype = C.c_uint32
+    L.zip_batch_free.argtypes = [vp]
+    L.zip_batch_free.restype = None
+    L.zip_batch_member.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    L.zip_batch_open_eval.argtypes = [vp, u64p, C.POINTER(ZipField), u64p, C.c_int]
+    L.zip_batch_open.argtypes = [vp, i64p, u32p, C.c_uint32, u64p, C.POINTER(ZipField), u8p, C.c_int]
+    for fn in ("zip_batch_commit", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open"):
+        getattr(L, fn).restype = C.c_int32
     L.zip_commitment_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.zip_commit_download.argtypes = [vp, u64p, u8p, u8p]
     L.zip_commitment_upload.argtypes = [vp, u64p, u8p, u8p, C.POINTER(vp)]
@@ -393,6 +404,19 @@ class ZipContext:
             rc = lib().zip_commit(self._h, ptr, n, kind, int(with_merkle), rp, C.byref(h))
             self._check(rc, "zip_commit")
         return Commitment(self, h, bool(with_merkle)), roots
+
+    def batch_commit(self, evals_2d, want_roots=True):
+        """zip_batch_commit: MultilinearZip::commit of every row of evals_2d ([n_polys, 2^num_vars] int64 numpy array or
+        CUDA tensor) in one launch.  A CUDA tensor is read in place and must outlive the Batch and its members.
+        -> Batch; its .roots is [n_polys, num_rows, 32] (None without want_roots)."""
+        ptr, kind = _ptr(evals_2d)
+        n = evals_2d.size if isinstance(evals_2d, np.ndarray) else evals_2d.numel()
+        n_polys = evals_2d.shape[0] if len(evals_2d.shape) > 1 else 1
+        roots = np.zeros((n_polys, self.num_rows, 32), dtype=np.uint8) if want_roots else None
+        h = C.c_void_p()
+        rc = lib().zip_batch_commit(self._h, ptr, n, n_polys, kind, roots.ctypes.data if roots is not None else None, C.byref(h))
+        self._check(rc, "zip_batch_commit")
+        return Batch(self, h, evals_2d if kind == MEM_DEVICE else None, roots)
 
     def commit_open(self, evals, coeffs, cols, q0_mont, field, out=None, want_roots=True, keep=False):
         """zip_commit_open: MultilinearZip::commit + open in one call (prover.rs:305-328).
@@ -639,11 +663,68 @@ class ZipMultiContext:
             pass
 
 
+class Batch:
+    """The commitments of many polynomials of one geometry behind a zip_batch handle (ZipContext.batch_commit)."""
+
+    def __init__(self, ctx: ZipContext, handle, keep, roots=None):
+        self.ctx, self._h, self._keep = ctx, handle, keep  # (_keep: a device witness the library reads in place)
+        self.roots = roots
+
+    def __len__(self):
+        return lib().zip_batch_size(self._h)
+
+    def free(self):
+        if getattr(self, "_h", None) and self.ctx._h:
+            lib().zip_batch_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def member(self, i):
+        """A Commitment for polynomial i that borrows the batch's storage; it may outlive the Batch."""
+        h = C.c_void_p()
+        self.ctx._check(lib().zip_batch_member(self._h, i, C.byref(h)), "zip_batch_member")
+        return Commitment(self.ctx, h, True, keep=self._keep)
+
+    def open_eval(self, q0_mont, field: ZipField, out=None):
+        """Every polynomial's evaluation row -> [n_polys, row_len, limbs] Montgomery limbs.  q0_mont: [n_polys, num_rows,
+        limbs], or None when num_rows == 1."""
+        c = self.ctx
+        q0 = np.ascontiguousarray(q0_mont, dtype=np.uint64) if q0_mont is not None else None
+        assert q0 is None or q0.size == len(self) * c.num_rows * field.limbs
+        res = out if out is not None else np.zeros((len(self), c.row_len, field.limbs), dtype=np.uint64)
+        optr, okind = _ptr(res)
+        rc = lib().zip_batch_open_eval(self._h, q0.ctypes.data if q0 is not None else None, C.byref(field), optr, okind)
+        c._check(rc, "zip_batch_open_eval")
+        return res
+
+    def open(self, coeffs, cols, q0_mont, field: ZipField, out=None):
+        """The proof streams of every polynomial, back to back -> [n_polys, proof_len] bytes.  coeffs [n_polys, num_rows]
+        and q0_mont [n_polys, num_rows, limbs] (None when num_rows == 1), cols [n_polys, n_cols]."""
+        c = self.ctx
+        cols = np.ascontiguousarray(cols, dtype=np.uint32).reshape(len(self), -1)
+        coeffs_c = np.ascontiguousarray(coeffs, dtype=np.int64) if coeffs is not None else None
+        q0 = np.ascontiguousarray(q0_mont, dtype=np.uint64) if q0_mont is not None else None
+        assert coeffs_c is None or coeffs_c.size == len(self) * c.num_rows
+        assert q0 is None or q0.size == len(self) * c.num_rows * field.limbs
+        n_cols = cols.shape[1]
+        res = out if out is not None else np.zeros((len(self), c.proof_len(n_cols, field.limbs)), dtype=np.uint8)
+        optr, okind = _ptr(res)
+        rc = lib().zip_batch_open(self._h, coeffs_c.ctypes.data if coeffs_c is not None else None, cols.ctypes.data, n_cols,
+                                  q0.ctypes.data if q0 is not None else None, C.byref(field), optr, okind)
+        c._check(rc, "zip_batch_open")
+        return res
+
+
 class Commitment:
     """Device-resident MultilinearZipData (+ roots) behind a zip_commitment handle."""
 
-    def __init__(self, ctx: ZipContext, handle, has_merkle):
-        self.ctx, self._h, self.has_merkle = ctx, handle, has_merkle
+    def __init__(self, ctx: ZipContext, handle, has_merkle, keep=None):
+        self.ctx, self._h, self.has_merkle, self._keep = ctx, handle, has_merkle, keep
 
     def free(self):
         if getattr(self, "_h", None) and self.ctx._h:

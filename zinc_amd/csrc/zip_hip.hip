@@ -26,6 +26,7 @@
 #include "../../include/zip_hip.h"
 #include "kernels_commit.cuh"
 #include "kernels_open.cuh"
+#include "kernels_batch.cuh"
 #include "kernels_verify.cuh"
 #include "kernels_sumcheck.cuh"
 #include "kernels_sumcheck_tail.cuh"
@@ -180,7 +181,30 @@ struct zip_ctx {
     std::vector<std::string> stat_names;  // stable storage for returned names
 };
 
+// The device storage of a zip_batch: the row entries, trees and roots of all its polynomials in one block each (and the
+// library's copy of a HOST witness).  The batch and every member handle taken from it (zip_batch_member) hold a
+// reference; the blocks return to the pool with the last of them.
+struct BatchStore {
+    void *rows = nullptr, *layers = nullptr, *roots = nullptr, *evals = nullptr;
+    std::function<void(BatchStore &)> release;
+    BatchStore() = default;
+    BatchStore(const BatchStore &) = delete;
+    BatchStore &operator=(const BatchStore &) = delete;
+    ~BatchStore() { if (release) release(*this); }
+};
+
+struct zip_batch {
+    zip_ctx *ctx = nullptr;
+    uint32_t n_polys = 0;
+    std::shared_ptr<BatchStore> store;
+    const int64_t *evals_d = nullptr;  // [n_polys][num_rows][row_len] on the device: the store's copy, or the caller's array
+};
+
 struct zip_commitment {
+    // a member of a zip_batch: rows / layers / roots / evals point INTO the batch's blocks (`store` keeps them alive)
+    // and are not this handle's to release -- except `rows` once materialize_rows has replaced them by a copy
+    std::shared_ptr<BatchStore> store;
+    bool borrows_rows = false, borrows_rest = false;
     const uint32_t *gather_order = nullptr;  // device, valid during one open: OpenColsArgs.order
     zip_ctx *ctx = nullptr;
     uint64_t *rows = nullptr;   // [rows_local][cw][4], or [rows_local][cw][2] while compact_rows (see materialize_rows)
@@ -1950,6 +1974,32 @@ int32_t ccs_field(zip_ccs *c, HostField *hf) {
 // =============================================================================
 // exported symbols
 // =============================================================================
+// ------------------------------------------------------------------ batches (kernels_batch.cuh)
+namespace {
+template <int FL>
+int32_t launch_batch_combine_fl(zip_ctx *ctx, BatchCombineArgs a, uint32_t n_polys, bool do_int, const HostField &hf) {
+    const FieldDev<FL> fd = to_dev<FL>(hf);
+    const dim3 grid((a.row_len + kBatchCombineThreads - 1) / kBatchCombineThreads, n_polys), block(kBatchCombineThreads);
+    LaunchTimer t(ctx, "batch_combine_kernel", ctx->stream);
+    if (a.quirk_mod) {  // (rare moduli: the instances that carry the 64-bit division)
+        if (do_int) hipLaunchKernelGGL((batch_combine_kernel<FL, true, true>), grid, block, 0, ctx->stream, a, fd);
+        else hipLaunchKernelGGL((batch_combine_kernel<FL, false, true>), grid, block, 0, ctx->stream, a, fd);
+    } else {
+        if (do_int) hipLaunchKernelGGL((batch_combine_kernel<FL, true, false>), grid, block, 0, ctx->stream, a, fd);
+        else hipLaunchKernelGGL((batch_combine_kernel<FL, false, false>), grid, block, 0, ctx->stream, a, fd);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return ZIP_OK;
+}
+int32_t launch_batch_combine(zip_ctx *ctx, const BatchCombineArgs &a, uint32_t n_polys, bool do_int, const HostField &hf) {
+    switch (hf.fl) {
+        case 2: return launch_batch_combine_fl<2>(ctx, a, n_polys, do_int, hf);
+        case 3: return launch_batch_combine_fl<3>(ctx, a, n_polys, do_int, hf);
+        default: return launch_batch_combine_fl<4>(ctx, a, n_polys, do_int, hf);
+    }
+}
+}  // namespace
+
 extern "C" {
 
 int32_t zip_abi_version(void) { return ZIP_HIP_ABI_VERSION; }
@@ -2637,11 +2687,13 @@ void zip_commitment_free(zip_commitment *c) {
     pool_release(c->ctx, c->digest_d);
     pool_release(c->ctx, c->need_d);
     if (c->hint_h) c->ctx->hint_free.push_back(c->hint_h);
-    pool_release(c->ctx, c->rows);
-    pool_release(c->ctx, c->layers);
-    pool_release(c->ctx, c->roots);
-    pool_release(c->ctx, c->evals);
-    delete c;
+    if (!c->borrows_rows) pool_release(c->ctx, c->rows);
+    if (!c->borrows_rest) {
+        pool_release(c->ctx, c->layers);
+        pool_release(c->ctx, c->roots);
+        pool_release(c->ctx, c->evals);
+    }
+    delete c;  // (a batch member: drops its reference to the batch's storage)
 }
 
 static int32_t materialize_rows(zip_commitment *c);
@@ -2682,7 +2734,8 @@ static int32_t materialize_rows(zip_commitment *c) {
         pool_release(ctx, full);
         return fail(ctx, ZIP_ERR_HIP, "expanding the row entries failed: %s", hipGetErrorString(e));
     }
-    pool_release(ctx, c->rows);
+    if (!c->borrows_rows) pool_release(ctx, c->rows);
+    c->borrows_rows = false;
     c->rows = static_cast<uint64_t *>(full);
     c->rows_bytes = (size_t)n * 32;
     c->compact_rows = false;
@@ -3203,6 +3256,244 @@ int32_t zip_job_wait(zip_job *j, uint8_t *roots_out) {
     ctx->last_error = keep;
     delete j;
     return rc;
+}
+
+// =====================================================================================================
+// Batches: many small polynomials on one ctx (the reference's batch_commit / batch_open, commit.rs:134-142,
+// open_z.rs:43-58).  Every row has its own Merkle tree, so to the commit kernels B polynomials of R rows are B * R
+// rows: ONE launch of the kernel a single commit of this geometry takes, everything stored, nothing hinted, no chunk
+// published.  The open is two launches whatever B is (kernels_batch.cuh): the polynomial is a grid dimension.
+// =====================================================================================================
+int32_t zip_batch_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uint32_t n_polys, zip_mem_kind evals_kind,
+                         uint8_t *roots_out, zip_batch **out) {
+    if (!ctx || !evals || !out) return ZIP_ERR_NULL;
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len;
+    if (n_polys == 0 || n_polys > 65535)
+        return fail(ctx, ZIP_ERR_INVALID_PARAM, "a batch holds 1 .. 65535 polynomials (got %u)", n_polys);
+    if (ctx->rows_local != R) return fail(ctx, ZIP_ERR_INVALID_PARAM, "batches need an unsharded ctx");
+    if (cw > 16384)
+        return fail(ctx, ZIP_ERR_UNSUPPORTED, "batches serve codewords up to 16384 (got %u): larger polynomials are not launch-bound, "
+                    "use zip_commit_open_begin", cw);
+    if ((uint64_t)n_polys * R > 0xFFFFFFFFull)
+        return fail(ctx, ZIP_ERR_UNSUPPORTED, "%u polynomials of %u rows exceed 2^32 rows", n_polys, R);
+    if (n_evals != (size_t)n_polys * R * C)
+        return fail(ctx, ZIP_ERR_SHAPE, "A batch of %u polynomials has an incorrect number of evaluations (%zu) for the expected "
+                    "matrix size (%zu each)", n_polys, n_evals, (size_t)R * C);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint32_t total = n_polys * R;
+    zip_batch *b = new (std::nothrow) zip_batch();
+    if (!b) return ZIP_ERR_ALLOC;
+    b->ctx = ctx;
+    b->n_polys = n_polys;
+    b->store = std::make_shared<BatchStore>();
+    {
+        std::shared_ptr<bool> alive = ctx->alive;  // (storage that outlives its ctx must not touch the ctx's pool)
+        b->store->release = [ctx, alive](BatchStore &s) {
+            if (!*alive) return;
+            std::lock_guard<std::recursive_mutex> lock(ctx->api_mu);
+            // nothing may still be reading or writing the blocks when they return to the pool
+            (void)stream_wait(ctx->s_commit);
+            (void)stream_wait(ctx->stream);
+            pool_release(ctx, s.rows);
+            pool_release(ctx, s.layers);
+            pool_release(ctx, s.roots);
+            pool_release(ctx, s.evals);
+        };
+    }
+    BatchStore &S = *b->store;
+    int32_t rc = ZIP_OK;
+    do {
+        if ((rc = pool_alloc(ctx, (size_t)total * cw * 16, &S.rows))) break;
+        if ((rc = pool_alloc(ctx, (size_t)total * 2 * cw * 32, &S.layers))) break;
+        if ((rc = pool_alloc(ctx, (size_t)total * 32, &S.roots))) break;
+        b->evals_d = evals;
+        if (evals_kind == ZIP_MEM_HOST) {
+            if ((rc = pool_alloc(ctx, n_evals * 8, &S.evals))) break;
+            if ((rc = copy_h2d_bounced(ctx, S.evals, evals, n_evals * 8, ctx->s_commit))) break;
+            b->evals_d = static_cast<const int64_t *>(S.evals);
+        }
+        // the launch of commit_impl for `total` rows: as many workgroups as stay resident, equal chunks of about four
+        // rounds (a chunk end is where the kernel builds the upper tree levels of the rows it has finished)
+        const CommitGeom geom = commit_geom(cw, C);
+        uint32_t G = ctx->num_cus * commit_wgs_per_cu(geom);
+        if (G > total) G = total;
+        const uint32_t rounds = (total + G - 1) / G;
+        uint32_t nch = rounds >= 8 ? std::min(8u, rounds / 4) : rounds >= 2 ? 2u : 1u;
+        const uint32_t rpc = (rounds + nch - 1) / nch;
+        CommitArgs a{};
+        a.classes = 1;
+        a.evals = b->evals_d;
+        a.perm1 = ctx->perm1_d;
+        a.perm2 = ctx->perm2_d;
+        a.rows = static_cast<uint64_t *>(S.rows);
+        a.compact_rows = 1u;
+        a.layers = static_cast<uint32_t *>(S.layers);
+        a.row_len = C;
+        a.cw = cw;
+        a.num_rows = total;
+        a.rounds_per_chunk = rpc;
+        a.roots = static_cast<uint32_t *>(S.roots);
+        if ((rc = dispatch_commit<true>(ctx, a, G, ctx->s_commit))) break;
+        // the handle and its members are complete when this call returns: nothing later has to wait for the commit
+        hipError_t e = stream_wait(ctx->s_commit);
+        if (e != hipSuccess) { rc = fail(ctx, ZIP_ERR_HIP, "batch commit failed: %s", hipGetErrorString(e)); break; }
+        if (roots_out && (rc = copy_d2h_bounced(ctx, roots_out, S.roots, (size_t)total * 32, ctx->stream))) break;
+    } while (0);
+    if (rc) {
+        delete b;
+        return rc;
+    }
+    *out = b;
+    return ZIP_OK;
+}
+
+uint32_t zip_batch_size(const zip_batch *b) { return b ? b->n_polys : 0; }
+
+void zip_batch_free(zip_batch *b) {
+    if (!b) return;
+    std::lock_guard<std::recursive_mutex> api_lock(b->ctx->api_mu);
+    delete b;  // (the storage goes with the last of the batch and its members)
+}
+
+int32_t zip_batch_member(zip_batch *b, uint32_t index, zip_commitment **out) {
+    if (!b || !out) return ZIP_ERR_NULL;
+    *out = nullptr;
+    zip_ctx *ctx = b->ctx;
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (index >= b->n_polys)
+        return fail(ctx, ZIP_ERR_INVALID_PARAM, "member %u of a batch of %u polynomials", index, b->n_polys);
+    zip_commitment *c = new (std::nothrow) zip_commitment();
+    if (!c) return ZIP_ERR_ALLOC;
+    const size_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len;
+    c->ctx = ctx;
+    c->store = b->store;
+    c->borrows_rows = c->borrows_rest = true;
+    c->compact_rows = true;
+    c->rows_bytes = R * cw * 16;
+    c->layers_bytes = R * 2 * cw * 32;
+    c->roots_bytes = R * 32;
+    c->evals_bytes = R * C * 8;
+    c->rows = static_cast<uint64_t *>(b->store->rows) + (size_t)index * R * cw * 2;
+    c->layers = static_cast<uint32_t *>(b->store->layers) + (size_t)index * R * 2 * cw * 8;
+    c->roots = static_cast<uint32_t *>(b->store->roots) + (size_t)index * R * 8;
+    c->evals = const_cast<int64_t *>(b->evals_d) + (size_t)index * R * C;  // (only ever read)
+    *out = c;
+    return ZIP_OK;
+}
+
+int32_t zip_batch_open_eval(zip_batch *b, const uint64_t *q0_mont, const zip_field *field, uint64_t *rows_out,
+                            zip_mem_kind out_kind) {
+    if (!b || !rows_out) return ZIP_ERR_NULL;
+    zip_ctx *ctx = b->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    HostField hf;
+    int32_t rc;
+    if ((rc = make_field(ctx, field, &hf))) return rc;
+    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, B = b->n_polys;
+    const bool single = R == 1;
+    if (!single && !q0_mont) return fail(ctx, ZIP_ERR_NULL, "q0_mont is NULL");
+    const size_t bytes = (size_t)B * C * hf.fl * 8;
+    Scratch res(ctx), small(ctx);
+    uint64_t *out_d = rows_out;
+    if (out_kind == ZIP_MEM_HOST) {
+        if ((rc = res.get(bytes))) return rc;
+        out_d = res.as<uint64_t>();
+    }
+    SmallInputs si;
+    si.src[1] = single ? hf.r : q0_mont;  // one row: the evaluation row is map_to_field(evals) = 1_mont * w (open_z.rs:84-88)
+    si.bytes[1] = single ? (size_t)hf.fl * 8 : (size_t)B * R * hf.fl * 8;
+    unsigned char *sb;
+    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
+    BatchCombineArgs a{};
+    a.evals = b->evals_d;
+    a.q0 = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
+    a.q0_shared = single ? 1u : 0u;
+    a.num_rows = R;
+    a.row_len = C;
+    a.m_limbs = ctx->p.m_limbs;
+    a.quirk_mod = hf.quirk_mod;
+    a.row_limbs = out_d;
+    if ((rc = launch_batch_combine(ctx, a, B, false, hf))) return rc;
+    if (out_kind == ZIP_MEM_HOST) return deliver(ctx, rows_out, ZIP_MEM_HOST, out_d, bytes);
+    HIP_TRY(ctx, stream_wait(ctx->stream));  // q0 was read from host memory
+    return ZIP_OK;
+}
+
+int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont,
+                       const zip_field *field, uint8_t *proofs_out, zip_mem_kind out_kind) {
+    if (!b || !proofs_out || (n_cols && !cols)) return ZIP_ERR_NULL;
+    zip_ctx *ctx = b->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    HostField hf;
+    int32_t rc;
+    if ((rc = make_field(ctx, field, &hf))) return rc;
+    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, B = b->n_polys;
+    const bool single = R == 1;
+    if (!single && (!coeffs || !q0_mont)) return fail(ctx, ZIP_ERR_NULL, "coeffs / q0_mont is NULL");
+    if ((uint64_t)B * n_cols > 0xFFFFFFFFull) return fail(ctx, ZIP_ERR_UNSUPPORTED, "%u x %u openings exceed 2^32", B, n_cols);
+    if ((rc = check_cols(ctx, cols, B * n_cols))) return rc;
+    const size_t stream_bytes = zip_proof_len(ctx, n_cols, hf.fl), total = (size_t)B * stream_bytes;
+    const size_t u_bytes = single ? 0 : (size_t)C * ctx->p.m_limbs * 8;
+    const size_t col_bytes = (size_t)n_cols * column_bytes(ctx);
+    Scratch res(ctx), small(ctx);
+    uint8_t *out_d = proofs_out;
+    if (out_kind == ZIP_MEM_HOST) {
+        if ((rc = res.get(total))) return rc;
+        out_d = res.as<uint8_t>();
+    }
+    SmallInputs si;
+    if (!single) {
+        si.src[0] = coeffs;
+        si.bytes[0] = (size_t)B * R * 8;
+    }
+    si.src[1] = single ? hf.r : q0_mont;
+    si.bytes[1] = single ? (size_t)hf.fl * 8 : (size_t)B * R * hf.fl * 8;
+    si.src[2] = cols;
+    si.bytes[2] = (size_t)B * n_cols * 4;
+    unsigned char *sb;
+    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
+    // 1. every polynomial's u' and evaluation row, straight to their places in its stream
+    BatchCombineArgs a{};
+    a.evals = b->evals_d;
+    a.coeffs = single ? nullptr : reinterpret_cast<const int64_t *>(sb + si.off[0]);
+    a.q0 = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
+    a.q0_shared = single ? 1u : 0u;
+    a.num_rows = R;
+    a.row_len = C;
+    a.m_limbs = ctx->p.m_limbs;
+    a.quirk_mod = hf.quirk_mod;
+    a.uprime = single ? nullptr : out_d;
+    a.row_be = out_d + u_bytes + col_bytes;
+    a.out_stride = stream_bytes;
+    if ((rc = launch_batch_combine(ctx, a, B, !single, hf))) return rc;
+    // 2. every polynomial's column openings
+    if (n_cols) {
+        BatchOpenColsArgs g{};
+        g.rows = static_cast<const uint64_t *>(b->store->rows);
+        g.layers = static_cast<const uint64_t *>(b->store->layers);
+        g.cols = reinterpret_cast<const uint32_t *>(sb + si.off[2]);
+        g.out = out_d;
+        g.stream_bytes = stream_bytes;
+        g.openings_at = u_bytes;
+        g.n_cols = n_cols;
+        g.num_rows = R;
+        g.cw = ctx->p.codeword_len;
+        g.depth = ctx->depth;
+        g.rows_per_block = R < 32u ? R : 32u;
+        // (cw <= 16384: 2 * depth + 1 <= 29 lanes per row; an image of 32 records is at most 14.6 KB)
+        const size_t lds = (size_t)g.rows_per_block * (8 + 32 * (size_t)ctx->depth);
+        const dim3 grid(n_cols, (R + g.rows_per_block - 1) / g.rows_per_block, B), block(256);
+        LaunchTimer t(ctx, "batch_open_columns_kernel", ctx->stream);
+        hipLaunchKernelGGL(batch_open_columns_kernel<32>, grid, block, lds, ctx->stream, g);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (out_kind == ZIP_MEM_HOST) return deliver(ctx, proofs_out, ZIP_MEM_HOST, out_d, total);
+    HIP_TRY(ctx, stream_wait(ctx->stream));  // coeffs, cols and q0 were read from host memory
+    return ZIP_OK;
 }
 
 // =====================================================================================================

@@ -244,6 +244,58 @@ int32_t zinc_zip_open(const zinc_zip_params *pp, const int64_t *evals, size_t n_
     });
 }
 
+int32_t zinc_zip_batch_commit(const zinc_zip_params *pp, const int64_t *const *polys, const size_t *n_evals,
+                              const uint32_t *poly_num_vars, size_t n_polys, uint8_t *roots_out, zinc_zip_data **out) {
+    if (!pp || (n_polys && (!polys || !n_evals || !poly_num_vars || !out))) return ZINC_ERR_NULL;
+    for (size_t i = 0; i < n_polys; i++) out[i] = nullptr;
+    return guarded([&] {
+        std::vector<PolyRef> refs(n_polys);
+        for (size_t i = 0; i < n_polys; i++) refs[i] = {polys[i], n_evals[i], poly_num_vars[i]};
+        auto res = MultilinearZip::batch_commit(pp->pp, refs.data(), n_polys);
+        const size_t root_bytes = (size_t)pp->pp.num_rows * 32;
+        for (size_t i = 0; i < n_polys; i++) {
+            if (roots_out) std::memcpy(roots_out + i * root_bytes, res[i].second.roots.data(), root_bytes);
+            out[i] = new zinc_zip_data{std::move(res[i].first)};
+        }
+    });
+}
+
+int32_t zinc_zip_batch_open(const zinc_zip_params *pp, const int64_t *const *polys, const size_t *n_evals,
+                            const uint32_t *poly_num_vars, const zinc_zip_data *const *datas, const uint64_t *const *points,
+                            size_t n_polys, const uint64_t *modulus, uint32_t limbs, zinc_pcs_transcript *transcript) {
+    if (!pp || !transcript || (n_polys && (!polys || !n_evals || !poly_num_vars || !datas || !points))) return ZINC_ERR_NULL;
+    for (size_t i = 0; i < n_polys; i++)
+        if (!datas[i]) return ZINC_ERR_NULL;
+    return guarded([&] {
+        const FieldConfig f = FieldConfig::make(modulus, limbs);
+        std::vector<PolyRef> refs(n_polys);
+        std::vector<std::vector<Limbs>> pts(n_polys);
+        std::vector<const Limbs *> pt_ptrs(n_polys);
+        std::vector<const MultilinearZipData *> ds(n_polys);
+        for (size_t i = 0; i < n_polys; i++) {
+            refs[i] = {polys[i], n_evals[i], poly_num_vars[i]};
+            pts[i].resize(poly_num_vars[i]);
+            for (uint32_t k = 0; k < poly_num_vars[i]; k++) pts[i][k] = load(points[i] + (size_t)k * limbs, limbs);
+            pt_ptrs[i] = pts[i].data();
+            ds[i] = &datas[i]->d;
+        }
+        MultilinearZip::batch_open(pp->pp, refs.data(), ds.data(), pt_ptrs.data(), n_polys, f, transcript->t);
+    });
+}
+
+int32_t zinc_zip_batch_open_challenges(uint32_t num_rows, uint32_t row_len, uint32_t codeword_len, uint32_t n_cols,
+                                       const uint64_t *modulus, uint32_t limbs, zinc_pcs_transcript *transcript,
+                                       const uint64_t *eval_rows, size_t n_polys, int64_t *coeffs_out, uint32_t *cols_out) {
+    if (!modulus || !transcript || (n_polys && (!eval_rows || (n_cols && !cols_out) || (num_rows > 1 && !coeffs_out))))
+        return ZINC_ERR_NULL;
+    return guarded([&] {
+        if (!codeword_len) throw ZipError(ZipError::InvalidPcsParam, "codeword_len is 0");
+        const FieldConfig f = FieldConfig::make(modulus, limbs);
+        MultilinearZip::batch_open_challenges(num_rows, row_len, codeword_len, n_cols, f, transcript->t, eval_rows, n_polys,
+                                              coeffs_out, cols_out);
+    });
+}
+
 zinc_pcs_transcript *zinc_pcs_transcript_from_proof(const uint8_t *proof, size_t len) {
     auto *t = new zinc_pcs_transcript();
     t->t = PcsTranscript::from_proof(proof, len);

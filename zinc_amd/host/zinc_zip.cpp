@@ -863,6 +863,119 @@ void MultilinearZip::open(const MultilinearZipParams &pp, const int64_t *evals, 
     }
 }
 
+static bool batch_path_enabled() {
+    const char *e = std::getenv("ZIP_HIP_BATCH");  // (read per call: the tests flip it)
+    return !(e && e[0] == '0' && !e[1]);
+}
+
+std::vector<std::pair<MultilinearZipData, MultilinearZipCommitment>> MultilinearZip::batch_commit(const MultilinearZipParams &pp,
+                                                                                                 const PolyRef *polys,
+                                                                                                 size_t n_polys) {
+    std::vector<std::pair<MultilinearZipData, MultilinearZipCommitment>> out;
+    if (!n_polys) return out;
+    const uint32_t row_len = pp.linear_code.row_len, num_rows = pp.num_rows, cw = pp.linear_code.codeword_len();
+    const size_t per = (size_t)row_len * num_rows;
+    bool batched = batch_path_enabled() && cw <= 16384 && n_polys <= 65535 && (uint64_t)n_polys * num_rows <= 0xFFFFFFFFull;
+    for (size_t i = 0; i < n_polys && batched; i++) batched = polys[i].n_evals == per && polys[i].num_vars <= pp.num_vars;
+    if (!batched) {  // (also where the loop's own checks produce the reference's errors)
+        for (size_t i = 0; i < n_polys; i++) out.push_back(commit(pp, polys[i].evals, polys[i].n_evals, polys[i].num_vars));
+        return out;
+    }
+    // polynomial-major and contiguous is what the device call wants; the reference's callers hold separate Vecs
+    bool contiguous = true;
+    for (size_t i = 1; i < n_polys && contiguous; i++) contiguous = polys[i].evals == polys[i - 1].evals + per;
+    IntVec packed;
+    const int64_t *evals = polys[0].evals;
+    if (!contiguous) {
+        packed.resize(n_polys * per);
+        for (size_t i = 0; i < n_polys; i++) std::memcpy(packed.data() + i * per, polys[i].evals, per * 8);
+        evals = packed.data();
+    }
+    std::vector<uint8_t> roots(n_polys * (size_t)num_rows * 32);
+    zip_batch *b = nullptr;
+    check(pp.ctx.get(), zip_batch_commit(pp.ctx.get(), evals, n_polys * per, (uint32_t)n_polys, ZIP_MEM_HOST, roots.data(), &b),
+          "zip_batch_commit");
+    std::shared_ptr<zip_batch> batch(b, zip_batch_free);
+    out.reserve(n_polys);
+    for (size_t i = 0; i < n_polys; i++) {
+        zip_commitment *h = nullptr;
+        check(pp.ctx.get(), zip_batch_member(b, (uint32_t)i, &h), "zip_batch_member");
+        MultilinearZipData data;
+        data.ctx = pp.ctx;
+        data.handle = std::shared_ptr<zip_commitment>(h, zip_commitment_free);
+        data.batch = batch;
+        data.batch_index = (uint32_t)i;
+        MultilinearZipCommitment comm;
+        comm.roots.resize(num_rows);
+        std::memcpy(comm.roots.data(), roots.data() + i * (size_t)num_rows * 32, (size_t)num_rows * 32);
+        out.emplace_back(std::move(data), std::move(comm));
+    }
+    return out;
+}
+
+void MultilinearZip::batch_open_challenges(uint32_t num_rows, uint32_t row_len, uint32_t codeword_len, uint32_t n_cols,
+                                           const FieldConfig &field, PcsTranscript &transcript, const uint64_t *eval_rows,
+                                           size_t n_polys, int64_t *coeffs_out, uint32_t *cols_out) {
+    for (size_t i = 0; i < n_polys; i++) {
+        if (num_rows > 1) {  // prove_testing_phase, open_z.rs:100-113
+            const auto coeffs = transcript.fs_transcript.get_integer_challenges_i64(num_rows);
+            std::memcpy(coeffs_out + i * num_rows, coeffs.data(), (size_t)num_rows * 8);
+        }
+        for (uint32_t k = 0; k < n_cols; k++)  // open_z.rs:116-120
+            cols_out[i * n_cols + k] = (uint32_t)transcript.squeeze_challenge_idx(field, codeword_len);
+        const uint64_t *row = eval_rows + i * (size_t)row_len * field.limbs;
+        for (uint32_t c = 0; c < row_len; c++) {  // write_field_elements' absorption, pcs_transcript.rs:107-113
+            Limbs v{};
+            for (uint32_t k = 0; k < field.limbs; k++) v[k] = row[(size_t)c * field.limbs + k];
+            transcript.fs_transcript.absorb_random_field(field, v);
+        }
+    }
+}
+
+void MultilinearZip::batch_open(const MultilinearZipParams &pp, const PolyRef *polys, const MultilinearZipData *const *datas,
+                                const Limbs *const *points, size_t n_polys, const FieldConfig &field, PcsTranscript &transcript) {
+    if (!n_polys) return;
+    const uint32_t row_len = pp.linear_code.row_len, num_rows = pp.num_rows, cw = pp.linear_code.codeword_len();
+    zip_batch *b = datas[0]->batch.get();
+    bool batched = batch_path_enabled() && b && zip_batch_size(b) == n_polys && pp.linear_code.num_proximity_testing == 1;
+    for (size_t i = 0; i < n_polys && batched; i++)
+        batched = datas[i]->batch.get() == b && datas[i]->batch_index == i && polys[i].num_vars == pp.num_vars &&
+                  polys[i].n_evals == (size_t)row_len * num_rows;
+    if (!batched) {
+        for (size_t i = 0; i < n_polys; i++)
+            open(pp, polys[i].evals, polys[i].n_evals, polys[i].num_vars, *datas[i], points[i], polys[i].num_vars, field, transcript);
+        return;
+    }
+    zip_ctx *ctx = pp.ctx.get();
+    const uint32_t fl = field.limbs, n_cols = pp.linear_code.num_column_opening;
+    // left_point_to_tensor (pcs/utils.rs:279-292) per polynomial: the points differ
+    std::vector<uint64_t> q0;
+    if (num_rows > 1) {
+        const uint32_t lr = ilog2(num_rows);
+        q0.resize(n_polys * (size_t)num_rows * fl);
+        for (size_t i = 0; i < n_polys; i++) {
+            const auto eq = build_eq_x_r(field, points[i] + (pp.num_vars - lr), lr);
+            for (uint32_t r = 0; r < num_rows; r++)
+                for (uint32_t k = 0; k < fl; k++) q0[(i * num_rows + r) * fl + k] = eq[r][k];
+        }
+    }
+    const zip_field zf = field.to_abi();
+    // 1. every evaluation row: they depend on the witness and the point alone
+    std::vector<uint64_t> rows(n_polys * (size_t)row_len * fl);
+    check(ctx, zip_batch_open_eval(b, q0.empty() ? nullptr : q0.data(), &zf, rows.data(), ZIP_MEM_HOST), "zip_batch_open_eval");
+    // 2. the shared transcript, in the reference's order
+    std::vector<int64_t> coeffs(num_rows > 1 ? n_polys * (size_t)num_rows : 0);
+    std::vector<uint32_t> cols(n_polys * (size_t)n_cols);
+    batch_open_challenges(num_rows, row_len, cw, n_cols, field, transcript, rows.data(), n_polys, coeffs.data(), cols.data());
+    // 3. every proof stream, straight into the transcript's stream
+    const size_t len = zip_proof_len(ctx, n_cols, fl), at = transcript.stream.size();
+    transcript.stream.resize(at + n_polys * len);
+    check(ctx,
+          zip_batch_open(b, coeffs.empty() ? nullptr : coeffs.data(), cols.data(), n_cols, q0.empty() ? nullptr : q0.data(), &zf,
+                         transcript.stream.data() + at, ZIP_MEM_HOST),
+          "zip_batch_open");
+}
+
 // point_to_tensor (pcs/utils.rs:252-276): q_0 over the last log2(num_rows) coordinates, q_1 over the rest;
 // an empty half gives an EMPTY vector (MLE::zero()).
 static void point_to_tensor(const FieldConfig &field, uint32_t num_rows, const Limbs *point, size_t point_len,

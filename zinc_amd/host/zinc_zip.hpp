@@ -225,6 +225,16 @@ struct MultilinearZipParams {
 struct MultilinearZipData {
     std::shared_ptr<zip_ctx> ctx;             // keeps the device context alive (declared first: destroyed last)
     std::shared_ptr<zip_commitment> handle;
+    // what batch_commit returns: `handle` is member `batch_index` of `batch` (zip_batch_member) and every member shares
+    // the reference to it; batch_open recognises the members 0 .. B-1 of one batch by these
+    std::shared_ptr<zip_batch> batch;
+    uint32_t batch_index = 0;
+};
+// one polynomial of a batch call: DenseMultilinearExtension {evaluations, num_vars}
+struct PolyRef {
+    const int64_t *evals = nullptr;
+    size_t n_evals = 0;
+    uint32_t num_vars = 0;
 };
 // MultilinearZipCommitment (structs.rs:42-45)
 struct MultilinearZipCommitment {
@@ -249,6 +259,25 @@ struct MultilinearZip {
     static void open(const MultilinearZipParams &pp, const int64_t *evals, size_t n_evals, uint32_t poly_num_vars,
                      const MultilinearZipData &commit_data, const Limbs *point, size_t point_len,
                      const FieldConfig &field, PcsTranscript &transcript);
+    // commit.rs:134-142.  ONE zip_batch for all polynomials (one commit launch); the returned data are its members.
+    // Geometries a batch does not serve (codewords above 16384) and ZIP_HIP_BATCH=0 fall back to the loop over commit.
+    static std::vector<std::pair<MultilinearZipData, MultilinearZipCommitment>> batch_commit(const MultilinearZipParams &pp,
+                                                                                           const PolyRef *polys, size_t n_polys);
+    // open_z.rs:43-58.  points[i]: polys[i].num_vars field elements.  When `datas` are the members 0 .. B-1 of one
+    // batch, in order, the whole loop is three device steps (all evaluation rows, the transcript walk of
+    // batch_open_challenges on the host, all proof streams in one call); otherwise, or with ZIP_HIP_BATCH=0, the
+    // loop over open.  The transcript and the stream end up the same either way.
+    static void batch_open(const MultilinearZipParams &pp, const PolyRef *polys, const MultilinearZipData *const *datas,
+                           const Limbs *const *points, size_t n_polys, const FieldConfig &field, PcsTranscript &transcript);
+    // The Fiat-Shamir walk of batch_open with the evaluation rows already known (in `open` only write_field_elements
+    // absorbs, pcs_transcript.rs:107-113, and the row does not depend on anything squeezed before it): per polynomial,
+    // in the reference's order, get_integer_challenges(num_rows) if num_rows > 1 (open_z.rs:104), n_cols times
+    // squeeze_challenge_idx(codeword_len) (:116-120), then the absorption of its row_len evaluation-row elements.
+    // eval_rows: [n_polys][row_len][limbs] Montgomery limbs; coeffs_out: [n_polys][num_rows] (untouched when
+    // num_rows == 1); cols_out: [n_polys][n_cols].  Host only.
+    static void batch_open_challenges(uint32_t num_rows, uint32_t row_len, uint32_t codeword_len, uint32_t n_cols,
+                                      const FieldConfig &field, PcsTranscript &transcript, const uint64_t *eval_rows,
+                                      size_t n_polys, int64_t *coeffs_out, uint32_t *cols_out);
     // verify_z.rs:19-38.  Throws ZipError{InvalidPcsOpen} with the reference's message when a check
     // fails ("Proximity failure", "Evaluation consistency failure"), std::logic_error where the
     // reference panics (encode_wide overflow).  Merkle paths are checked (zip_hip.h, zip_verify).

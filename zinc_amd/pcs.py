@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = (
     "zinc_zip_proof_num_roots", "zinc_zip_proof_read", "zinc_zip_proof_free", "zinc_zip_release_cached_contexts", "zinc_sumcheck_prove_product", "zinc_sumcheck_prove_ccs", "zinc_zip_data_download", "zinc_zip_data_upload", "zinc_merkle_tree_new",
     "zinc_prover_prove", "zinc_prover_prepare", "zinc_prepared_ccs_free", "zinc_verifier_verify",
     "zinc_sumcheck_prove_products", "zinc_sumcheck_verify",
+    "zinc_zip_batch_commit", "zinc_zip_batch_open", "zinc_zip_batch_open_challenges",
 )
 
 
@@ -96,6 +97,10 @@ def lib():
         L.zinc_pcs_transcript_probe.argtypes = [vp]
         L.zinc_pcs_transcript_probe.restype = C.c_uint64
         L.zinc_zip_open.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp, C.c_size_t, vp, C.c_uint32, vp]
+        L.zinc_zip_batch_commit.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
+        L.zinc_zip_batch_open.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_uint32, vp]
+        L.zinc_zip_batch_open_challenges.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp,
+                                                     C.c_size_t, vp, vp]
         L.zinc_pcs_transcript_from_proof.argtypes = [vp, C.c_size_t]
         L.zinc_pcs_transcript_from_proof.restype = vp
         L.zinc_pcs_transcript_position.argtypes = [vp]
@@ -390,14 +395,44 @@ class MultilinearZip:
 
     @staticmethod
     def batch_commit(pp: MultilinearZipParams, polys):
-        """commit.rs:134-142: a plain loop over the polynomials"""
-        return [MultilinearZip.commit(pp, p) for p in polys]
+        """commit.rs:134-142: one device batch, one commit launch for all polynomials (zinc_zip_batch_commit)
+        -> [(MultilinearZipData, roots)]"""
+        evs = [np.ascontiguousarray(p, dtype=np.int64) for p in polys]
+        m = len(evs)
+        if not m:
+            return []
+        ptrs = (C.c_void_p * m)(*[e.ctypes.data for e in evs])
+        sizes = (C.c_size_t * m)(*[e.size for e in evs])
+        nvs = (C.c_uint32 * m)(*[max(e.size, 1).bit_length() - 1 for e in evs])
+        roots = np.zeros((m, pp.num_rows, 32), np.uint8)
+        outs = (C.c_void_p * m)()
+        rc = lib().zinc_zip_batch_commit(pp._h, ptrs, sizes, nvs, m, roots.ctypes.data, outs)
+        datas = [MultilinearZipData(C.c_void_p(h), pp, True) for h in outs if h]  # (adopted first: freed if the call failed)
+        _check(rc)
+        return [(d, roots[i]) for i, d in enumerate(datas)]
 
     @staticmethod
     def batch_open(pp: MultilinearZipParams, polys, datas, points, field: "FieldConfig", transcript: "PcsTranscript"):
-        """open_z.rs:43-58"""
-        for p, d, pt in zip(polys, datas, points):
-            MultilinearZip.open(pp, p, d, pt, field, transcript)
+        """open_z.rs:43-58 (zinc_zip_batch_open): batched on the device when `datas` are all the members of one
+        batch_commit, in order; the loop over open otherwise"""
+        evs = [np.ascontiguousarray(p, dtype=np.int64) for p in polys]
+        m = min(len(evs), len(datas), len(points))
+        if not m:
+            return
+        pts = [np.ascontiguousarray(pt, dtype=np.uint64).reshape(-1, field.limbs) if np.size(pt) else np.zeros((0, field.limbs), np.uint64)
+               for pt in points[:m]]
+        nv = [max(e.size, 1).bit_length() - 1 for e in evs[:m]]
+        for i in range(m):
+            if pts[i].shape[0] != nv[i]:  # validate_input (pcs/utils.rs:24-58): the loop raises the reference's error
+                for p, d, pt in zip(polys, datas, points):
+                    MultilinearZip.open(pp, p, d, pt, field, transcript)
+                return
+        ptrs = (C.c_void_p * m)(*[e.ctypes.data for e in evs[:m]])
+        sizes = (C.c_size_t * m)(*[e.size for e in evs[:m]])
+        nvs = (C.c_uint32 * m)(*nv)
+        dh = (C.c_void_p * m)(*[d._h if isinstance(d._h, int) else d._h.value for d in datas[:m]])
+        pp_ = (C.c_void_p * m)(*[pt.ctypes.data for pt in pts])
+        _check(lib().zinc_zip_batch_open(pp._h, ptrs, sizes, nvs, dh, pp_, m, field._m.ctypes.data, field.limbs, transcript._h))
 
     @staticmethod
     def batch_verify_z(vp: MultilinearZipParams, comms, points, evals, transcript: "PcsTranscript", field: "FieldConfig"):
