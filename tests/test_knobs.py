@@ -37,3 +37,15 @@ def test_no_experiment_switches_in_the_kernels():
     prefix = "ZIPK_" + "EXP_"  # (split: a grep for the prefix over the tree stays empty)
     hits = [os.path.relpath(p, ROOT) for p in _sources("zinc_amd/csrc/*") if prefix in _read(p)]
     assert hits == []
+
+
+def test_schedule_and_gather_knobs_are_read_by_zip_ctx_create_only():
+    """tests/test_gpu_gather_variants.py sets these per test, in process, before it makes its context: each is read in
+    exactly one place, inside zip_ctx_create -- a `static const` read anywhere else would pin the first test's value."""
+    src = _read(os.path.join(ROOT, "zinc_amd", "csrc", "zip_hip.hip"))
+    start = src.index("int32_t zip_ctx_create(")
+    body = src[start:src.index("\nvoid zip_ctx_destroy(", start)]
+    for knob in ("ZIP_HIP_CHUNKS", "ZIP_HIP_CHUNK_ROUNDS", "ZIP_HIP_GATHER_RPB", "ZIP_HIP_GATHER_STREAM", "ZIP_HIP_NO_COMPACT_ROWS"):
+        reads = re.findall(r'(?:getenv|env_long)\(\s*"' + knob + '"', src)
+        assert len(reads) == 1, (knob, len(reads))
+        assert len(re.findall(r'(?:getenv|env_long)\(\s*"' + knob + '"', body)) == 1, knob

@@ -121,6 +121,12 @@ struct zip_ctx {
     // chunk k+1.
     hipStream_t stream = nullptr, s_commit = nullptr, s_upper = nullptr;
     uint32_t n_chunks = 1;
+    // knobs read from the environment ONCE, by zip_ctx_create (the calls read none of them again): ZIP_HIP_GATHER_RPB
+    // (0: unset), ZIP_HIP_GATHER_STREAM (-1: unset), ZIP_HIP_CHUNK_ROUNDS (empty: unset), ZIP_HIP_NO_COMPACT_ROWS
+    uint32_t knob_rpb = 0;
+    int knob_stream = -1;
+    std::string knob_chunk_rounds;
+    bool no_compact = false;
     uint32_t num_cus = 256;
     uint32_t *timeout_flag_h = nullptr, *timeout_flag_d = nullptr;  // pinned: a pipeline wait gave up
     unsigned long long *clock_h = nullptr, *clock_d = nullptr;      // pinned: CommitArgs.clock stamps of the last profiled commit
@@ -1286,7 +1292,7 @@ int32_t run_open_columns(zip_commitment *c, const uint32_t *cols_dv, uint32_t n_
     // commit workgroups of this geometry -- the gather is meant to run BESIDE them (at cw = 16384 the commit kernel
     // leaves 11.5 KB per CU and 32 records are 14.6 KB: the gathers then only started when the commit ended).
     // (ZIP_HIP_GATHER_RPB: a test hook; each path below takes it only within its own range)
-    static const uint32_t knob_rpb = (uint32_t)env_long("ZIP_HIP_GATHER_RPB", 0, 2, 4096);
+    const uint32_t knob_rpb = ctx->knob_rpb;  // (zip_ctx_create reads it)
     uint32_t rpb = 32u;
     const size_t rec = 8 + 32 * (size_t)ctx->depth;  // bytes of one record in the LDS image
     size_t free_lds = 0;
@@ -1313,7 +1319,7 @@ int32_t run_open_columns(zip_commitment *c, const uint32_t *cols_dv, uint32_t n_
     a.prio = 1;
     // Where the commit kernel leaves little LDS (cw = 16384: 16 records per workgroup):
     // the kernel without an LDS image.  ZIP_HIP_GATHER_STREAM=1 / 0 forces it on / off.
-    static const long knob_stream = env_long("ZIP_HIP_GATHER_STREAM", -1, 0, 1);
+    const int knob_stream = ctx->knob_stream;  // (zip_ctx_create reads it)
     const bool stream = knob_stream >= 0 ? knob_stream == 1 : rpb < 32;
     if (c->packed) {
         // a packed commitment: everything row-interleaved in groups of four (open_columns_ilv_kernel); blocks of whole
@@ -2126,6 +2132,11 @@ int32_t zip_ctx_create(const zip_params *p, zip_ctx **out) {
         // pipeline chunks: the persistent commit kernel publishes its rows in this many groups
         // (0 = chosen per commit from the number of rounds; ZIP_HIP_CHUNKS overrides)
         ctx->n_chunks = (uint32_t)env_long("ZIP_HIP_CHUNKS", 0, 1, 64);
+        // the other knobs of the chunk schedule and of the gather (zip_ctx): read here, never by a call
+        ctx->knob_rpb = (uint32_t)env_long("ZIP_HIP_GATHER_RPB", 0, 2, 4096);
+        ctx->knob_stream = (int)env_long("ZIP_HIP_GATHER_STREAM", -1, 0, 1);
+        if (const char *e = getenv("ZIP_HIP_CHUNK_ROUNDS")) ctx->knob_chunk_rounds = e;
+        ctx->no_compact = getenv("ZIP_HIP_NO_COMPACT_ROWS") != nullptr;
         const size_t pb = (size_t)p->codeword_len * 4;
         if (hipMalloc((void **)&ctx->perm1_d, pb) != hipSuccess || hipMalloc((void **)&ctx->perm2_d, pb) != hipSuccess) {
             rc = ZIP_ERR_ALLOC;
@@ -2240,8 +2251,7 @@ static int32_t commit_impl(zip_ctx *ctx, const int64_t *evals, size_t n_evals, z
     do {
         // A commit that will be opened keeps 16-byte row entries in HBM (half the row stores; the gather expands them
         // on the way into the proof); encode_rows / commit_no_merkle is read back and stays Int<4>.
-        static const bool no_compact = getenv("ZIP_HIP_NO_COMPACT_ROWS") != nullptr;
-        c->compact_rows = with_merkle && !no_compact;
+        c->compact_rows = with_merkle && !ctx->no_compact;
         c->rows_bytes = (size_t)R * cw * (c->compact_rows ? 16 : 32);
         {
             // packed openings take the place of the 16-byte row entries; where a row's packed block is larger than they
@@ -2290,7 +2300,7 @@ static int32_t commit_impl(zip_ctx *ctx, const int64_t *evals, size_t n_evals, z
         // whose last entry is stretched / cut to the number of rounds
         std::vector<uint32_t> sched;
         if (with_merkle && rounds <= 64) {
-            static const char *env = getenv("ZIP_HIP_CHUNK_ROUNDS");
+            const char *env = ctx->knob_chunk_rounds.empty() ? nullptr : ctx->knob_chunk_rounds.c_str();
             if (env && !ctx->n_chunks) {
                 uint32_t used = 0;
                 for (const char *q = env; *q && used < rounds;) {
@@ -2663,8 +2673,7 @@ static int32_t ensure_columns(zip_commitment *c, const uint32_t *cols, uint32_t 
 // An opening names the columns this ctx's prover squeezes: the next plain zip_commit hints itself with them.
 static void note_columns(zip_ctx *ctx, const uint32_t *cols, uint32_t n_cols) {
     if (!ctx->speculate || !n_cols || !commit_supports_hint(ctx->p.codeword_len)) return;
-    static const bool no_compact = getenv("ZIP_HIP_NO_COMPACT_ROWS") != nullptr;
-    (void)get_hint_plan(ctx, cols, n_cols, !no_compact && packed_enabled());
+    (void)get_hint_plan(ctx, cols, n_cols, !ctx->no_compact && packed_enabled());
     ctx->seen_columns = true;
 }
 
