@@ -138,6 +138,30 @@ size_t zinc_pcs_transcript_position(const zinc_pcs_transcript *t);
 int32_t zinc_zip_verify(const zinc_zip_params *vp, const uint8_t *roots, const uint64_t *point, size_t point_len,
                         const uint64_t *eval, const uint64_t *modulus, uint32_t limbs, zinc_pcs_transcript *transcript);
 
+/* MultilinearZip::batch_verify_z (src/zip/pcs/verify_z.rs:40-58): verify per polynomial on ONE transcript.  With at
+ * least two polynomials, codewords up to 16384, one proximity test and every point of num_vars coordinates, the host
+ * walks the shared transcript over the streams that are all there and makes ONE device call for all of them (zip_hip.h,
+ * the batched verifier); otherwise, or with ZIP_HIP_BATCH=0, it is the loop over verify.  Result, error message,
+ * transcript and cursor are the loop's either way: after a rejected polynomial i the cursor is at the start of its stream.
+ *   roots       n_polys * num_rows * 32 bytes, polynomial-major
+ *   points      n_polys pointers to point_lens[i] * limbs Montgomery limbs
+ *   evals       n_polys * limbs Montgomery limbs */
+int32_t zinc_zip_batch_verify(const zinc_zip_params *vp, const uint8_t *roots, const uint64_t *const *points,
+                              const size_t *point_lens, const uint64_t *evals, size_t n_polys, const uint64_t *modulus,
+                              uint32_t limbs, zinc_pcs_transcript *transcript);
+/* The Fiat-Shamir walk of batch_verify_z -- host only, what a Rust shim runs in front of the one device call.  In
+ * `verify` only read_field_elements absorbs (pcs_transcript.rs:91-103), and what it absorbs are the last
+ * row_len * 8 * limbs bytes of the stream itself.  Per polynomial, in the reference's order: get_integer_challenges over
+ * num_rows (only if num_rows > 1, verify_z.rs:69-72), n_cols times squeeze_challenge_idx over codeword_len (:88-90),
+ * then the absorption of the evaluation row at the end of its stream.  The transcript's cursor is not moved.
+ *   proofs      n_polys whole streams of stream_len bytes each
+ *   coeffs_out  n_polys * num_rows (untouched when num_rows == 1; may then be NULL)
+ *   cols_out    n_polys * n_cols */
+int32_t zinc_zip_batch_verify_challenges(uint32_t num_rows, uint32_t row_len, uint32_t codeword_len, uint32_t n_cols,
+                                         const uint64_t *modulus, uint32_t limbs, zinc_pcs_transcript *transcript,
+                                         const uint8_t *proofs, size_t stream_len, size_t n_polys, int64_t *coeffs_out,
+                                         uint32_t *cols_out);
+
 /* z_mle.map_to_field(config).evaluate(r_y) (src/zinc/prover.rs:317-319): out = limbs Montgomery limbs */
 int32_t zinc_zip_evaluate(const zinc_zip_params *pp, const int64_t *evals, size_t n_evals, const uint64_t *point,
                           size_t point_len, const uint64_t *modulus, uint32_t limbs, uint64_t *out);

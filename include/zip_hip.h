@@ -42,7 +42,8 @@ extern "C" {
 /* (zip_keccak_state and zip_sumcheck_prove came later and are purely additive: no existing entry point or structure
  * changed, so the version stays 3; a caller that needs them looks the symbol up.  Likewise zip_sumcheck_init taking
  * up to 8 tables instead of 4: a widening, every call that was valid means what it meant.  The batch entry points,
- * zip_batch_commit and the five beside it, are additive in the same way.) */
+ * zip_batch_commit and the five beside it, are additive in the same way, and so are zip_batch_verify and
+ * zip_batch_verify_calls.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -255,6 +256,7 @@ int32_t zip_job_wait(zip_job *job, uint8_t *roots_out);
  * machine one at a time (2^12: 64 one-wave workgroups): all polynomials of a batch share the ctx's geometry and
  * permutations, every row has its own Merkle tree, so B polynomials of R rows are B * R rows to ONE commit launch, and
  * the open is one launch set with the polynomial as a grid dimension.  The number of launches does not depend on B.
+ * The verifier's side of the family, zip_batch_verify, is declared with zip_verify below.
  * Unsharded ctx, codeword_len <= 16384, 1 <= n_polys <= 65535, n_polys * num_rows < 2^32.
  *
  * zip_batch_commit: MultilinearZip::commit (with Merkle trees) of n_polys polynomials.
@@ -346,6 +348,37 @@ int32_t zip_verify(zip_ctx *ctx, const uint8_t *roots, const uint8_t *proof, zip
                    const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont,
                    const uint64_t *q1_mont, const uint64_t *eval_mont, const zip_field *field,
                    zip_verify_report *report);
+
+/* zip_batch_verify: MultilinearZip::batch_verify_z (verify_z.rs:40-58) for n_polys proofs of the ctx's geometry in one
+ * launch set -- the third member of the batch family above, with the same constraints (unsharded ctx, codeword_len
+ * <= 16384, 1 <= n_polys <= 65535).  batch_verify_z runs verify per polynomial on ONE PcsTranscript, so the challenges
+ * of polynomial i depend on what polynomials 0 .. i-1 absorbed; but in `verify` only read_field_elements absorbs
+ * (pcs_transcript.rs:91-103; read_integers and read_merkle_proof do not, :137-155, :181-196), and what it absorbs are
+ * bytes of the stream itself at a known offset, the last row_len * 8 * limbs bytes of stream i.  The whole transcript
+ * walk -- per polynomial: squeeze the coefficients (num_rows > 1), squeeze the columns, absorb the row read from the
+ * stream -- is therefore host work that needs no verdict; the caller does it first and then makes this one call.
+ *   proofs      HOST or DEVICE per proofs_kind; stream i starts at byte i * zip_proof_len(ctx, n_cols, field->limbs)
+ *               (a multiple of 8, not of 16): the layout zip_batch_open writes
+ *   proofs_len  bytes available at `proofs`.  A polynomial whose stream does not lie wholly inside gets
+ *               ZIP_VERIFY_MALFORMED with zero counts (what zip_verify gives a short stream) and never reaches the
+ *               device; the polynomials before it are verified.
+ *   HOST, polynomial-major: roots n_polys * num_rows * 32 bytes; coeffs n_polys * num_rows (NULL when num_rows == 1);
+ *               cols n_polys * n_cols; q0_mont n_polys * num_rows * limbs (NULL when num_rows == 1); q1_mont
+ *               n_polys * row_len * limbs (may be NULL when row_len == 1); evals_mont n_polys * limbs
+ *   reports     HOST, n_polys entries.  reports[i] equals, field by field, what zip_verify returns for polynomial i's
+ *               slices, for every input, with every deliberate deviation documented there.
+ * Five kernel launches whatever n_polys is, one device-to-host copy (of the n_polys reports), one synchronisation.
+ * Errors, before anything reaches the device: ZIP_ERR_NULL (ctx, roots, proofs, reports, evals_mont; cols when
+ * n_cols != 0; a needed coeffs / q0_mont / q1_mont), ZIP_ERR_INVALID_PARAM (n_polys 0 or above 65535, row-sharded ctx,
+ * a column index >= codeword_len), ZIP_ERR_UNSUPPORTED (codeword_len above 16384, n_polys * n_cols beyond 32 bits,
+ * field limbs outside {2, 3, 4}).
+ * zip_batch_verify_calls: process-wide, monotonic count of zip_batch_verify calls that reached the device (tests and
+ * tools read from it which path a caller took; kept like zip_sumcheck_launch_counts). */
+int32_t zip_batch_verify(zip_ctx *ctx, uint32_t n_polys, const uint8_t *roots, const uint8_t *proofs,
+                         zip_mem_kind proofs_kind, size_t proofs_len, const int64_t *coeffs, const uint32_t *cols,
+                         uint32_t n_cols, const uint64_t *q0_mont, const uint64_t *q1_mont, const uint64_t *evals_mont,
+                         const zip_field *field, zip_verify_report *reports);
+uint64_t zip_batch_verify_calls(void);
 
 /* ---- sumcheck prover --------------------------------------------
  * IPForMLSumcheck::prove_round (src/sumcheck/prover.rs:62-180) for the two combination functions

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "zip_ccs_create", "zip_ccs_free", "zip_ccs_last_error", "zip_ccs_set_z", "zip_ccs_eq_table",
     "zip_ccs_second_table", "zip_ccs_table", "zip_ccs_download", "zip_ccs_eval_matrices",
     "zip_batch_commit", "zip_batch_size", "zip_batch_free", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open",
+    "zip_batch_verify", "zip_batch_verify_calls",
 )
 
 
@@ -207,6 +208,11 @@ def lib():
     L.zip_job_wait.restype = C.c_int32
     L.zip_verify.argtypes = [vp, u8p, vp, C.c_int, C.c_size_t, i64p, u32p, C.c_uint32, u64p, u64p, u64p,
                              C.POINTER(ZipField), C.POINTER(VerifyReport)]
+    L.zip_batch_verify.argtypes = [vp, C.c_uint32, u8p, vp, C.c_int, C.c_size_t, i64p, u32p, C.c_uint32, u64p, u64p, u64p,
+                                   C.POINTER(ZipField), C.POINTER(VerifyReport)]
+    L.zip_batch_verify.restype = C.c_int32
+    L.zip_batch_verify_calls.argtypes = []
+    L.zip_batch_verify_calls.restype = C.c_uint64
     L.zip_mle_eval.argtypes = [vp, i64p, C.c_int, u64p, u64p, C.POINTER(ZipField), u64p]
     L.zip_commitment_mle_eval.argtypes = [vp, u64p, u64p, C.POINTER(ZipField), u64p]
     L.zip_field_map_int256.argtypes = [vp, u64p, C.c_uint32, C.POINTER(ZipField), u64p]
@@ -531,6 +537,39 @@ class ZipContext:
         return {"verdict": rep.verdict, "column": rep.column, "bad_merkle_paths": rep.bad_merkle_paths,
                 "malformed_paths": rep.malformed_paths}
 
+    def batch_verify(self, roots, proofs, coeffs, cols, q0_mont, q1_mont, evals_mont, field: ZipField, proofs_len=None):
+        """zip_batch_verify: MultilinearZip::verify of every proof stream in `proofs` (numpy array or CUDA tensor, stream i
+        at byte i * proof_len) in one launch set.  roots [n, num_rows, 32], coeffs [n, num_rows], cols [n, n_cols], q0_mont
+        [n, num_rows, limbs], q1_mont [n, row_len, limbs], evals_mont [n, limbs]; coeffs / q0_mont / q1_mont are None where
+        zip_verify takes none.  proofs_len: the bytes to treat as available (default: all of `proofs`).
+        -> a list of n report dicts shaped like the one verify returns."""
+        roots_c = np.ascontiguousarray(roots, dtype=np.uint8)
+        cols_c = np.ascontiguousarray(cols, dtype=np.uint32)
+        n_polys, n_cols = cols_c.shape
+        coeffs_c = None if coeffs is None else np.ascontiguousarray(coeffs, dtype=np.int64)
+        q0 = None if q0_mont is None else np.ascontiguousarray(q0_mont, dtype=np.uint64)
+        q1 = None if q1_mont is None else np.ascontiguousarray(q1_mont, dtype=np.uint64)
+        ev = np.ascontiguousarray(evals_mont, dtype=np.uint64)
+        assert roots_c.size == n_polys * self.num_rows * 32 and ev.size == n_polys * field.limbs
+        assert coeffs_c is None or coeffs_c.size == n_polys * self.num_rows
+        assert q0 is None or q0.size == n_polys * self.num_rows * field.limbs
+        assert q1 is None or q1.size == n_polys * self.row_len * field.limbs
+        if isinstance(proofs, np.ndarray):
+            proofs = np.ascontiguousarray(proofs, dtype=np.uint8)
+        pptr, pkind = _ptr(proofs)
+        plen = proofs.size if isinstance(proofs, np.ndarray) else proofs.numel() * proofs.element_size()
+        if proofs_len is not None:
+            assert proofs_len <= plen
+            plen = proofs_len
+        reps = (VerifyReport * n_polys)()
+        rc = lib().zip_batch_verify(self._h, n_polys, roots_c.ctypes.data, pptr, pkind, plen,
+                                    None if coeffs_c is None else coeffs_c.ctypes.data, cols_c.ctypes.data, n_cols,
+                                    None if q0 is None else q0.ctypes.data, None if q1 is None else q1.ctypes.data,
+                                    ev.ctypes.data, C.byref(field), reps)
+        self._check(rc, "zip_batch_verify")
+        return [{"verdict": r.verdict, "column": r.column, "bad_merkle_paths": r.bad_merkle_paths,
+                 "malformed_paths": r.malformed_paths} for r in reps]
+
     def mle_eval(self, evals, q0_mont, q1_mont, field: ZipField):
         ptr, kind = _ptr(evals)
         q0 = None if q0_mont is None else np.ascontiguousarray(q0_mont, dtype=np.uint64)
@@ -832,6 +871,11 @@ def merkle_trees(leaves, depth, device=0):
     if rc != ZIP_OK:
         raise ZipError(rc, "zip_merkle_trees")
     return out
+
+
+def batch_verify_calls() -> int:
+    """zip_batch_verify_calls: zip_batch_verify calls of this process that reached the device"""
+    return lib().zip_batch_verify_calls()
 
 
 def sumcheck_launch_counts():

@@ -1,0 +1,421 @@
+// Batched verifier kernels: MultilinearZip::verify of MANY small proofs that share one zip_ctx (zip_batch_verify).
+// The polynomial is a grid dimension, so the number of launches does not depend on how many there are, and the verdict
+// is folded on the device: n_polys reports come back, not 3 * n_cols words per proof.
+//
+// Reference loops replaced (per polynomial, as in kernels_verify.cuh):
+//   encode_wide / encode_f (one row)             src/zip/code_raa.rs:107-138
+//   read_field_elements + <row, q1>              src/zip/pcs_transcript.rs:138-160, src/zip/pcs/verify_z.rs:139-149
+//   verify_column_testing / verify_proximity_q_0 src/zip/pcs/verify_z.rs:88-127,165-188
+//   MerkleProof::verify                          src/zip/pcs/utils.rs:178-210
+// and the loop over the polynomials itself, src/zip/pcs/verify_z.rs:40-58.
+//
+// Proof stream b starts at proofs + b * stream_bytes, a multiple of 8 bytes and not of 16: every wire load is 8 bytes.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "blake3.cuh"
+#include "kernels_open.cuh"
+#include "kernels_verify.cuh"
+
+namespace zipk {
+
+// what the two encodings leave per polynomial for the report kernel
+struct BatchVerifyHead {
+    uint32_t overflow, noncanonical, pad[2];
+    uint64_t dot[4];  // <row, q1>, Montgomery
+};
+
+// zip_verify_report and zip_verify_verdict (include/zip_hip.h; the library asserts that they agree)
+struct BatchVerifyReport {
+    int32_t verdict;
+    uint32_t column, bad_merkle_paths, malformed_paths;
+};
+constexpr int32_t kVerdictAccept = 0, kVerdictProximityTesting = 1, kVerdictEvalConsistency = 2, kVerdictProximityQ0 = 3,
+                  kVerdictMerkle = 4, kVerdictMalformed = 5, kVerdictOverflow = 6;
+
+// ---------------------------------------------------------------------------------------
+// encode_row_kernel with the polynomial as blockIdx.x and the input row read where it lies in proof stream b:
+//   FIELD = false: u', L-limb little-endian integers at the start of the stream; head[b].overflow
+//   FIELD = true : the evaluation row, big-endian Montgomery values at in_at; head[b].noncanonical counts
+//                  elements >= q (not range-checked by the reference: see zip_verify in zip_hip.h) and
+//                  head[b].dot = <row, q1[b]> -- decode_field_row_kernel and field_dot_kernel in the same workgroup.
+// Grid (n_polys), blockDim.x = T threads sized to cw by the host, dynamic LDS T * sizeof(EncElem<L, FIELD>).
+// ---------------------------------------------------------------------------------------
+struct BatchEncodeArgs {
+    const uint8_t *proofs;
+    size_t stream_bytes, in_at;
+    uint32_t row_len, cw;
+    const uint32_t *perm1, *perm2;
+    uint64_t *tmp, *out;     // [n_polys][cw][L]
+    const uint64_t *q1;      // FIELD: [n_polys][row_len][L], or null (row_len == 1)
+    uint32_t clear_overflow; // FIELD: no encode_wide runs (num_rows == 1); this kernel zeroes head[b].overflow
+    BatchVerifyHead *head;   // [n_polys]
+};
+
+template <int L, bool FIELD>
+__device__ __forceinline__ void batch_enc_load_wire(EncElem<L, FIELD> &x, const uint64_t *p) {
+    if constexpr (FIELD) {
+#pragma unroll
+        for (int i = 0; i < L; i++) x.v[i] = __builtin_bswap64(p[L - 1 - i]);
+    } else {
+        enc_load<L, FIELD>(x, p);
+    }
+}
+
+template <int L, bool FIELD>
+__global__ void __launch_bounds__(1024) batch_encode_kernel(BatchEncodeArgs a, FieldDev<L> f) {
+    extern __shared__ __align__(16) unsigned char benc_smem[];
+    using El = EncElem<L, FIELD>;
+    El *tot = reinterpret_cast<El *>(benc_smem);  // [blockDim.x]
+    const uint32_t T = blockDim.x, tid = threadIdx.x, b = blockIdx.x, cw = a.cw;
+    const uint64_t *in = reinterpret_cast<const uint64_t *>(a.proofs + (size_t)b * a.stream_bytes + a.in_at);
+    uint64_t *tmp = a.tmp + (size_t)b * cw * L, *out = a.out + (size_t)b * cw * L;
+    const uint32_t per = (cw + T - 1) / T;
+    const uint32_t j0 = tid * per, j1 = min(j0 + per, cw);
+    bool ovf = false;
+    for (int pass = 0; pass < 2; pass++) {
+        // source of element j: pass 0 = repeated input row through pi1, pass 1 = tmp through pi2
+        auto fetch = [&](uint32_t j, El &x) {
+            if (pass == 0) batch_enc_load_wire<L, FIELD>(x, in + (size_t)(a.perm1[j] & (a.row_len - 1)) * L);
+            else enc_load<L, FIELD>(x, tmp + (size_t)a.perm2[j] * L);
+        };
+        El sum;
+        enc_zero<L, FIELD>(sum);
+        for (uint32_t j = j0; j < j1; j++) {
+            El x;
+            fetch(j, x);
+            enc_add<L, FIELD>(sum, x, f);
+        }
+        tot[tid] = sum;
+        __syncthreads();
+        // inclusive scan of the T chunk totals in place, as in encode_row_kernel
+        for (uint32_t off = 1; off < T; off <<= 1) {
+            El x;
+            enc_zero<L, FIELD>(x);
+            if (tid >= off) x = tot[tid - off];
+            __syncthreads();
+            if (tid >= off) {
+                El y = tot[tid];
+                enc_add<L, FIELD>(y, x, f);
+                tot[tid] = y;
+            }
+            __syncthreads();
+        }
+        El run;
+        enc_zero<L, FIELD>(run);
+        if (tid) run = tot[tid - 1];
+        uint64_t *dst = pass == 0 ? tmp : out;
+        for (uint32_t j = j0; j < j1; j++) {
+            El x;
+            fetch(j, x);
+            enc_add<L, FIELD>(run, x, f);
+            ovf |= enc_store<L, FIELD>(run, dst + (size_t)j * L);
+        }
+        __threadfence_block();
+        __syncthreads();  // (pass 1 reads tmp; the tail below reuses tot)
+    }
+    if constexpr (!FIELD) {
+        const int any = __syncthreads_or(ovf ? 1 : 0);
+        if (tid == 0) a.head[b].overflow = any ? 1u : 0u;
+    } else {
+        // the row once more: range check and <row, q1>
+        uint32_t nc = 0;
+        uint64_t acc[L];
+#pragma unroll
+        for (int i = 0; i < L; i++) acc[i] = 0;
+        const uint64_t *q1 = a.q1 ? a.q1 + (size_t)b * a.row_len * L : nullptr;
+        for (uint32_t c = tid; c < a.row_len; c += T) {
+            El x;
+            batch_enc_load_wire<L, FIELD>(x, in + (size_t)c * L);
+            if (geq_n<L>(x.v, f.modulus)) nc++;
+            if (q1) {
+                uint64_t y[L], t[L];
+#pragma unroll
+                for (int i = 0; i < L; i++) y[i] = q1[(size_t)c * L + i];
+                mont_mul<L>(x.v, y, f, t);
+                const uint64_t cy = add_n<L>(acc, t);
+                if (cy || geq_n<L>(acc, f.modulus)) sub_n<L>(acc, f.modulus);
+            }
+        }
+        const int any_nc = __syncthreads_or(nc ? 1 : 0);
+#pragma unroll
+        for (int i = 0; i < L; i++) tot[tid].v[i] = acc[i];
+        __syncthreads();
+        for (uint32_t s = T / 2; s > 0; s >>= 1) {  // (T is a power of two)
+            if (tid < s) {
+                El p = tot[tid];
+                enc_add<L, FIELD>(p, tot[tid + s], f);
+                tot[tid] = p;
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            BatchVerifyHead &h = a.head[b];
+            if (a.clear_overflow) h.overflow = 0;
+            h.noncanonical = any_nc ? 1u : 0u;
+#pragma unroll
+            for (int i = 0; i < 4; i++) h.dot[i] = i < L ? tot[0].v[i < L ? i : 0] : 0;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// Every (polynomial, opening): hash the paths, form the two column inner products, compare them with the encoded
+// combined rows.  A 256-thread workgroup serves ONE polynomial (blockIdx.y) and
+//   num_rows <  256: 256 / num_rows consecutive openings, one thread per opened entry -- every lane hashes a path;
+//   num_rows >= 256: one opening, thread t walks rows t, t + 256, ... (the polynomials supply the parallelism, as in
+//                    batch_combine_kernel): no row-block partials, no finalize pass.
+// The sums of an opening are reduced by a butterfly of wave shuffles over its min(num_rows, 64) lanes (384-bit
+// wrap-around adds and modular adds: both commute), then over its waves through 4 LDS slots.
+// flags[b][ci]: bit 0 = proximity test over Z failed (verify_z.rs:122-125), bit 1 = over F_q (:184-186).
+// Grid (ceil(n_cols / openings per workgroup), n_polys).
+// ---------------------------------------------------------------------------------------
+struct BatchVerifyColsArgs {
+    const uint8_t *proofs;
+    size_t stream_bytes, openings_at;  // length of one stream; where its column openings start (behind u')
+    const uint32_t *cols;    // [n_polys][n_cols]
+    const int64_t *coeffs;   // [n_polys][num_rows] or null (num_rows == 1)
+    const uint64_t *q0;      // [n_polys][num_rows][FL] Montgomery, or null (num_rows == 1)
+    const uint32_t *roots;   // [n_polys][num_rows][8]
+    const uint64_t *enc_u;   // [n_polys][cw][8] or null (num_rows == 1)
+    const uint64_t *enc_f;   // [n_polys][cw][FL]
+    uint32_t num_rows, depth, n_cols, cw, quirk;
+    uint32_t *flags, *bad_merkle, *malformed;  // [n_polys][n_cols]
+};
+
+template <int FL>
+__global__ void __launch_bounds__(256) batch_verify_columns_kernel(BatchVerifyColsArgs a, FieldDev<FL> f, FieldDev<FL> fq) {
+    constexpr int W = 6 + FL;
+    __shared__ uint64_t wave_sum[4][W];
+    __shared__ uint32_t s_bad[256], s_mal[256];
+    const uint32_t tid = threadIdx.x, b = blockIdx.y, R = a.num_rows;
+    const uint32_t lgS = R < 256 ? (uint32_t)__ffs((int)R) - 1 : 8;  // (num_rows is a power of two)
+    const uint32_t S = 1u << lgS;                                    // threads per opening
+    const uint32_t o = tid >> lgS, r0 = tid & (S - 1);
+    const uint32_t ci = (blockIdx.x << (8 - lgS)) + o;
+    const bool live = ci < a.n_cols;
+    s_bad[tid] = 0;
+    s_mal[tid] = 0;
+    __syncthreads();
+
+    uint64_t si[6] = {0, 0, 0, 0, 0, 0}, sf[FL];
+#pragma unroll
+    for (int i = 0; i < FL; i++) sf[i] = 0;
+    uint32_t col = 0;
+    if (live) {
+        col = a.cols[(size_t)b * a.n_cols + ci];
+        const uint32_t d = a.depth, rec_bytes = 8 + 32 * d;
+        const size_t col_bytes = (size_t)R * (32 + rec_bytes);
+        const uint8_t *base = a.proofs + (size_t)b * a.stream_bytes + a.openings_at + (size_t)ci * col_bytes;
+        const int64_t *coeffs = a.coeffs ? a.coeffs + (size_t)b * R : nullptr;
+        const uint64_t *q0 = a.q0 ? a.q0 + (size_t)b * R * FL : nullptr;
+        const uint32_t *roots = a.roots + (size_t)b * R * 8;
+        uint32_t n_bad = 0, n_mal = 0;
+        for (uint32_t r = r0; r < R; r += 256) {
+            uint64_t v[4];
+            const uint64_t *vp = reinterpret_cast<const uint64_t *>(base + (size_t)r * 32);
+#pragma unroll
+            for (int i = 0; i < 4; i++) v[i] = vp[i];
+            // ---- coeffs[r] * expand(v) in 384-bit two's complement (verify_z.rs:114-120) ----
+            if (coeffs) {
+                uint64_t t[6];
+                const int64_t c = coeffs[r];
+                const uint64_t cu = (uint64_t)c;
+                uint64_t carry = 0;
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const u128 x = (u128)v[i] * cu + carry;
+                    t[i] = (uint64_t)x;
+                    carry = (uint64_t)(x >> 64);
+                }
+                t[4] = carry;
+                t[5] = 0;
+                if ((int64_t)v[3] < 0) {  // v = v_u - 2^256
+                    const u128 x = (u128)t[4] - cu;
+                    t[4] = (uint64_t)x;
+                    t[5] -= (uint64_t)(x >> 64) & 1;
+                }
+                if (c < 0) {  // c = c_u - 2^64, with v sign-extended to 5 limbs above bit 64
+                    uint64_t borrow = 0;
+                    const uint64_t ext = (uint64_t)((int64_t)v[3] >> 63);
+#pragma unroll
+                    for (int i = 0; i < 5; i++) {
+                        const uint64_t sub = i < 4 ? v[i] : ext;
+                        const u128 x = (u128)t[i + 1] - sub - borrow;
+                        t[i + 1] = (uint64_t)x;
+                        borrow = (uint64_t)(x >> 64) & 1;
+                    }
+                }
+                add_n<6>(si, t);
+            }
+            // ---- q0[r] (x) phi(v)  (verify_z.rs:176-183) ----
+            {
+                uint64_t e[FL], t[FL];
+                field_from_int256<FL>(v, f, fq, a.quirk != 0, e);
+                if (q0) {
+                    uint64_t q[FL];
+#pragma unroll
+                    for (int i = 0; i < FL; i++) q[i] = q0[(size_t)r * FL + i];
+                    mont_mul<FL>(q, e, f, t);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < FL; i++) t[i] = e[i];
+                }
+                const uint64_t cy = add_n<FL>(sf, t);
+                if (cy || geq_n<FL>(sf, f.modulus)) sub_n<FL>(sf, f.modulus);
+            }
+            // ---- MerkleProof::verify (pcs/utils.rs:178-210) ----
+            const uint64_t *rec = reinterpret_cast<const uint64_t *>(base + (size_t)R * 32 + (size_t)r * rec_bytes);
+            if (rec[0] != __builtin_bswap64((uint64_t)d)) {
+                n_mal++;
+            } else {
+                uint32_t cur[8];
+                blake3_leaf_limbs<4>(v, cur);
+                uint32_t index = col;
+                for (uint32_t l = 0; l < d; l++) {
+                    uint32_t sib[8];
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        const uint64_t w = rec[1 + 4 * l + i];
+                        sib[2 * i] = (uint32_t)w;
+                        sib[2 * i + 1] = (uint32_t)(w >> 32);
+                    }
+                    uint32_t m[16], h[8];
+                    const bool right = index & 1u;  // current node is the right child
+#pragma unroll
+                    for (int i = 0; i < 8; i++) {
+                        m[i] = right ? sib[i] : cur[i];
+                        m[8 + i] = right ? cur[i] : sib[i];
+                    }
+                    blake3_block64(m, h);
+#pragma unroll
+                    for (int i = 0; i < 8; i++) cur[i] = h[i];
+                    index >>= 1;
+                }
+                bool ok = true;
+#pragma unroll
+                for (int i = 0; i < 8; i++) ok &= cur[i] == roots[(size_t)r * 8 + i];
+                if (!ok) n_bad++;
+            }
+        }
+        if (n_bad) atomicAdd(&s_bad[o], n_bad);
+        if (n_mal) atomicAdd(&s_mal[o], n_mal);
+    }
+    // ---- the sums of one opening: butterfly over its lanes of this wave (dead lanes hold zeros) ----
+    const uint32_t span = S < 64 ? S : 64;
+    for (uint32_t off = 1; off < span; off <<= 1) {
+        uint64_t y[6], q[FL];
+#pragma unroll
+        for (int i = 0; i < 6; i++) y[i] = __shfl_xor(si[i], (int)off);
+#pragma unroll
+        for (int i = 0; i < FL; i++) q[i] = __shfl_xor(sf[i], (int)off);
+        add_n<6>(si, y);
+        const uint64_t cy = add_n<FL>(sf, q);
+        if (cy || geq_n<FL>(sf, f.modulus)) sub_n<FL>(sf, f.modulus);
+    }
+    // ---- ... and over its waves (S = 128 or 256) ----
+    if (S > 64 && (tid & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) wave_sum[tid >> 6][i] = si[i];
+#pragma unroll
+        for (int i = 0; i < FL; i++) wave_sum[tid >> 6][6 + i] = sf[i];
+    }
+    __syncthreads();
+    if (!live || r0 != 0) return;
+    if (S > 64) {
+        const uint32_t w0 = tid >> 6, nw = S >> 6;
+        for (uint32_t w = w0 + 1; w < w0 + nw; w++) {
+            uint64_t y[6], q[FL];
+#pragma unroll
+            for (int i = 0; i < 6; i++) y[i] = wave_sum[w][i];
+#pragma unroll
+            for (int i = 0; i < FL; i++) q[i] = wave_sum[w][6 + i];
+            add_n<6>(si, y);
+            const uint64_t cy = add_n<FL>(sf, q);
+            if (cy || geq_n<FL>(sf, f.modulus)) sub_n<FL>(sf, f.modulus);
+        }
+    }
+    // ---- the opening's leader holds the complete column sums: compare (verify_finalize_kernel's checks) ----
+    uint32_t fl = 0;
+    if (a.enc_u) {
+        const uint64_t *eu = a.enc_u + ((size_t)b * a.cw + col) * 8;
+        const uint64_t sign = (uint64_t)((int64_t)si[5] >> 63);
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if (eu[i] != (i < 6 ? si[i < 6 ? i : 0] : sign)) fl |= 1u;
+    }
+    const uint64_t *ef = a.enc_f + ((size_t)b * a.cw + col) * FL;
+#pragma unroll
+    for (int i = 0; i < FL; i++)
+        if (ef[i] != sf[i]) fl |= 2u;
+    const size_t slot = (size_t)b * a.n_cols + ci;
+    a.flags[slot] = fl;
+    a.bad_merkle[slot] = s_bad[o];
+    a.malformed[slot] = s_mal[o];
+}
+
+// ---------------------------------------------------------------------------------------
+// One workgroup per polynomial folds its n_cols entries into a zip_verify_report: the two counts, and the first
+// failing check in the order zip_verify applies (the reference's, verify_z.rs:60-163, with zip_verify's documented
+// deviations).  evals: the claimed evaluations [n_polys][FL]; for a one-column matrix <row, q1> is 0.
+// ---------------------------------------------------------------------------------------
+struct BatchVerifyReportArgs {
+    const uint32_t *flags, *bad_merkle, *malformed;  // [n_polys][n_cols]
+    const BatchVerifyHead *head;                     // [n_polys]
+    const uint64_t *evals;                           // [n_polys][FL]
+    uint32_t n_cols, row_len;
+    BatchVerifyReport *reports;                      // [n_polys]
+};
+
+template <int FL>
+__global__ void __launch_bounds__(256) batch_verify_report_kernel(BatchVerifyReportArgs a) {
+    __shared__ uint32_t s_first_a, s_first_b, s_bad, s_mal;
+    const uint32_t tid = threadIdx.x, b = blockIdx.x, n = a.n_cols;
+    const uint32_t *flags = a.flags + (size_t)b * n, *bad = a.bad_merkle + (size_t)b * n, *mal = a.malformed + (size_t)b * n;
+    if (tid == 0) {
+        s_first_a = s_first_b = 0xFFFFFFFFu;
+        s_bad = s_mal = 0;
+    }
+    __syncthreads();
+    uint32_t first_a = 0xFFFFFFFFu, first_b = 0xFFFFFFFFu, n_bad = 0, n_mal = 0;
+    for (uint32_t ci = tid; ci < n; ci += 256) {
+        const uint32_t fl = flags[ci], nb = bad[ci], nm = mal[ci];
+        n_bad += nb;
+        n_mal += nm;
+        if (((fl & 1u) || nb || nm) && first_a == 0xFFFFFFFFu) first_a = ci;
+        if ((fl & 2u) && first_b == 0xFFFFFFFFu) first_b = ci;
+    }
+    if (n_bad) atomicAdd(&s_bad, n_bad);
+    if (n_mal) atomicAdd(&s_mal, n_mal);
+    if (first_a != 0xFFFFFFFFu) atomicMin(&s_first_a, first_a);
+    if (first_b != 0xFFFFFFFFu) atomicMin(&s_first_b, first_b);
+    __syncthreads();
+    if (tid != 0) return;
+    const BatchVerifyHead &h = a.head[b];
+    BatchVerifyReport rep;
+    rep.verdict = kVerdictAccept;
+    rep.column = 0;
+    rep.bad_merkle_paths = s_bad;
+    rep.malformed_paths = s_mal;
+    bool eval_differs = false;
+#pragma unroll
+    for (int i = 0; i < FL; i++) eval_differs |= a.evals[(size_t)b * FL + i] != (a.row_len > 1 ? h.dot[i] : 0);
+    if (h.overflow) {
+        rep.verdict = kVerdictOverflow;
+    } else if (s_first_a != 0xFFFFFFFFu) {
+        const uint32_t ci = s_first_a;
+        rep.column = ci;
+        rep.verdict = (flags[ci] & 1u) ? kVerdictProximityTesting : mal[ci] ? kVerdictMalformed : kVerdictMerkle;
+    } else if (eval_differs) {
+        rep.verdict = kVerdictEvalConsistency;
+    } else if (h.noncanonical) {
+        rep.verdict = kVerdictMalformed;
+    } else if (s_first_b != 0xFFFFFFFFu) {
+        rep.verdict = kVerdictProximityQ0;
+        rep.column = s_first_b;
+    }
+    a.reports[b] = rep;
+}
+
+}  // namespace zipk

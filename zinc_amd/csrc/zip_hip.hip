@@ -28,6 +28,7 @@
 #include "kernels_open.cuh"
 #include "kernels_batch.cuh"
 #include "kernels_verify.cuh"
+#include "kernels_batch_verify.cuh"
 #include "kernels_sumcheck.cuh"
 #include "kernels_sumcheck_tail.cuh"
 #include "kernels_sumcheck_wide.cuh"
@@ -1595,6 +1596,135 @@ int32_t run_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, std
     flags.assign(w, w + n_cols);
     bad.assign(w + n_cols, w + 2 * n_cols);
     malformed.assign(w + 2 * n_cols, w + 3 * n_cols);
+    return ZIP_OK;
+}
+
+// ---- the batched verifier (zip_batch_verify): five launches whatever n_polys is -- encode_wide(u'), encode_f(row) with
+// the decode and <row, q1> fused in, the column checks, the reports -- one device-to-host copy of n_polys reports, one wait.
+static_assert(sizeof(BatchVerifyReport) == sizeof(zip_verify_report) && offsetof(BatchVerifyReport, column) == offsetof(zip_verify_report, column) &&
+                  offsetof(BatchVerifyReport, bad_merkle_paths) == offsetof(zip_verify_report, bad_merkle_paths) &&
+                  offsetof(BatchVerifyReport, malformed_paths) == offsetof(zip_verify_report, malformed_paths),
+              "the report kernel writes zip_verify_report");
+static_assert(kVerdictAccept == ZIP_VERIFY_ACCEPT && kVerdictProximityTesting == ZIP_VERIFY_PROXIMITY_TESTING &&
+                  kVerdictEvalConsistency == ZIP_VERIFY_EVAL_CONSISTENCY && kVerdictProximityQ0 == ZIP_VERIFY_PROXIMITY_Q0 &&
+                  kVerdictMerkle == ZIP_VERIFY_MERKLE && kVerdictMalformed == ZIP_VERIFY_MALFORMED && kVerdictOverflow == ZIP_VERIFY_OVERFLOW,
+              "the report kernel writes zip_verify_verdict");
+
+// Process-wide count of zip_batch_verify calls that reached the device (zip_batch_verify_calls)
+std::atomic<uint64_t> g_batch_verify_calls{0};
+
+template <int L, bool FIELD>
+int32_t launch_batch_encode(zip_ctx *ctx, BatchEncodeArgs a, uint32_t n_polys, const FieldDev<L> &fd, const char *name) {
+    const uint32_t cw = ctx->p.codeword_len;
+    const uint32_t threads = cw < 1024 ? (cw < 64 ? 64 : cw) : 1024;  // (a power of two: the dot product's tree needs one)
+    const size_t lds = (size_t)threads * sizeof(EncElem<L, FIELD>);
+    auto kern = batch_encode_kernel<L, FIELD>;
+    if (int32_t rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
+    LaunchTimer t(ctx, name);
+    hipLaunchKernelGGL(kern, dim3(n_polys), dim3(threads), lds, ctx->stream, a, fd);
+    HIP_TRY(ctx, hipGetLastError());
+    return ZIP_OK;
+}
+
+struct BatchVerifyIn {
+    const uint8_t *proofs_d;
+    size_t stream_bytes;
+    const uint8_t *roots_d;
+    const int64_t *coeffs_d;
+    const uint32_t *cols_d;
+    const uint64_t *q0_d, *q1_d, *evals_d;
+    uint32_t n_cols, n_polys;
+};
+
+template <int FL>
+int32_t run_batch_verify_fl(zip_ctx *ctx, const BatchVerifyIn &in, const HostField &hf, zip_verify_report *reports) {
+    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len, M = ctx->p.m_limbs;
+    const uint32_t n_cols = in.n_cols, B = in.n_polys;
+    const bool single = R == 1;
+    const size_t u_bytes = single ? 0 : (size_t)C * M * 8;
+    const size_t cols_bytes = (size_t)n_cols * column_bytes(ctx);
+    Scratch enc_u(ctx), enc_f(ctx), tmp(ctx), misc(ctx);
+    int32_t rc;
+    if (!single && (rc = enc_u.get((size_t)B * cw * M * 8))) return rc;
+    if ((rc = enc_f.get((size_t)B * cw * FL * 8))) return rc;
+    if ((rc = tmp.get((size_t)B * cw * (single ? FL : M) * 8))) return rc;  // (the two encodings run one after the other)
+    // misc: reports[B] | heads[B] | flags[B n] | bad[B n] | malformed[B n]; every word is written before it is read
+    const size_t per_opening = (size_t)B * n_cols * 4;
+    const size_t misc_bytes = (size_t)B * (sizeof(BatchVerifyReport) + sizeof(BatchVerifyHead)) + 3 * per_opening;
+    if ((rc = misc.get(misc_bytes))) return rc;
+    BatchVerifyReport *reports_d = misc.as<BatchVerifyReport>();
+    BatchVerifyHead *head_d = reinterpret_cast<BatchVerifyHead *>(reports_d + B);
+    uint32_t *flags_d = reinterpret_cast<uint32_t *>(head_d + B), *bad_d = flags_d + (size_t)B * n_cols,
+             *mal_d = bad_d + (size_t)B * n_cols;
+    const FieldDev<FL> fd = to_dev<FL>(hf);
+    FieldDev<FL> fq = fd;
+    bool quirk = false;
+    if constexpr (FL == 4) {
+        HostField hq;
+        quirk = make_quirk_field(hf, &hq);
+        if (quirk) fq = to_dev<4>(hq);
+    }
+    BatchEncodeArgs e{};
+    e.proofs = in.proofs_d;
+    e.stream_bytes = in.stream_bytes;
+    e.row_len = C;
+    e.cw = cw;
+    e.perm1 = ctx->perm1_d;
+    e.perm2 = ctx->perm2_d;
+    e.tmp = tmp.as<uint64_t>();
+    e.head = head_d;
+    if (!single) {  // encode_wide(u') (verify_z.rs:75-77)
+        FieldDev<8> unused{};
+        e.in_at = 0;
+        e.out = enc_u.as<uint64_t>();
+        if ((rc = launch_batch_encode<8, false>(ctx, e, B, unused, "batch_encode_wide_kernel"))) return rc;
+    }
+    // read_field_elements + encode_f + <row, q1> (verify_z.rs:139-149)
+    e.in_at = u_bytes + cols_bytes;
+    e.out = enc_f.as<uint64_t>();
+    e.q1 = C > 1 ? in.q1_d : nullptr;
+    e.clear_overflow = single ? 1u : 0u;
+    if ((rc = launch_batch_encode<FL, true>(ctx, e, B, fd, "batch_encode_field_kernel"))) return rc;
+    if (n_cols) {
+        BatchVerifyColsArgs a{};
+        a.proofs = in.proofs_d;
+        a.stream_bytes = in.stream_bytes;
+        a.openings_at = u_bytes;
+        a.cols = in.cols_d;
+        a.coeffs = single ? nullptr : in.coeffs_d;
+        a.q0 = single ? nullptr : in.q0_d;
+        a.roots = reinterpret_cast<const uint32_t *>(in.roots_d);
+        a.enc_u = single ? nullptr : enc_u.as<uint64_t>();
+        a.enc_f = enc_f.as<uint64_t>();
+        a.num_rows = R;
+        a.depth = ctx->depth;
+        a.n_cols = n_cols;
+        a.cw = cw;
+        a.quirk = quirk ? 1u : 0u;
+        a.flags = flags_d;
+        a.bad_merkle = bad_d;
+        a.malformed = mal_d;
+        const uint32_t per_wg = R < 256 ? 256 / R : 1;  // openings per workgroup
+        LaunchTimer t(ctx, "batch_verify_columns_kernel");
+        hipLaunchKernelGGL(batch_verify_columns_kernel<FL>, dim3((n_cols + per_wg - 1) / per_wg, B), dim3(256), 0, ctx->stream, a, fd, fq);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    {
+        BatchVerifyReportArgs a{};
+        a.flags = flags_d;
+        a.bad_merkle = bad_d;
+        a.malformed = mal_d;
+        a.head = head_d;
+        a.evals = in.evals_d;
+        a.n_cols = n_cols;
+        a.row_len = C;
+        a.reports = reports_d;
+        LaunchTimer t(ctx, "batch_verify_report_kernel");
+        hipLaunchKernelGGL(batch_verify_report_kernel<FL>, dim3(B), dim3(256), 0, ctx->stream, a);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(reports, reports_d, (size_t)B * sizeof(zip_verify_report), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, stream_wait(ctx->stream));
     return ZIP_OK;
 }
 
@@ -3272,6 +3402,8 @@ int32_t zip_job_wait(zip_job *j, uint8_t *roots_out) {
 // open_z.rs:43-58).  Every row has its own Merkle tree, so to the commit kernels B polynomials of R rows are B * R
 // rows: ONE launch of the kernel a single commit of this geometry takes, everything stored, nothing hinted, no chunk
 // published.  The open is two launches whatever B is (kernels_batch.cuh): the polynomial is a grid dimension.
+// The verifier's side, batch_verify_z (verify_z.rs:40-58), is zip_batch_verify beside zip_verify below: five launches
+// whatever B is (kernels_batch_verify.cuh), the verdicts folded on the device, B reports copied back.
 // =====================================================================================================
 int32_t zip_batch_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uint32_t n_polys, zip_mem_kind evals_kind,
                          uint8_t *roots_out, zip_batch **out) {
@@ -4040,6 +4172,74 @@ int32_t zip_verify(zip_ctx *ctx, const uint8_t *roots, const uint8_t *proof, zip
     report->verdict = ZIP_VERIFY_ACCEPT;
     return ZIP_OK;
 }
+
+// The batched verifier: MultilinearZip::batch_verify_z (verify_z.rs:40-58) once the caller has walked the shared
+// transcript (see zip_hip.h).  Stream i starts at byte i * zip_proof_len of `proofs`; a stream that does not lie wholly
+// inside proofs_len is malformed, as it is for zip_verify, and never reaches the device.
+int32_t zip_batch_verify(zip_ctx *ctx, uint32_t n_polys, const uint8_t *roots, const uint8_t *proofs, zip_mem_kind proofs_kind,
+                         size_t proofs_len, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont,
+                         const uint64_t *q1_mont, const uint64_t *evals_mont, const zip_field *field, zip_verify_report *reports) {
+    if (!ctx || !roots || !proofs || !reports || !evals_mont || (n_cols && !cols)) return ZIP_ERR_NULL;
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len;
+    if (n_polys == 0 || n_polys > 65535)
+        return fail(ctx, ZIP_ERR_INVALID_PARAM, "a batch holds 1 .. 65535 polynomials (got %u)", n_polys);
+    if (ctx->rows_local != R) return fail(ctx, ZIP_ERR_INVALID_PARAM, "batches need an unsharded ctx");
+    if (cw > 16384)
+        return fail(ctx, ZIP_ERR_UNSUPPORTED, "batches serve codewords up to 16384 (got %u): larger proofs are not launch-bound, "
+                    "use zip_verify", cw);
+    if ((uint64_t)n_polys * n_cols > 0xFFFFFFFFull)
+        return fail(ctx, ZIP_ERR_UNSUPPORTED, "%u x %u openings exceed 2^32", n_polys, n_cols);
+    HostField hf;
+    int32_t rc;
+    if ((rc = make_field(ctx, field, &hf))) return rc;
+    const bool single = R == 1;
+    if (!single && (!coeffs || !q0_mont)) return fail(ctx, ZIP_ERR_NULL, "coeffs / q0_mont is NULL");
+    if (C > 1 && !q1_mont) return fail(ctx, ZIP_ERR_NULL, "q1_mont is NULL");
+    if ((rc = check_cols(ctx, cols, n_polys * n_cols))) return rc;
+    memset(reports, 0, (size_t)n_polys * sizeof *reports);
+    // the reference runs out of stream in the first polynomial that is not all there (pcs_transcript.rs:125-160)
+    const size_t len = zip_proof_len(ctx, n_cols, hf.fl);
+    const uint32_t k = (uint32_t)std::min<size_t>(n_polys, proofs_len / len);
+    for (uint32_t i = k; i < n_polys; i++) reports[i].verdict = ZIP_VERIFY_MALFORMED;
+    if (k == 0) return ZIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Scratch pbuf(ctx), small(ctx);
+    const uint8_t *proofs_d = proofs;
+    if (proofs_kind == ZIP_MEM_HOST) {
+        if ((rc = pbuf.get((size_t)k * len))) return rc;
+        if ((rc = copy_h2d_bounced(ctx, pbuf.ptr, proofs, (size_t)k * len, ctx->stream))) return rc;
+        proofs_d = pbuf.as<uint8_t>();
+    }
+    SmallInputs si;
+    si.src[0] = coeffs;     si.bytes[0] = single ? 0 : (size_t)k * R * 8;
+    si.src[1] = q0_mont;    si.bytes[1] = single ? 0 : (size_t)k * R * hf.fl * 8;
+    si.src[2] = cols;       si.bytes[2] = (size_t)k * n_cols * 4;
+    si.src[3] = q1_mont;    si.bytes[3] = C > 1 ? (size_t)k * C * hf.fl * 8 : 0;
+    si.src[4] = roots;      si.bytes[4] = (size_t)k * R * 32;
+    si.src[5] = evals_mont; si.bytes[5] = (size_t)k * hf.fl * 8;
+    unsigned char *sb;
+    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
+    BatchVerifyIn in{};
+    in.proofs_d = proofs_d;
+    in.stream_bytes = len;
+    in.coeffs_d = reinterpret_cast<const int64_t *>(sb + si.off[0]);
+    in.q0_d = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
+    in.cols_d = reinterpret_cast<const uint32_t *>(sb + si.off[2]);
+    in.q1_d = reinterpret_cast<const uint64_t *>(sb + si.off[3]);
+    in.roots_d = sb + si.off[4];
+    in.evals_d = reinterpret_cast<const uint64_t *>(sb + si.off[5]);
+    in.n_cols = n_cols;
+    in.n_polys = k;
+    g_batch_verify_calls++;
+    switch (hf.fl) {
+        case 2: return run_batch_verify_fl<2>(ctx, in, hf, reports);
+        case 3: return run_batch_verify_fl<3>(ctx, in, hf, reports);
+        default: return run_batch_verify_fl<4>(ctx, in, hf, reports);
+    }
+}
+
+uint64_t zip_batch_verify_calls(void) { return g_batch_verify_calls.load(); }
 
 int32_t zip_commitment_mle_eval(zip_commitment *c, const uint64_t *q0_mont, const uint64_t *q1_mont,
                                 const zip_field *field, uint64_t *value_out) {

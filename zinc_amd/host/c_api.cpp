@@ -317,6 +317,46 @@ int32_t zinc_zip_verify(const zinc_zip_params *vp, const uint8_t *roots, const u
     });
 }
 
+int32_t zinc_zip_batch_verify(const zinc_zip_params *vp, const uint8_t *roots, const uint64_t *const *points,
+                              const size_t *point_lens, const uint64_t *evals, size_t n_polys, const uint64_t *modulus,
+                              uint32_t limbs, zinc_pcs_transcript *transcript) {
+    if (!vp || !transcript || (n_polys && (!roots || !points || !point_lens || !evals))) return ZINC_ERR_NULL;
+    return guarded([&] {
+        const FieldConfig f = FieldConfig::make(modulus, limbs);
+        const size_t root_bytes = (size_t)vp->pp.num_rows * 32;
+        std::vector<MultilinearZipCommitment> comms(n_polys);
+        std::vector<const MultilinearZipCommitment *> comm_ptrs(n_polys);
+        std::vector<std::vector<Limbs>> pts(n_polys);
+        std::vector<const Limbs *> pt_ptrs(n_polys);
+        std::vector<Limbs> evs(n_polys);
+        for (size_t i = 0; i < n_polys; i++) {
+            comms[i].roots.resize(vp->pp.num_rows);
+            std::memcpy(comms[i].roots.data(), roots + i * root_bytes, root_bytes);
+            comm_ptrs[i] = &comms[i];
+            pts[i].resize(point_lens[i]);
+            for (size_t k = 0; k < point_lens[i]; k++) pts[i][k] = load(points[i] + k * limbs, limbs);
+            pt_ptrs[i] = pts[i].data();
+            evs[i] = load(evals + i * limbs, limbs);
+        }
+        MultilinearZip::batch_verify_z(vp->pp, comm_ptrs.data(), pt_ptrs.data(), point_lens, evs.data(), n_polys, transcript->t, f);
+    });
+}
+
+int32_t zinc_zip_batch_verify_challenges(uint32_t num_rows, uint32_t row_len, uint32_t codeword_len, uint32_t n_cols,
+                                         const uint64_t *modulus, uint32_t limbs, zinc_pcs_transcript *transcript,
+                                         const uint8_t *proofs, size_t stream_len, size_t n_polys, int64_t *coeffs_out,
+                                         uint32_t *cols_out) {
+    if (!modulus || !transcript || (n_polys && (!proofs || (n_cols && !cols_out) || (num_rows > 1 && !coeffs_out))))
+        return ZINC_ERR_NULL;
+    return guarded([&] {
+        if (!codeword_len) throw ZipError(ZipError::InvalidPcsParam, "codeword_len is 0");
+        if (stream_len < (size_t)row_len * limbs * 8) throw ZipError(ZipError::InvalidPcsParam, "stream_len is shorter than the evaluation row");
+        const FieldConfig f = FieldConfig::make(modulus, limbs);
+        MultilinearZip::batch_verify_challenges(num_rows, row_len, codeword_len, n_cols, f, transcript->t, proofs, stream_len,
+                                                n_polys, coeffs_out, cols_out);
+    });
+}
+
 int32_t zinc_zip_evaluate(const zinc_zip_params *pp, const int64_t *evals, size_t n_evals, const uint64_t *point,
                           size_t point_len, const uint64_t *modulus, uint32_t limbs, uint64_t *out) {
     if (!pp || !evals || !out) return ZINC_ERR_NULL;

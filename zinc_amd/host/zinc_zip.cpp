@@ -993,6 +993,34 @@ static void point_to_tensor(const FieldConfig &field, uint32_t num_rows, const L
     if (lc) flat(build_eq_x_r(field, point, (uint32_t)lc), q1);
 }
 
+// what MultilinearZip::verify returns for a verdict of the device (zip_verify_verdict): Ok(()), the reference's errors,
+// a panic where it panics
+static void throw_unless_accepted(int32_t verdict) {
+    switch (verdict) {
+        case ZIP_VERIFY_ACCEPT: return;
+        case ZIP_VERIFY_PROXIMITY_TESTING:
+        case ZIP_VERIFY_PROXIMITY_Q0: throw ZipError(ZipError::InvalidPcsOpen, "Proximity failure");
+        case ZIP_VERIFY_EVAL_CONSISTENCY: throw ZipError(ZipError::InvalidPcsOpen, "Evaluation consistency failure");
+        case ZIP_VERIFY_MERKLE: throw ZipError(ZipError::InvalidPcsOpen, "Merkle proof verification failed");
+        case ZIP_VERIFY_OVERFLOW: throw std::logic_error("attempt to add with overflow (encode_wide of the combined row)");
+        default: throw ZipError(ZipError::Transcript, "Failed to read the proof stream");
+    }
+}
+
+// read_field_elements' absorption (pcs_transcript.rs:138-160): row_len big-endian elements, not range-checked
+static void absorb_row_be(const FieldConfig &field, PcsTranscript &transcript, const uint8_t *row_be, uint32_t row_len) {
+    for (uint32_t c = 0; c < row_len; c++) {
+        Limbs v{};
+        const uint8_t *b = row_be + (size_t)c * field.limbs * 8;
+        for (uint32_t i = 0; i < field.limbs; i++) {
+            uint64_t w = 0;
+            for (int k = 0; k < 8; k++) w = (w << 8) | b[8 * (field.limbs - 1 - i) + k];
+            v[i] = w;
+        }
+        transcript.fs_transcript.absorb_random_field(field, v);
+    }
+}
+
 void MultilinearZip::verify(const MultilinearZipParams &vp, const MultilinearZipCommitment &comm, const Limbs *point,
                             size_t point_len, const Limbs &eval, PcsTranscript &transcript, const FieldConfig &field) {
     validate_input("verify", vp.num_vars, vp.num_vars, &point_len);
@@ -1019,28 +1047,90 @@ void MultilinearZip::verify(const MultilinearZipParams &vp, const MultilinearZip
                      ZIP_MEM_HOST, avail, coeffs.empty() ? nullptr : coeffs.data(), cols.data(), (uint32_t)cols.size(),
                      q0.empty() ? nullptr : q0.data(), q1.empty() ? nullptr : q1.data(), eval.data(), &zf, &rep),
           "zip_verify");
-    switch (rep.verdict) {
-        case ZIP_VERIFY_ACCEPT: break;
-        case ZIP_VERIFY_PROXIMITY_TESTING:
-        case ZIP_VERIFY_PROXIMITY_Q0: throw ZipError(ZipError::InvalidPcsOpen, "Proximity failure");
-        case ZIP_VERIFY_EVAL_CONSISTENCY: throw ZipError(ZipError::InvalidPcsOpen, "Evaluation consistency failure");
-        case ZIP_VERIFY_MERKLE: throw ZipError(ZipError::InvalidPcsOpen, "Merkle proof verification failed");
-        case ZIP_VERIFY_OVERFLOW: throw std::logic_error("attempt to add with overflow (encode_wide of the combined row)");
-        default: throw ZipError(ZipError::Transcript, "Failed to read the proof stream");
-    }
+    throw_unless_accepted(rep.verdict);
     // read_field_elements absorbed every element of the evaluation row (pcs_transcript.rs:138-160)
-    const uint8_t *row_be = transcript.read_data() + transcript.read_pos + len - (size_t)row_len * field.limbs * 8;
-    for (uint32_t c = 0; c < row_len; c++) {
-        Limbs v{};
-        const uint8_t *b = row_be + (size_t)c * field.limbs * 8;
-        for (uint32_t i = 0; i < field.limbs; i++) {
-            uint64_t w = 0;
-            for (int k = 0; k < 8; k++) w = (w << 8) | b[8 * (field.limbs - 1 - i) + k];
-            v[i] = w;
-        }
-        transcript.fs_transcript.absorb_random_field(field, v);
-    }
+    absorb_row_be(field, transcript, transcript.read_data() + transcript.read_pos + len - (size_t)row_len * field.limbs * 8, row_len);
     transcript.read_pos += len;
+}
+
+// One polynomial of the verifier's Fiat-Shamir walk: the squeezes of verify_testing (verify_z.rs:69-90), then -- `absorb`
+// -- what read_field_elements absorbs, the evaluation row at the end of its stream.
+static void verify_walk_one(uint32_t num_rows, uint32_t row_len, uint32_t codeword_len, uint32_t n_cols, const FieldConfig &field,
+                            PcsTranscript &transcript, const uint8_t *stream, size_t stream_len, bool absorb, int64_t *coeffs_out,
+                            uint32_t *cols_out) {
+    if (num_rows > 1) {
+        const auto coeffs = transcript.fs_transcript.get_integer_challenges_i64(num_rows);
+        if (coeffs_out) std::memcpy(coeffs_out, coeffs.data(), (size_t)num_rows * 8);
+    }
+    for (uint32_t k = 0; k < n_cols; k++) {
+        const uint32_t c = (uint32_t)transcript.squeeze_challenge_idx(field, codeword_len);
+        if (cols_out) cols_out[k] = c;
+    }
+    if (absorb) absorb_row_be(field, transcript, stream + stream_len - (size_t)row_len * field.limbs * 8, row_len);
+}
+
+void MultilinearZip::batch_verify_challenges(uint32_t num_rows, uint32_t row_len, uint32_t codeword_len, uint32_t n_cols,
+                                             const FieldConfig &field, PcsTranscript &transcript, const uint8_t *proofs,
+                                             size_t stream_len, size_t n_polys, int64_t *coeffs_out, uint32_t *cols_out) {
+    for (size_t i = 0; i < n_polys; i++)
+        verify_walk_one(num_rows, row_len, codeword_len, n_cols, field, transcript, proofs + i * stream_len, stream_len, true,
+                        num_rows > 1 ? coeffs_out + i * num_rows : nullptr, cols_out + i * n_cols);
+}
+
+void MultilinearZip::batch_verify_z(const MultilinearZipParams &vp, const MultilinearZipCommitment *const *comms,
+                                    const Limbs *const *points, const size_t *point_lens, const Limbs *evals, size_t n_polys,
+                                    PcsTranscript &transcript, const FieldConfig &field) {
+    const uint32_t row_len = vp.linear_code.row_len, num_rows = vp.num_rows, cw = vp.linear_code.codeword_len();
+    const uint32_t n_cols = vp.linear_code.num_column_opening, fl = field.limbs;
+    bool batched = batch_path_enabled() && n_polys >= 2 && n_polys <= 65535 && cw <= 16384 &&
+                   vp.linear_code.num_proximity_testing == 1 && (uint64_t)n_polys * n_cols <= 0xFFFFFFFFull;
+    for (size_t i = 0; i < n_polys && batched; i++) batched = point_lens[i] == vp.num_vars && comms[i]->roots.size() == num_rows;
+    if (!batched) {  // (also where the loop's own checks produce the reference's errors)
+        for (size_t i = 0; i < n_polys; i++) verify(vp, *comms[i], points[i], point_lens[i], evals[i], transcript, field);
+        return;
+    }
+    zip_ctx *ctx = vp.ctx.get();
+    const size_t len = zip_proof_len(ctx, n_cols, fl);
+    const uint8_t *proofs = transcript.read_data() + transcript.read_pos;
+    // the polynomials whose streams are all there; the first one after them fails on a short stream, as in the loop
+    const size_t k = std::min(n_polys, (transcript.read_size() - transcript.read_pos) / len);
+    if (k) {
+        // 1. the shared transcript, in the reference's order: needs no verdict (zip_hip.h, zip_batch_verify)
+        const KeccakTranscript before = transcript.fs_transcript;
+        std::vector<int64_t> coeffs(num_rows > 1 ? k * (size_t)num_rows : 0);
+        std::vector<uint32_t> cols(k * (size_t)n_cols);
+        batch_verify_challenges(num_rows, row_len, cw, n_cols, field, transcript, proofs, len, k, coeffs.data(), cols.data());
+        // 2. point_to_tensor per polynomial (the points differ), roots and claimed evaluations polynomial-major
+        std::vector<uint64_t> q0, q1, one0, one1, ev(k * (size_t)fl);
+        std::vector<uint8_t> roots(k * (size_t)num_rows * 32);
+        for (size_t i = 0; i < k; i++) {
+            point_to_tensor(field, num_rows, points[i], point_lens[i], one0, one1);
+            q0.insert(q0.end(), one0.begin(), one0.end());
+            q1.insert(q1.end(), one1.begin(), one1.end());
+            std::memcpy(roots.data() + i * (size_t)num_rows * 32, comms[i]->roots.data(), (size_t)num_rows * 32);
+            for (uint32_t l = 0; l < fl; l++) ev[i * fl + l] = evals[i][l];
+        }
+        // 3. every proof in one launch set
+        const zip_field zf = field.to_abi();
+        std::vector<zip_verify_report> reps(k);
+        check(ctx,
+              zip_batch_verify(ctx, (uint32_t)k, roots.data(), proofs, ZIP_MEM_HOST, k * len, coeffs.empty() ? nullptr : coeffs.data(),
+                               cols.data(), n_cols, q0.empty() ? nullptr : q0.data(), q1.empty() ? nullptr : q1.data(), ev.data(), &zf,
+                               reps.data()),
+              "zip_batch_verify");
+        for (size_t i = 0; i < k; i++) {
+            if (reps[i].verdict == ZIP_VERIFY_ACCEPT) continue;
+            // the reference stops here: leave what the loop leaves -- polynomials 0 .. i-1 walked in full, the squeezes of
+            // polynomial i, the cursor at the start of its stream -- and throw what verify throws
+            transcript.fs_transcript = before;
+            batch_verify_challenges(num_rows, row_len, cw, n_cols, field, transcript, proofs, len, i, coeffs.data(), cols.data());
+            verify_walk_one(num_rows, row_len, cw, n_cols, field, transcript, proofs + i * len, len, false, nullptr, nullptr);
+            transcript.read_pos += i * len;
+            throw_unless_accepted(reps[i].verdict);
+        }
+        transcript.read_pos += k * len;
+    }
+    for (size_t i = k; i < n_polys; i++) verify(vp, *comms[i], points[i], point_lens[i], evals[i], transcript, field);
 }
 
 Limbs MultilinearZip::evaluate(const MultilinearZipParams &pp, const int64_t *evals, size_t n_evals, const Limbs *point,

@@ -283,6 +283,23 @@ struct MultilinearZip {
     // reference panics (encode_wide overflow).  Merkle paths are checked (zip_hip.h, zip_verify).
     static void verify(const MultilinearZipParams &vp, const MultilinearZipCommitment &comm, const Limbs *point,
                        size_t point_len, const Limbs &eval, PcsTranscript &transcript, const FieldConfig &field);
+    // verify_z.rs:40-58: verify per polynomial on ONE transcript.  With at least two polynomials, codewords up to 16384,
+    // one proximity test, every point of num_vars coordinates and every commitment of num_rows roots (and ZIP_HIP_BATCH
+    // not 0) the whole loop is the host walk of batch_verify_challenges over the streams that are all there and ONE
+    // zip_batch_verify call; otherwise the loop over verify, which raises the reference's own errors.  Either way the
+    // transcript, the cursor and the exception are what the loop leaves: after a rejected polynomial i, polynomials
+    // 0 .. i-1 absorbed, the squeezes of polynomial i drawn, read_pos at the start of stream i.
+    static void batch_verify_z(const MultilinearZipParams &vp, const MultilinearZipCommitment *const *comms,
+                               const Limbs *const *points, const size_t *point_lens, const Limbs *evals, size_t n_polys,
+                               PcsTranscript &transcript, const FieldConfig &field);
+    // The Fiat-Shamir walk of batch_verify_z over n_polys whole streams of stream_len bytes at `proofs`: in `verify` only
+    // read_field_elements absorbs (pcs_transcript.rs:91-103), and what it absorbs are the last row_len * 8 * limbs bytes
+    // of the stream itself.  Per polynomial: get_integer_challenges(num_rows) if num_rows > 1, n_cols times
+    // squeeze_challenge_idx(codeword_len), then the absorption of the evaluation row read from the stream.  read_pos is
+    // not touched.  coeffs_out: [n_polys][num_rows] (untouched when num_rows == 1); cols_out: [n_polys][n_cols].  Host only.
+    static void batch_verify_challenges(uint32_t num_rows, uint32_t row_len, uint32_t codeword_len, uint32_t n_cols,
+                                        const FieldConfig &field, PcsTranscript &transcript, const uint8_t *proofs,
+                                        size_t stream_len, size_t n_polys, int64_t *coeffs_out, uint32_t *cols_out);
     // z_mle.map_to_field(config).evaluate(r_y, config) (zinc/prover.rs:317-319; poly_f/mle/dense.rs:35-41):
     // nullopt-like failure (wrong point length) throws ZipError{InvalidPcsParam}.
     static Limbs evaluate(const MultilinearZipParams &pp, const int64_t *evals, size_t n_evals, const Limbs *point,

@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = (
     "zinc_prover_prove", "zinc_prover_prepare", "zinc_prepared_ccs_free", "zinc_verifier_verify",
     "zinc_sumcheck_prove_products", "zinc_sumcheck_verify",
     "zinc_zip_batch_commit", "zinc_zip_batch_open", "zinc_zip_batch_open_challenges",
+    "zinc_zip_batch_verify", "zinc_zip_batch_verify_challenges",
 )
 
 
@@ -101,6 +102,9 @@ def lib():
         L.zinc_zip_batch_open.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_uint32, vp]
         L.zinc_zip_batch_open_challenges.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp,
                                                      C.c_size_t, vp, vp]
+        L.zinc_zip_batch_verify.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_uint32, vp]
+        L.zinc_zip_batch_verify_challenges.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp,
+                                                       C.c_size_t, C.c_size_t, vp, vp]
         L.zinc_pcs_transcript_from_proof.argtypes = [vp, C.c_size_t]
         L.zinc_pcs_transcript_from_proof.restype = vp
         L.zinc_pcs_transcript_position.argtypes = [vp]
@@ -436,9 +440,20 @@ class MultilinearZip:
 
     @staticmethod
     def batch_verify_z(vp: MultilinearZipParams, comms, points, evals, transcript: "PcsTranscript", field: "FieldConfig"):
-        """verify_z.rs:40-58"""
-        for c, pt, ev in zip(comms, points, evals):
-            MultilinearZip.verify(vp, c, pt, ev, field, transcript)
+        """verify_z.rs:40-58 (zinc_zip_batch_verify): one host walk of the shared transcript and one device call for all
+        polynomials where the batch serves them, the loop over verify otherwise.  Returns None when every proof is accepted;
+        raises what verify raises for the first rejected polynomial and leaves the transcript where the loop leaves it."""
+        m = min(len(comms), len(points), len(evals))
+        if not m:
+            return
+        roots = np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.uint8).reshape(-1) for c in comms[:m]]))
+        pts = [np.ascontiguousarray(pt, dtype=np.uint64).reshape(-1, field.limbs) if np.size(pt) else np.zeros((0, field.limbs), np.uint64)
+               for pt in points[:m]]
+        ptrs = (C.c_void_p * m)(*[pt.ctypes.data for pt in pts])
+        lens = (C.c_size_t * m)(*[pt.shape[0] for pt in pts])
+        ev = np.ascontiguousarray(np.stack([np.asarray(e, dtype=np.uint64).reshape(-1)[:field.limbs] for e in evals[:m]]))
+        _check(lib().zinc_zip_batch_verify(vp._h, roots.ctypes.data, ptrs, lens, ev.ctypes.data, m, field._m.ctypes.data,
+                                           field.limbs, transcript._h))
 
     @staticmethod
     def open(pp: MultilinearZipParams, evaluations, commit_data: MultilinearZipData, point: np.ndarray,
