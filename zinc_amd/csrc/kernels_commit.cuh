@@ -58,7 +58,10 @@ struct CommitArgs {
     // 32-byte reads of lines 512 KB apart were 55.7 M requests per launch at 2^24, profiles/round3_gather_pmc.md).
     uint8_t *pk;                // [ceil(num_rows / 4)][4 * pk_stride]
     uint32_t pk_stride, pk_off0, pk_off1, pk_off2;  // bytes: row stride, start of the three node sections (of ONE row)
-    const uint32_t *pk_tab;     // [waves][16] words: per wave the 32 16-bit section ranks its lanes' stores start at
+    // base ranks, row invariant.  raa_commit_kernel (OwnLeaves8): [threads][2] words, per lane the 16-bit ranks its
+    // members of the four sections start at (values | N0 << 16, N1 | N2 << 16).  raa_commit16_kernel (StridedLeaves):
+    // [waves][2][16] words, per wave and output phase the 32 16-bit section ranks its lanes' stores start at
+    const uint32_t *pk_tab;
     uint32_t *chunk_done;       // [chunks] arrival counters, or null
     // A commit of ONE round with several workgroups per CU (2^20: four of 256 threads): 1 = as always; k > 1 = k classes
     // of workgroups (commit_class) at DIFFERENT wave priorities, so that the workgroups sharing a CU finish one after the
@@ -216,7 +219,8 @@ __device__ __forceinline__ void subtree_hash(Src &src, uint32_t (&h)[8]) {
 // with the node of step E0 + (t mod 2^l).  Every lane still hashes E leaves, E/2 ... 1 nodes.
 // MODE 0: every entry and node is stored.  MODE 1 (zip_commit_hinted): stores no opening of the hinted columns reads
 // are predicated off, at the natural places (ZIP_HIP_PACKED=0, and what hinted commits below codeword 512 ... do not
-// have: they store everything).  MODE 3 (hinted commits): as 1, but what the openings read of the entries and of
+// have: they store everything).  MODE 3 (hinted commits; here only the 16-entry kernel's -- the packed 8-entry commit
+// does not transpose at all, OwnLeaves8 below): as 1, but what the openings read of the entries and of
 // levels 0..2 goes to the packed per-row block (CommitArgs.pk).  A lane's place in a
 // section is the rank of its entry / node among the section's members: the members owned by the lanes of one wave at
 // one store site are consecutive in index order (per parity class for level 1, per tid mod 4 for level 2), so the
@@ -363,6 +367,92 @@ __device__ __forceinline__ uint32_t store_mask(const uint32_t *need, uint32_t cw
         m |= ((n2[i >> 5] >> (i & 31)) & 1u) << (24 + g);
     }
     return m;
+}
+
+// Natural ownership for the output phase of the packed 8-entry commit (raa_commit_kernel<8, true, kStorePacked>):
+// lane t keeps the entries 8t .. 8t+7 it owns after pass 2 -- one aligned 8-leaf subtree, hashed in registers by
+// subtree_hash<3, 0> with no exchange between lanes: level-1 nodes 4t + i, level-2 nodes 2t + i, level-3 node t.
+// Strided ownership buys contiguous stores, and a packed commit has none to make contiguous: ~88 % of the stores of the
+// entries and of levels 0..2 are predicated off and the rest go to rank-ordered sections, while the level-3 store is one
+// node per lane in lane order either way.  In index order all of lane t's members of a section precede lane t+1's, so a
+// store's place is the lane's row-invariant base rank in that section (rk01 / rk23, CommitArgs.pk_tab: 16 bits each for
+// values, N0 | N1, N2) + the number of the lane's own smask bits of that section below the current one: no ballot.
+// The entries wait in the lane's own slots of the t2 planes (lz_lo / lz_hi [e * lz_stride]) and are read when their turn
+// comes, as StridedLeaves LAZY does.
+struct OwnLeaves8 {
+    const uint64_t *lz_lo;
+    const uint32_t *lz_hi;
+    uint32_t lz_stride;
+    uint32_t *node3;  // the lane's level-3 node slot in the (row-interleaved) tree
+    uint8_t *pk_v, *pk_n;  // this row's lane of its group's packed block (StridedLeaves::set_packed)
+    uint32_t pk_off0, pk_off1, pk_off2;
+    uint32_t rk01, rk23;
+    // bit e = entry 8t + e, bit 8 + e = its leaf hash, bit 16 + i = level-1 node 4t + i, bit 24 + i = level-2 node 2t + i
+    uint32_t smask;
+    __device__ __forceinline__ void set_packed(const CommitArgs &a, uint32_t row) {
+        uint8_t *g = a.pk + (size_t)(row >> 2) * 4 * a.pk_stride;
+        pk_v = g + (row & 3u) * 16u;
+        pk_n = g + (row & 3u) * 32u;
+        pk_off0 = 4u * a.pk_off0;
+        pk_off1 = 4u * a.pk_off1;
+        pk_off2 = 4u * a.pk_off2;
+    }
+    // place of the member at smask bit B: base rank + the lane's members of the same section (bits from S up) below it
+    template <int B, int S>
+    __device__ __forceinline__ uint32_t place(uint32_t base) const {
+        return base + (uint32_t)__builtin_popcount(smask & (((1u << B) - 1u) & ~((1u << S) - 1u)));
+    }
+    template <int E0>
+    __device__ __forceinline__ void leaf(uint32_t (&h)[8]) {
+        const uint64_t lo = lz_lo[E0 * lz_stride];
+        const uint32_t d0 = (uint32_t)lo, d1 = (uint32_t)(lo >> 32), d2 = lz_hi[E0 * lz_stride];
+        if (smask & (1u << E0)) {
+            const uint32_t pos = place<E0, 0>(rk01 & 0xFFFFu);
+            *reinterpret_cast<uint4 *>(pk_v + (size_t)pos * 64) = make_uint4(d0, d1, d2, (uint32_t)((int32_t)d2 >> 31));
+        }
+        blake3_leaf_sext96(d0, d1, d2, h);
+        if (smask & (0x100u << E0)) {
+            const uint32_t pos = place<8 + E0, 8>(rk01 >> 16);
+            store_hash(reinterpret_cast<uint32_t *>(pk_n + pk_off0) + (size_t)pos * 32, h);
+        }
+    }
+    template <int LVL, int I>
+    __device__ __forceinline__ void node(const uint32_t (&h)[8]) {
+        if constexpr (LVL == 1) {
+            if (smask & (0x10000u << I)) {
+                const uint32_t pos = place<16 + I, 16>(rk23 & 0xFFFFu);
+                store_hash(reinterpret_cast<uint32_t *>(pk_n + pk_off1) + (size_t)pos * 32, h);
+            }
+        } else if constexpr (LVL == 2) {
+            if (smask & (0x1000000u << I)) {
+                const uint32_t pos = place<24 + I, 24>(rk23 >> 16);
+                store_hash(reinterpret_cast<uint32_t *>(pk_n + pk_off2) + (size_t)pos * 32, h);
+            }
+        } else {
+            store_hash(node3, h);
+        }
+    }
+    // (subtree_hash hands level and index over as arguments: both are constants once it is inlined)
+    __device__ __forceinline__ void store(int lvl, uint32_t idx, const uint32_t (&h)[8]) {
+        if (lvl == 1) {
+            if (idx == 0) node<1, 0>(h);
+            else if (idx == 1) node<1, 1>(h);
+            else if (idx == 2) node<1, 2>(h);
+            else node<1, 3>(h);
+        } else if (lvl == 2) {
+            if (idx == 0) node<2, 0>(h);
+            else node<2, 1>(h);
+        } else {
+            node<3, 0>(h);
+        }
+    }
+};
+
+// OwnLeaves8::smask from the hint bitmaps: the lane's members are aligned runs of 8 / 8 / 4 / 2 bits of V / N0 / N1 / N2
+__device__ __forceinline__ uint32_t store_mask_own8(const uint32_t *need, uint32_t cw, uint32_t tid) {
+    const uint32_t *nv = need, *n0 = nv + (cw + 31) / 32, *n1 = n0 + (cw + 31) / 32, *n2 = n1 + (cw / 2 + 31) / 32;
+    return ((nv[tid >> 2] >> ((tid & 3u) * 8u)) & 0xFFu) | (((n0[tid >> 2] >> ((tid & 3u) * 8u)) & 0xFFu) << 8) |
+           (((n1[tid >> 3] >> ((tid & 7u) * 4u)) & 0xFu) << 16) | (((n2[tid >> 4] >> ((tid & 15u) * 2u)) & 3u) << 24);
 }
 
 template <int E, int E0, class Src>
@@ -720,9 +810,12 @@ __device__ __forceinline__ uint32_t opaque_zero(uint32_t dep) {
 template <int E, bool HASH, int MODE = kStoreAll>
 __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
     constexpr bool MASKED = MODE != kStoreAll;
+    // packed commits keep natural ownership in the output phase (OwnLeaves8): three barriers per row, no transposition
+    constexpr bool OWN = MODE == kStorePacked;
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int LOGE = (E == 1) ? 0 : (E == 2) ? 1 : (E == 4) ? 2 : 3;
     static_assert((1 << LOGE) == E && E <= 8, "E must be 1, 2, 4 or 8");
+    static_assert(!OWN || (E == 8 && HASH), "packed commits of this kernel: 8 entries per thread, hashed");
 
     const uint32_t tid0 = threadIdx.x, T = blockDim.x;
     constexpr uint32_t PAD = 32 / E;
@@ -759,13 +852,15 @@ __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
     };
     load_pidx(tid0);
     // ... the lane's store mask under an opening hint ...
-    const uint32_t smask = (MASKED && active) ? store_mask<E>(a.need, cw, 0u, a.nact, tid0) : 0xFFFFFFFFu;
-    // ... and (packed openings) the wave's base ranks, wave-uniform
-    uint32_t ptab[16] = {};
-    if (MODE == kStorePacked) {
-        const uint32_t *wt = a.pk_tab + (size_t)__builtin_amdgcn_readfirstlane(tid0 >> 6) * 16;
-#pragma unroll
-        for (int k = 0; k < 16; k++) ptab[k] = __builtin_amdgcn_readfirstlane(wt[k]);
+    const uint32_t smask = !(MASKED && active) ? 0xFFFFFFFFu
+                           : OWN               ? store_mask_own8(a.need, cw, tid0)
+                                               : store_mask<E>(a.need, cw, 0u, a.nact, tid0);
+    // ... and (packed openings) the lane's four base ranks, two registers (CommitArgs.pk_tab)
+    uint32_t rk01 = 0, rk23 = 0;
+    if (OWN && active) {
+        const uint2 rk = reinterpret_cast<const uint2 *>(a.pk_tab)[tid0];
+        rk01 = rk.x;
+        rk23 = rk.y;
     }
     // ... and the NEXT witness row, fetched during the scan passes of the current one (rep = 2
     // geometry: row_len == NPF * blockDim; anything else takes the direct path).
@@ -854,6 +949,29 @@ __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
 #pragma unroll
             for (int e = 1; e < E; e++) v[e] += v[e - 1];
         }
+        // Under the row's LAST barrier (so that NO barrier follows the hash phase -- the waves of a SIMD finish hashing one
+        // after the other, and the early ones go straight on into the next row's pass 1):
+        //   the prefetched row is staged: rowbuf was last read in pass 1, in front of the first scan's barrier;
+        //   the stores of a chunk end that is still owed (its head, one row ago) are drained (fin.top_of_row()): they must
+        //   be in L2 before the oldest waves read them back after THIS row's hash phase.  Here, a scan pass and more after
+        //   they were issued, the wait is for nothing -- at the top of the row (round 3) the last wave to arrive stood in
+        //   it on the critical path.
+        // The last barrier is the transposition's for strided ownership, and the one inside the second scan for natural
+        // ownership (OWN), which has three barriers per row:
+        //   scan 1's    rowbuf reads of pass 1 | the staging below; wave_tot half 0
+        //   the middle  t2 writes of pass 1 | the gather of pass 2
+        //   scan 2's    the gather of pass 2 | the lanes' parking of their final values in t2; the staging | the next row's
+        //               pass 1; the drain of owed stores | after_hash; wave_tot half 1
+        // and none for the parked values: a lane reads back its own slots, and only the lane itself writes them again
+        // (pass 1 of the next row) before the next middle barrier.
+        auto under_last_barrier = [&]() {
+            if (prefetch && has_next) {
+#pragma unroll
+                for (int k = 0; k < NPF; k++) rowbuf[k * T + tid] = nxt[k];
+            }
+            fin.top_of_row();
+        };
+        if (OWN) under_last_barrier();
         {
             // the barriers inside also order the t2 reads above before the stores below
             const i128 pre = block_exclusive_scan_i96(v[E - 1], wave_tot, 1);
@@ -861,7 +979,7 @@ __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
             for (int e = 0; e < E; e++) v[e] += pre;
         }
 
-        // ---- transpose to strided ownership through LDS, then rows + hashes ------
+        // ---- the final values go back to LDS: read lazily by the hash phase, by whoever owns them there ------
         if (active) {
 #pragma unroll
             for (int e = 0; e < E; e++) {
@@ -870,33 +988,38 @@ __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
                 t2hi[slot] = (uint32_t)((u128)v[e] >> 64);
             }
         }
-        if (prefetch && has_next) {
-            // rowbuf was last read in pass 1 (two barriers ago): stage the prefetched row now, under the
-            // barrier below, so that NO barrier follows the hash phase -- the waves of a SIMD finish
-            // hashing one after the other, and the early ones go straight on into the next row's pass 1
-#pragma unroll
-            for (int k = 0; k < NPF; k++) rowbuf[k * T + tid] = nxt[k];
+        if (OWN) {
+            asm volatile("" ::: "memory");  // (the values are re-read from LDS when their turn comes, not kept in 24 registers)
+        } else {
+            // transpose to strided ownership through LDS
+            under_last_barrier();
+            lds_barrier();
         }
-        // the stores of a chunk end that is still owed (its head, one row ago) must be in L2 before the oldest waves read
-        // them back after THIS row's hash phase: drained here, two scan passes after they were issued, the wait is for
-        // nothing -- at the top of the row (round 3) the last wave to arrive stood in it on the critical path
-        fin.top_of_row();
-        lds_barrier();
         ZIPK_PH(ph_a);
-        if (active) {
+        if constexpr (OWN) {
+            if (active) {
+                OwnLeaves8 src;
+                src.lz_lo = t2lo + tid;
+                src.lz_hi = t2hi + tid;
+                src.lz_stride = PS;
+                src.node3 = tree_of<true>(a.layers, cw, row) + ((size_t)level_off(cw, 3) + tid) * kNodeWords<true>;
+                src.set_packed(a, row);
+                // (^ opaque 0: hoisted out of the row loop, the 22 places of the lane's stores are 22 registers more)
+                src.rk01 = rk01 ^ z;
+                src.rk23 = rk23 ^ z;
+                src.smask = smask ^ z;
+                uint32_t top[8];
+                subtree_hash<3, 0>(src, top);
+            }
+        } else if (active) {
             StridedLeaves<E, MODE, true> src;
             src.out_row = out_row;
             src.compact = a.compact_rows;
-            src.tree = HASH ? tree_of<MODE == kStorePacked>(a.layers, cw, row) : nullptr;
+            src.tree = HASH ? tree_of<false>(a.layers, cw, row) : nullptr;
             src.cw = cw;
             src.T = a.nact;
             src.tid = tid;
             src.smask = smask;
-            if (MODE == kStorePacked) {
-                src.set_packed(a, row);
-#pragma unroll
-                for (int k = 0; k < 16; k++) src.ptab[k] = ptab[k];
-            }
             {
                 // entry j = e * nact + tid sits at slot (j % E) * PS + j / E; nact is a multiple of E (or E = 1), so the
                 // slot of step e is the slot of step 0 + e * nact / E: read when its turn comes (StridedLeaves LAZY)

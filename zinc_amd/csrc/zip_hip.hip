@@ -76,10 +76,12 @@ struct HintPlan {
     std::vector<uint32_t> bm;
     bool packed = false;
     PackedLayout L;
-    std::vector<uint32_t> wave_tab;  // [waves][phases][16] words = 32 16-bit bases each
+    // CommitArgs.pk_tab: e = 16: [waves][phases][16] words = 32 16-bit bases each; e = 8: [threads][2] words = the
+    // lane's four 16-bit base ranks (values | N0 << 16, N1 | N2 << 16)
+    std::vector<uint32_t> rank_tab;
     std::vector<uint16_t> pos[4];    // 0xFFFF: not a member
     std::vector<uint16_t> own_ranks; // pk_rank of cols[] themselves, [n][4] (OpenColsArgs.pk_rank)
-    // device copy, made once: bm at 0 (CommitArgs.need), wave_tab at kHintTables, own_ranks at kPackedRanksAt
+    // device copy, made once: bm at 0 (CommitArgs.need), rank_tab at kHintTables, own_ranks at kPackedRanksAt
     unsigned char *dev = nullptr;
     std::function<void(unsigned char *)> release;  // gives `dev` back to its ctx's block pool (hipFree would stall the device)
     HintPlan() = default;
@@ -919,56 +921,29 @@ uint32_t commit_wgs_per_cu(const CommitGeom &g) {
 bool commit_supports_hint(uint32_t cw) { return cw >= 512 && cw <= 16384; }
 // one pinned / device block per hinted commit: the bitmaps (<= 5.6 KB for cw <= 16384) at offset 0, the
 // column -> openings tables of zip_commit_open (first[cw] | next[n_cols], u16) at kHintTables
-// (packed openings: the wave table at kHintTables, the ranks of the hinted openings at kPackedRanksAt)
+// (packed openings: the rank table at kHintTables -- up to 8 bytes for each of 1024 threads --, the ranks of the hinted
+// openings at kPackedRanksAt)
 constexpr uint32_t kRingSlots = 64, kRingChunks = 16, kRingStride = 16;  // zip_ctx::ring_d
-constexpr size_t kHintTables = 8192, kHintBytes = kHintTables + 8 * (8192 / 32) + 4 * 4096 + 64, kPackedRanksAt = kHintTables + 2048;
+constexpr size_t kHintTables = 8192, kPackedRanksAt = kHintTables + 8192, kHintBytes = kPackedRanksAt + 8 * (8192 / 32) + 4 * 4096 + 64;
 // ---- opening hints and packed openings (CommitArgs.need / .pk) -------------------------------------------------
 // Everything a hinted commit derives from its column list, kept per ctx until the list changes (in the prover flow it
 // never does: a fresh PcsTranscript squeezes the same columns for every proof, zinc/prover.rs:316).
 //   bm         the four bitmaps V | N0 (cw bits each) | N1 (cw / 2) | N2 (cw / 4): entries opened, level-0..2 nodes
 //              that are some opening's sibling
 //   packed     the commit kernel of this geometry can store those members densely (CommitArgs.pk); then
-//   pos[s][i]  = the place of member i in section s of a row's packed block, and wave_tab = CommitArgs.pk_tab.
+//   pos[s][i]  = the place of member i in section s of a row's packed block, and rank_tab = CommitArgs.pk_tab.
 // The place of a member is its turn in the enumeration  wave -> output phase -> store site -> lane class -> lane
 // of the kernel's lanes (StridedLeaves: entry of step e = e * sT + stid(lane); level-1 node of group g at lane
 // parity p = ((2g + p) sT + stid) >> 1; level-2 node of group g at lane mod 4 = c = ((4g + c) sT + stid) >> 2): the
-// kernel recovers it as a per-wave base (wave_tab) + the number of storing lanes of the class below it.  For the
-// 8-entries-per-thread kernel that enumeration is plain index order.
+// kernel recovers it as a per-wave base (rank_tab) + the number of storing lanes of the class below it.
+// The 8-entries-per-thread kernel keeps natural ownership (OwnLeaves8: lane t owns entries 8t.., level-1 nodes 4t..,
+// level-2 nodes 2t..): its enumeration is plain index order, and rank_tab holds per LANE the number of members of each
+// section below the lane's first -- the kernel adds the lane's own members below the one it stores.
 static bool packed_enabled() {
     return env_long("ZIP_HIP_PACKED", 1, 0, 1) != 0;  // (read per call: the tests flip it)
 }
-static void plan_packed(HintPlan &P) {
-    const uint32_t cw = P.cw, wv = (cw + 31) / 32, w1 = (cw / 2 + 31) / 32;
-    const uint32_t *sec[4] = {P.bm.data(), P.bm.data() + wv, P.bm.data() + 2 * wv, P.bm.data() + 2 * wv + w1};
-    const uint32_t bits[4] = {cw, cw, cw / 2, cw / 4};
-    const uint32_t waves = P.threads / 64, phases = P.e == 16 ? 2 : 1, sT = P.e == 16 ? 16 : P.threads;
-    for (int k = 0; k < 4; k++) P.pos[k].assign(bits[k], 0xFFFF);
-    P.wave_tab.assign((size_t)waves * phases * 16, 0);
-    uint32_t cnt[4] = {0, 0, 0, 0};
-    auto member = [&](int k, uint32_t i) { return (sec[k][i >> 5] >> (i & 31u)) & 1u; };
-    for (uint32_t w = 0; w < waves; w++)
-        for (uint32_t q = 0; q < phases; q++) {
-            uint16_t base[32];
-            auto stid = [&](uint32_t l) {
-                const uint32_t tid = 64 * w + l;
-                return P.e == 16 ? (tid & ~7u) * 16u + q * 8u + (tid & 7u) : tid;
-            };
-            auto site = [&](int k, int slot, uint32_t step, uint32_t shift, uint32_t cls, uint32_t ncls) {
-                base[slot] = (uint16_t)cnt[k];
-                for (uint32_t l = cls; l < 64; l += ncls) {
-                    const uint32_t i = (step * sT + stid(l)) >> shift;
-                    if (member(k, i)) P.pos[k][i] = (uint16_t)cnt[k]++;
-                }
-            };
-            for (uint32_t e = 0; e < 8; e++) site(0, (int)e, e, 0, 0, 1);
-            for (uint32_t e = 0; e < 8; e++) site(1, (int)(8 + e), e, 0, 0, 1);
-            for (uint32_t g = 0; g < 4; g++)
-                for (uint32_t par = 0; par < 2; par++) site(2, (int)(16 + 2 * g + par), 2 * g + par, 1, par, 2);
-            for (uint32_t g = 0; g < 2; g++)
-                for (uint32_t c4 = 0; c4 < 4; c4++) site(3, (int)(24 + 4 * g + c4), 4 * g + c4, 2, c4, 4);
-            uint32_t *tab = P.wave_tab.data() + ((size_t)w * phases + q) * 16;
-            for (uint32_t k = 0; k < 16; k++) tab[k] = (uint32_t)base[2 * k] | ((uint32_t)base[2 * k + 1] << 16);
-        }
+// the four sections of a row's packed block, each a whole number of 128-byte lines, from their member counts
+static void packed_layout(HintPlan &P, const uint32_t (&cnt)[4]) {
     uint32_t at = (cnt[0] * 16u + 127u) & ~127u;
     P.L.off[0] = at;
     at = (at + cnt[1] * 32u + 127u) & ~127u;
@@ -977,6 +952,71 @@ static void plan_packed(HintPlan &P) {
     P.L.off[2] = at;
     at = (at + cnt[3] * 32u + 127u) & ~127u;
     P.L.stride = at;
+}
+struct HintSections {  // the four bitmaps of a plan and their sizes in bits
+    const uint32_t *sec[4];
+    uint32_t bits[4];
+    explicit HintSections(const HintPlan &P) {
+        const uint32_t cw = P.cw, wv = (cw + 31) / 32, w1 = (cw / 2 + 31) / 32;
+        const uint32_t *b = P.bm.data();
+        sec[0] = b, sec[1] = b + wv, sec[2] = b + 2 * wv, sec[3] = b + 2 * wv + w1;
+        bits[0] = cw, bits[1] = cw, bits[2] = cw / 2, bits[3] = cw / 4;
+    }
+    uint32_t member(int k, uint32_t i) const { return (sec[k][i >> 5] >> (i & 31u)) & 1u; }
+};
+// raa_commit_kernel<8, ..., kStorePacked> (natural ownership): index order; rank_tab = [threads][2] per-lane bases
+static void plan_packed_own8(HintPlan &P) {
+    const HintSections S(P);
+    for (int k = 0; k < 4; k++) P.pos[k].assign(S.bits[k], 0xFFFF);
+    uint32_t cnt[4] = {0, 0, 0, 0};
+    P.rank_tab.assign((size_t)P.threads * 2, 0);
+    for (uint32_t t = 0; t < P.threads; t++) {
+        P.rank_tab[2 * t] = cnt[0] | (cnt[1] << 16);
+        P.rank_tab[2 * t + 1] = cnt[2] | (cnt[3] << 16);
+        for (int k = 0; k < 4; k++) {
+            const uint32_t per = S.bits[k] / P.threads;  // 8, 8, 4, 2 members of lane t at most
+            for (uint32_t i = t * per; i < (t + 1) * per; i++)
+                if (S.member(k, i)) P.pos[k][i] = (uint16_t)cnt[k]++;
+        }
+    }
+    packed_layout(P, cnt);
+}
+// raa_commit16_kernel<..., kStorePacked> (strided ownership inside 8-lane groups, two output phases): the enumeration
+// above; rank_tab = [waves][2][16] words of per-wave bases
+static void plan_packed_strided16(HintPlan &P) {
+    const HintSections S(P);
+    const uint32_t waves = P.threads / 64, phases = 2, sT = 16;
+    for (int k = 0; k < 4; k++) P.pos[k].assign(S.bits[k], 0xFFFF);
+    P.rank_tab.assign((size_t)waves * phases * 16, 0);
+    uint32_t cnt[4] = {0, 0, 0, 0};
+    for (uint32_t w = 0; w < waves; w++)
+        for (uint32_t q = 0; q < phases; q++) {
+            uint16_t base[32];
+            auto stid = [&](uint32_t l) {
+                const uint32_t tid = 64 * w + l;
+                return (tid & ~7u) * 16u + q * 8u + (tid & 7u);
+            };
+            auto site = [&](int k, int slot, uint32_t step, uint32_t shift, uint32_t cls, uint32_t ncls) {
+                base[slot] = (uint16_t)cnt[k];
+                for (uint32_t l = cls; l < 64; l += ncls) {
+                    const uint32_t i = (step * sT + stid(l)) >> shift;
+                    if (S.member(k, i)) P.pos[k][i] = (uint16_t)cnt[k]++;
+                }
+            };
+            for (uint32_t e = 0; e < 8; e++) site(0, (int)e, e, 0, 0, 1);
+            for (uint32_t e = 0; e < 8; e++) site(1, (int)(8 + e), e, 0, 0, 1);
+            for (uint32_t g = 0; g < 4; g++)
+                for (uint32_t par = 0; par < 2; par++) site(2, (int)(16 + 2 * g + par), 2 * g + par, 1, par, 2);
+            for (uint32_t g = 0; g < 2; g++)
+                for (uint32_t c4 = 0; c4 < 4; c4++) site(3, (int)(24 + 4 * g + c4), 4 * g + c4, 2, c4, 4);
+            uint32_t *tab = P.rank_tab.data() + ((size_t)w * phases + q) * 16;
+            for (uint32_t k = 0; k < 16; k++) tab[k] = (uint32_t)base[2 * k] | ((uint32_t)base[2 * k + 1] << 16);
+        }
+    packed_layout(P, cnt);
+}
+static void plan_packed(HintPlan &P) {
+    if (P.e == 8) plan_packed_own8(P);
+    else plan_packed_strided16(P);
 }
 // zip_commit_open stores the low part of the openings packed where the commit kernel has the variant (whole waves of
 // 8 or 16 entries per thread, depth >= 3); the packed rows take the place of the 16-byte row entries (commit_impl sizes
@@ -1011,7 +1051,7 @@ static std::shared_ptr<HintPlan> get_hint_plan(zip_ctx *ctx, const uint32_t *col
         ctx->depth >= 3) {
         plan_packed(*P);
         P->own_ranks.resize((size_t)n_cols * 4);
-        P->packed = P->L.stride > 0 && P->wave_tab.size() * 4 <= kPackedRanksAt - kHintTables &&
+        P->packed = P->L.stride > 0 && P->rank_tab.size() * 4 <= kPackedRanksAt - kHintTables &&
                     kPackedRanksAt + P->own_ranks.size() * 2 <= kHintBytes && P->ranks(cols, n_cols, P->own_ranks.data());
     }
     // the tables go to the device here, once, not with every commit
@@ -1019,7 +1059,7 @@ static std::shared_ptr<HintPlan> get_hint_plan(zip_ctx *ctx, const uint32_t *col
     memcpy(img.data(), P->bm.data(), P->bm.size() * 4);
     size_t used = P->bm.size() * 4;
     if (P->packed) {
-        memcpy(img.data() + kHintTables, P->wave_tab.data(), P->wave_tab.size() * 4);
+        memcpy(img.data() + kHintTables, P->rank_tab.data(), P->rank_tab.size() * 4);
         memcpy(img.data() + kPackedRanksAt, P->own_ranks.data(), P->own_ranks.size() * 2);
         used = kPackedRanksAt + P->own_ranks.size() * 2;
     }
@@ -2563,7 +2603,7 @@ static int32_t commit_impl(zip_ctx *ctx, const int64_t *evals, size_t n_evals, z
             size_t upload = words * 4;
             if (c->plan->packed) {
                 if (!resident) {
-                    memcpy(c->hint_h + kHintTables, c->plan->wave_tab.data(), c->plan->wave_tab.size() * 4);
+                    memcpy(c->hint_h + kHintTables, c->plan->rank_tab.data(), c->plan->rank_tab.size() * 4);
                     memcpy(c->hint_h + kPackedRanksAt, c->plan->own_ranks.data(), c->plan->own_ranks.size() * 2);
                 }
                 upload = kPackedRanksAt + c->plan->own_ranks.size() * 2;
@@ -2588,6 +2628,7 @@ static int32_t commit_impl(zip_ctx *ctx, const int64_t *evals, size_t n_evals, z
                 a.pk_off0 = c->pk_off[0];
                 a.pk_off1 = c->pk_off[1];
                 a.pk_off2 = c->pk_off[2];
+                // (HintPlan::rank_tab: per lane for the 8-entry kernel, per wave and output phase for the 16-entry one)
                 a.pk_tab = reinterpret_cast<const uint32_t *>(tables_d + kHintTables);
                 c->rank_d = reinterpret_cast<const uint16_t *>(tables_d + kPackedRanksAt);
             }
