@@ -269,27 +269,51 @@ class Model:
         n_mal = sum(len(f[2]) for f in facts)
         # encode_wide(u') with checked additions (verify_z.rs:75-77, int.rs:122-134)
         enc_u, lo, hi = raa_encode(i.z, i.u_prime(proof))
-        if lo < INT8_MIN or hi > INT8_MAX:
-            return Expect(OVERFLOW, 0, n_bad, n_mal, "overflow")
+        overflow = lo < INT8_MIN or hi > INT8_MAX
         # per opening: the proximity test over Z, then its Merkle records in stream order (verify_z.rs:88-127)
+        first, why = None, 0
         for k, (isum, _, mal, bad) in enumerate(facts):
-            if isum != enc_u[int(i.cols[k])]:
-                return Expect(PROXIMITY_TESTING, k, n_bad, n_mal, "reject")
-            if mal:
-                return Expect(MALFORMED, k, n_bad, n_mal, "transcript" if mal[min(mal)] > 64 else "reject")
-            if bad:
-                return Expect(MERKLE, k, n_bad, n_mal, "reject")
-        # verify_evaluation_z (verify_z.rs:129-163)
+            why = ((FAILS_PROXIMITY if isum != enc_u[int(i.cols[k])] else 0) | (FAILS_MALFORMED if mal else 0)
+                   | (FAILS_MERKLE if bad else 0))
+            if why:
+                first = k
+                break
+        # verify_evaluation_z (verify_z.rs:129-163); elements >= q: the device's deliberate deviation
         wire = i.row_elems(proof)
-        if i.dot_q1(wire) != ev:
-            return Expect(EVAL_CONSISTENCY, 0, n_bad, n_mal, "reject")
-        if any(x >= q for x in wire):  # the device's deliberate deviation, after the consistency check
-            return Expect(MALFORMED, 0, n_bad, n_mal, "noncanonical")
+        eval_differs = i.dot_q1(wire) != ev
+        noncanonical = any(x >= q for x in wire)
         enc_f = raa_encode(i.z, [i.std(x) for x in wire])[0]
-        for k, (_, fsum, _, _) in enumerate(facts):  # verify_proximity_q_0 (verify_z.rs:165-188)
-            if fsum != enc_f[int(i.cols[k])] % q:
-                return Expect(PROXIMITY_Q0, k, n_bad, n_mal, "reject")
-        return Expect(ACCEPT, 0, n_bad, n_mal, "accept")
+        first_q0 = next((k for k, (_, fsum, _, _) in enumerate(facts)  # verify_proximity_q_0 (verify_z.rs:165-188)
+                         if fsum != enc_f[int(i.cols[k])] % q), None)
+        verdict, column = verdict_order(overflow, first, why, eval_differs, noncanonical, first_q0)
+        oracle = {ACCEPT: "accept", OVERFLOW: "overflow"}.get(verdict, "reject")
+        if verdict == MALFORMED:
+            mal = facts[first][2] if first is not None else None
+            oracle = "noncanonical" if mal is None else "transcript" if mal[min(mal)] > 64 else "reject"
+        return Expect(verdict, column, n_bad, n_mal, oracle)
+
+
+# what an opening fails, as bits (zinc_amd/csrc/verify_verdict.h passes the same facts)
+FAILS_PROXIMITY, FAILS_MALFORMED, FAILS_MERKLE = 1, 2, 4
+
+
+def verdict_order(overflow, first, why, eval_differs, noncanonical, first_q0):
+    """(verdict, column) from the reduced facts, in the reference's order of checks (verify_z.rs:60-188): first = the first
+    opening that fails its proximity test over Z, a length prefix or a path (None: no opening does) and why = which of
+    those, as FAILS_* bits; first_q0 = the first opening that fails the proximity test over F_q."""
+    if overflow:
+        return OVERFLOW, 0
+    if first is not None:  # per opening: proximity, then its records in stream order
+        if why & FAILS_PROXIMITY:
+            return PROXIMITY_TESTING, first
+        return (MALFORMED if why & FAILS_MALFORMED else MERKLE), first
+    if eval_differs:
+        return EVAL_CONSISTENCY, 0
+    if noncanonical:  # after the consistency check
+        return MALFORMED, 0
+    if first_q0 is not None:
+        return PROXIMITY_Q0, first_q0
+    return ACCEPT, 0
 
 
 def expected_report(inst, proof, roots, ev):

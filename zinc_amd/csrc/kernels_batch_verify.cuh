@@ -17,22 +17,9 @@
 #include "blake3.cuh"
 #include "kernels_open.cuh"
 #include "kernels_verify.cuh"
+#include "verify_verdict.h"
 
 namespace zipk {
-
-// what the two encodings leave per polynomial for the report kernel
-struct BatchVerifyHead {
-    uint32_t overflow, noncanonical, pad[2];
-    uint64_t dot[4];  // <row, q1>, Montgomery
-};
-
-// zip_verify_report and zip_verify_verdict (include/zip_hip.h; the library asserts that they agree)
-struct BatchVerifyReport {
-    int32_t verdict;
-    uint32_t column, bad_merkle_paths, malformed_paths;
-};
-constexpr int32_t kVerdictAccept = 0, kVerdictProximityTesting = 1, kVerdictEvalConsistency = 2, kVerdictProximityQ0 = 3,
-                  kVerdictMerkle = 4, kVerdictMalformed = 5, kVerdictOverflow = 6;
 
 // ---------------------------------------------------------------------------------------
 // encode_row_kernel with the polynomial as blockIdx.x and the input row read where it lies in proof stream b:
@@ -50,7 +37,7 @@ struct BatchEncodeArgs {
     uint64_t *tmp, *out;     // [n_polys][cw][L]
     const uint64_t *q1;      // FIELD: [n_polys][row_len][L], or null (row_len == 1)
     uint32_t clear_overflow; // FIELD: no encode_wide runs (num_rows == 1); this kernel zeroes head[b].overflow
-    BatchVerifyHead *head;   // [n_polys]
+    VerifyHead *head;        // [n_polys]
 };
 
 template <int L, bool FIELD>
@@ -70,51 +57,9 @@ __global__ void __launch_bounds__(1024) batch_encode_kernel(BatchEncodeArgs a, F
     El *tot = reinterpret_cast<El *>(benc_smem);  // [blockDim.x]
     const uint32_t T = blockDim.x, tid = threadIdx.x, b = blockIdx.x, cw = a.cw;
     const uint64_t *in = reinterpret_cast<const uint64_t *>(a.proofs + (size_t)b * a.stream_bytes + a.in_at);
-    uint64_t *tmp = a.tmp + (size_t)b * cw * L, *out = a.out + (size_t)b * cw * L;
-    const uint32_t per = (cw + T - 1) / T;
-    const uint32_t j0 = tid * per, j1 = min(j0 + per, cw);
-    bool ovf = false;
-    for (int pass = 0; pass < 2; pass++) {
-        // source of element j: pass 0 = repeated input row through pi1, pass 1 = tmp through pi2
-        auto fetch = [&](uint32_t j, El &x) {
-            if (pass == 0) batch_enc_load_wire<L, FIELD>(x, in + (size_t)(a.perm1[j] & (a.row_len - 1)) * L);
-            else enc_load<L, FIELD>(x, tmp + (size_t)a.perm2[j] * L);
-        };
-        El sum;
-        enc_zero<L, FIELD>(sum);
-        for (uint32_t j = j0; j < j1; j++) {
-            El x;
-            fetch(j, x);
-            enc_add<L, FIELD>(sum, x, f);
-        }
-        tot[tid] = sum;
-        __syncthreads();
-        // inclusive scan of the T chunk totals in place, as in encode_row_kernel
-        for (uint32_t off = 1; off < T; off <<= 1) {
-            El x;
-            enc_zero<L, FIELD>(x);
-            if (tid >= off) x = tot[tid - off];
-            __syncthreads();
-            if (tid >= off) {
-                El y = tot[tid];
-                enc_add<L, FIELD>(y, x, f);
-                tot[tid] = y;
-            }
-            __syncthreads();
-        }
-        El run;
-        enc_zero<L, FIELD>(run);
-        if (tid) run = tot[tid - 1];
-        uint64_t *dst = pass == 0 ? tmp : out;
-        for (uint32_t j = j0; j < j1; j++) {
-            El x;
-            fetch(j, x);
-            enc_add<L, FIELD>(run, x, f);
-            ovf |= enc_store<L, FIELD>(run, dst + (size_t)j * L);
-        }
-        __threadfence_block();
-        __syncthreads();  // (pass 1 reads tmp; the tail below reuses tot)
-    }
+    const bool ovf = raa_encode_row<L, FIELD>([&](uint32_t c, El &x) { batch_enc_load_wire<L, FIELD>(x, in + (size_t)c * L); },
+                                              a.row_len, cw, a.perm1, a.perm2, a.tmp + (size_t)b * cw * L,
+                                              a.out + (size_t)b * cw * L, f, tot);
     if constexpr (!FIELD) {
         const int any = __syncthreads_or(ovf ? 1 : 0);
         if (tid == 0) a.head[b].overflow = any ? 1u : 0u;
@@ -131,11 +76,9 @@ __global__ void __launch_bounds__(1024) batch_encode_kernel(BatchEncodeArgs a, F
             if (geq_n<L>(x.v, f.modulus)) nc++;
             if (q1) {
                 uint64_t y[L], t[L];
-#pragma unroll
-                for (int i = 0; i < L; i++) y[i] = q1[(size_t)c * L + i];
+                fe_load<L>(y, q1 + (size_t)c * L);
                 mont_mul<L>(x.v, y, f, t);
-                const uint64_t cy = add_n<L>(acc, t);
-                if (cy || geq_n<L>(acc, f.modulus)) sub_n<L>(acc, f.modulus);
+                fe_add<L>(acc, t, f);
             }
         }
         const int any_nc = __syncthreads_or(nc ? 1 : 0);
@@ -151,7 +94,7 @@ __global__ void __launch_bounds__(1024) batch_encode_kernel(BatchEncodeArgs a, F
             __syncthreads();
         }
         if (tid == 0) {
-            BatchVerifyHead &h = a.head[b];
+            VerifyHead &h = a.head[b];
             if (a.clear_overflow) h.overflow = 0;
             h.noncanonical = any_nc ? 1u : 0u;
 #pragma unroll
@@ -214,90 +157,12 @@ __global__ void __launch_bounds__(256) batch_verify_columns_kernel(BatchVerifyCo
         uint32_t n_bad = 0, n_mal = 0;
         for (uint32_t r = r0; r < R; r += 256) {
             uint64_t v[4];
-            const uint64_t *vp = reinterpret_cast<const uint64_t *>(base + (size_t)r * 32);
-#pragma unroll
-            for (int i = 0; i < 4; i++) v[i] = vp[i];
-            // ---- coeffs[r] * expand(v) in 384-bit two's complement (verify_z.rs:114-120) ----
-            if (coeffs) {
-                uint64_t t[6];
-                const int64_t c = coeffs[r];
-                const uint64_t cu = (uint64_t)c;
-                uint64_t carry = 0;
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const u128 x = (u128)v[i] * cu + carry;
-                    t[i] = (uint64_t)x;
-                    carry = (uint64_t)(x >> 64);
-                }
-                t[4] = carry;
-                t[5] = 0;
-                if ((int64_t)v[3] < 0) {  // v = v_u - 2^256
-                    const u128 x = (u128)t[4] - cu;
-                    t[4] = (uint64_t)x;
-                    t[5] -= (uint64_t)(x >> 64) & 1;
-                }
-                if (c < 0) {  // c = c_u - 2^64, with v sign-extended to 5 limbs above bit 64
-                    uint64_t borrow = 0;
-                    const uint64_t ext = (uint64_t)((int64_t)v[3] >> 63);
-#pragma unroll
-                    for (int i = 0; i < 5; i++) {
-                        const uint64_t sub = i < 4 ? v[i] : ext;
-                        const u128 x = (u128)t[i + 1] - sub - borrow;
-                        t[i + 1] = (uint64_t)x;
-                        borrow = (uint64_t)(x >> 64) & 1;
-                    }
-                }
-                add_n<6>(si, t);
-            }
-            // ---- q0[r] (x) phi(v)  (verify_z.rs:176-183) ----
-            {
-                uint64_t e[FL], t[FL];
-                field_from_int256<FL>(v, f, fq, a.quirk != 0, e);
-                if (q0) {
-                    uint64_t q[FL];
-#pragma unroll
-                    for (int i = 0; i < FL; i++) q[i] = q0[(size_t)r * FL + i];
-                    mont_mul<FL>(q, e, f, t);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < FL; i++) t[i] = e[i];
-                }
-                const uint64_t cy = add_n<FL>(sf, t);
-                if (cy || geq_n<FL>(sf, f.modulus)) sub_n<FL>(sf, f.modulus);
-            }
-            // ---- MerkleProof::verify (pcs/utils.rs:178-210) ----
+            fe_load<4>(v, reinterpret_cast<const uint64_t *>(base + (size_t)r * 32));
+            opening_terms<FL, true>(v, coeffs ? coeffs + r : nullptr, q0 ? q0 + (size_t)r * FL : nullptr, f, fq, a.quirk != 0, si, sf);
             const uint64_t *rec = reinterpret_cast<const uint64_t *>(base + (size_t)R * 32 + (size_t)r * rec_bytes);
-            if (rec[0] != __builtin_bswap64((uint64_t)d)) {
-                n_mal++;
-            } else {
-                uint32_t cur[8];
-                blake3_leaf_limbs<4>(v, cur);
-                uint32_t index = col;
-                for (uint32_t l = 0; l < d; l++) {
-                    uint32_t sib[8];
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        const uint64_t w = rec[1 + 4 * l + i];
-                        sib[2 * i] = (uint32_t)w;
-                        sib[2 * i + 1] = (uint32_t)(w >> 32);
-                    }
-                    uint32_t m[16], h[8];
-                    const bool right = index & 1u;  // current node is the right child
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        m[i] = right ? sib[i] : cur[i];
-                        m[8 + i] = right ? cur[i] : sib[i];
-                    }
-                    blake3_block64(m, h);
-#pragma unroll
-                    for (int i = 0; i < 8; i++) cur[i] = h[i];
-                    index >>= 1;
-                }
-                bool ok = true;
-#pragma unroll
-                for (int i = 0; i < 8; i++) ok &= cur[i] == roots[(size_t)r * 8 + i];
-                if (!ok) n_bad++;
-            }
+            const MerkleRecord m = check_merkle_record(v, rec, d, col, roots + (size_t)r * 8);
+            n_mal += m == kMerkleMalformed;
+            n_bad += m == kMerkleBadPath;
         }
         if (n_bad) atomicAdd(&s_bad[o], n_bad);
         if (n_mal) atomicAdd(&s_mal[o], n_mal);
@@ -310,16 +175,12 @@ __global__ void __launch_bounds__(256) batch_verify_columns_kernel(BatchVerifyCo
         for (int i = 0; i < 6; i++) y[i] = __shfl_xor(si[i], (int)off);
 #pragma unroll
         for (int i = 0; i < FL; i++) q[i] = __shfl_xor(sf[i], (int)off);
-        add_n<6>(si, y);
-        const uint64_t cy = add_n<FL>(sf, q);
-        if (cy || geq_n<FL>(sf, f.modulus)) sub_n<FL>(sf, f.modulus);
+        column_sums_add<FL>(si, sf, y, q, f);
     }
     // ---- ... and over its waves (S = 128 or 256) ----
     if (S > 64 && (tid & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < 6; i++) wave_sum[tid >> 6][i] = si[i];
-#pragma unroll
-        for (int i = 0; i < FL; i++) wave_sum[tid >> 6][6 + i] = sf[i];
+        fe_store<6>(wave_sum[tid >> 6], si);
+        fe_store<FL>(wave_sum[tid >> 6] + 6, sf);
     }
     __syncthreads();
     if (!live || r0 != 0) return;
@@ -327,30 +188,14 @@ __global__ void __launch_bounds__(256) batch_verify_columns_kernel(BatchVerifyCo
         const uint32_t w0 = tid >> 6, nw = S >> 6;
         for (uint32_t w = w0 + 1; w < w0 + nw; w++) {
             uint64_t y[6], q[FL];
-#pragma unroll
-            for (int i = 0; i < 6; i++) y[i] = wave_sum[w][i];
-#pragma unroll
-            for (int i = 0; i < FL; i++) q[i] = wave_sum[w][6 + i];
-            add_n<6>(si, y);
-            const uint64_t cy = add_n<FL>(sf, q);
-            if (cy || geq_n<FL>(sf, f.modulus)) sub_n<FL>(sf, f.modulus);
+            fe_load<6>(y, wave_sum[w]);
+            fe_load<FL>(q, wave_sum[w] + 6);
+            column_sums_add<FL>(si, sf, y, q, f);
         }
     }
-    // ---- the opening's leader holds the complete column sums: compare (verify_finalize_kernel's checks) ----
-    uint32_t fl = 0;
-    if (a.enc_u) {
-        const uint64_t *eu = a.enc_u + ((size_t)b * a.cw + col) * 8;
-        const uint64_t sign = (uint64_t)((int64_t)si[5] >> 63);
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-            if (eu[i] != (i < 6 ? si[i < 6 ? i : 0] : sign)) fl |= 1u;
-    }
-    const uint64_t *ef = a.enc_f + ((size_t)b * a.cw + col) * FL;
-#pragma unroll
-    for (int i = 0; i < FL; i++)
-        if (ef[i] != sf[i]) fl |= 2u;
-    const size_t slot = (size_t)b * a.n_cols + ci;
-    a.flags[slot] = fl;
+    // ---- the opening's leader holds the complete column sums: compare, as verify_finalize_kernel does ----
+    const size_t slot = (size_t)b * a.n_cols + ci, at = (size_t)b * a.cw + col;
+    a.flags[slot] = column_flags<FL>(si, sf, a.enc_u ? a.enc_u + at * 8 : nullptr, 8, a.enc_f + at * FL);
     a.bad_merkle[slot] = s_bad[o];
     a.malformed[slot] = s_mal[o];
 }
@@ -362,10 +207,10 @@ __global__ void __launch_bounds__(256) batch_verify_columns_kernel(BatchVerifyCo
 // ---------------------------------------------------------------------------------------
 struct BatchVerifyReportArgs {
     const uint32_t *flags, *bad_merkle, *malformed;  // [n_polys][n_cols]
-    const BatchVerifyHead *head;                     // [n_polys]
+    const VerifyHead *head;                          // [n_polys]
     const uint64_t *evals;                           // [n_polys][FL]
     uint32_t n_cols, row_len;
-    BatchVerifyReport *reports;                      // [n_polys]
+    zip_verify_report *reports;                      // [n_polys]
 };
 
 template <int FL>
@@ -374,47 +219,38 @@ __global__ void __launch_bounds__(256) batch_verify_report_kernel(BatchVerifyRep
     const uint32_t tid = threadIdx.x, b = blockIdx.x, n = a.n_cols;
     const uint32_t *flags = a.flags + (size_t)b * n, *bad = a.bad_merkle + (size_t)b * n, *mal = a.malformed + (size_t)b * n;
     if (tid == 0) {
-        s_first_a = s_first_b = 0xFFFFFFFFu;
+        s_first_a = s_first_b = kNoOpening;
         s_bad = s_mal = 0;
     }
     __syncthreads();
-    uint32_t first_a = 0xFFFFFFFFu, first_b = 0xFFFFFFFFu, n_bad = 0, n_mal = 0;
+    uint32_t first_a = kNoOpening, first_b = kNoOpening, n_bad = 0, n_mal = 0;
     for (uint32_t ci = tid; ci < n; ci += 256) {
         const uint32_t fl = flags[ci], nb = bad[ci], nm = mal[ci];
         n_bad += nb;
         n_mal += nm;
-        if (((fl & 1u) || nb || nm) && first_a == 0xFFFFFFFFu) first_a = ci;
-        if ((fl & 2u) && first_b == 0xFFFFFFFFu) first_b = ci;
+        if (opening_fails(fl, nm, nb) && first_a == kNoOpening) first_a = ci;
+        if ((fl & 2u) && first_b == kNoOpening) first_b = ci;
     }
     if (n_bad) atomicAdd(&s_bad, n_bad);
     if (n_mal) atomicAdd(&s_mal, n_mal);
-    if (first_a != 0xFFFFFFFFu) atomicMin(&s_first_a, first_a);
-    if (first_b != 0xFFFFFFFFu) atomicMin(&s_first_b, first_b);
+    if (first_a != kNoOpening) atomicMin(&s_first_a, first_a);
+    if (first_b != kNoOpening) atomicMin(&s_first_b, first_b);
     __syncthreads();
     if (tid != 0) return;
-    const BatchVerifyHead &h = a.head[b];
-    BatchVerifyReport rep;
-    rep.verdict = kVerdictAccept;
-    rep.column = 0;
+    const VerifyHead &h = a.head[b];
+    VerifyFacts x;
+    x.overflow = h.overflow != 0;
+    x.first = s_first_a;
+    x.first_why = x.first != kNoOpening ? opening_fails(flags[x.first], mal[x.first], bad[x.first]) : 0u;
+    x.eval_differs = false;
+#pragma unroll
+    for (int i = 0; i < FL; i++) x.eval_differs |= a.evals[(size_t)b * FL + i] != (a.row_len > 1 ? h.dot[i] : 0);
+    x.noncanonical = h.noncanonical != 0;
+    x.first_q0 = s_first_b;
+    zip_verify_report rep;
+    verify_verdict(x, rep);
     rep.bad_merkle_paths = s_bad;
     rep.malformed_paths = s_mal;
-    bool eval_differs = false;
-#pragma unroll
-    for (int i = 0; i < FL; i++) eval_differs |= a.evals[(size_t)b * FL + i] != (a.row_len > 1 ? h.dot[i] : 0);
-    if (h.overflow) {
-        rep.verdict = kVerdictOverflow;
-    } else if (s_first_a != 0xFFFFFFFFu) {
-        const uint32_t ci = s_first_a;
-        rep.column = ci;
-        rep.verdict = (flags[ci] & 1u) ? kVerdictProximityTesting : mal[ci] ? kVerdictMalformed : kVerdictMerkle;
-    } else if (eval_differs) {
-        rep.verdict = kVerdictEvalConsistency;
-    } else if (h.noncanonical) {
-        rep.verdict = kVerdictMalformed;
-    } else if (s_first_b != 0xFFFFFFFFu) {
-        rep.verdict = kVerdictProximityQ0;
-        rep.column = s_first_b;
-    }
     a.reports[b] = rep;
 }
 

@@ -139,6 +139,31 @@ __device__ __forceinline__ void mont_mul(const uint64_t (&a)[FL], const uint64_t
     mont_redc<FL>(t, f, out);
 }
 
+template <int FL>
+__device__ __forceinline__ void fe_add(uint64_t (&a)[FL], const uint64_t (&b)[FL], const FieldDev<FL> &f) {
+    const uint64_t c = add_n<FL>(a, b);
+    if (c || geq_n<FL>(a, f.modulus)) sub_n<FL>(a, f.modulus);
+}
+template <int FL>
+__device__ __forceinline__ void fe_sub(uint64_t (&a)[FL], const uint64_t (&b)[FL], const FieldDev<FL> &f) {
+    if (sub_n<FL>(a, b)) {  // a < b: add the modulus back (wraps when q has no spare bit; the sum is exact)
+        uint64_t q[FL];
+#pragma unroll
+        for (int i = 0; i < FL; i++) q[i] = f.modulus[i];
+        add_n<FL>(a, q);
+    }
+}
+template <int FL>
+__device__ __forceinline__ void fe_load(uint64_t (&a)[FL], const uint64_t *p) {
+#pragma unroll
+    for (int i = 0; i < FL; i++) a[i] = p[i];
+}
+template <int FL>
+__device__ __forceinline__ void fe_store(uint64_t *p, const uint64_t (&a)[FL]) {
+#pragma unroll
+    for (int i = 0; i < FL; i++) p[i] = a[i];
+}
+
 // y (FL+2 limbs, < q * 2^(64+16)) mod q, canonical:  REDC(y) * R^2 * R^-1.
 template <int FL>
 __device__ __forceinline__ void reduce_wide(const uint64_t (&y)[FL + 2], const FieldDev<FL> &f, uint64_t (&out)[FL]) {

@@ -22,6 +22,13 @@
 
 namespace zipk {
 
+// What the encodings of u' and of the evaluation row leave for the verdict: one per proof, written by the kernels
+// (zip_verify: through pointers to its fields) and read by the host or by batch_verify_report_kernel.
+struct VerifyHead {
+    uint32_t overflow, noncanonical, pad[2];
+    uint64_t dot[4];  // <row, q1>, Montgomery
+};
+
 // ---------------------------------------------------------------------------------------
 // RAA encoding of ONE row: repeat, permute, accumulate, permute, accumulate
 // (code_raa.rs:89-105).  O(cw) work, one workgroup.
@@ -50,11 +57,8 @@ __device__ __forceinline__ void enc_load(EncElem<L, FIELD> &x, const uint64_t *p
 }
 template <int L, bool FIELD>
 __device__ __forceinline__ void enc_add(EncElem<L, FIELD> &a, const EncElem<L, FIELD> &b, const FieldDev<L> &f) {
-    constexpr int W = EncElem<L, FIELD>::W;
-    const uint64_t carry = add_n<W>(a.v, b.v);
-    if constexpr (FIELD) {
-        if (carry || geq_n<L>(a.v, f.modulus)) sub_n<L>(a.v, f.modulus);
-    }
+    if constexpr (FIELD) fe_add<L>(a.v, b.v, f);
+    else add_n<L + 1>(a.v, b.v);
 }
 // stores the L limbs; returns true when an integer does not fit them
 template <int L, bool FIELD>
@@ -65,14 +69,13 @@ __device__ __forceinline__ bool enc_store(const EncElem<L, FIELD> &x, uint64_t *
     return false;
 }
 
-template <int L, bool FIELD>
-__global__ void __launch_bounds__(1024) encode_row_kernel(const uint64_t *in, uint32_t row_len, uint32_t cw,
-                                                          const uint32_t *perm1, const uint32_t *perm2,
-                                                          uint64_t *tmp, uint64_t *out, FieldDev<L> f,
-                                                          uint32_t *overflow) {
-    extern __shared__ __align__(16) unsigned char enc_smem[];
+// The two passes, by every thread of ONE workgroup.  load_in(c, x) loads element c of the input row; tot: blockDim.x
+// elements of LDS.  Returns this thread's overflow bit; ends with a barrier (tot is free again).
+template <int L, bool FIELD, class LoadIn>
+__device__ __forceinline__ bool raa_encode_row(LoadIn load_in, uint32_t row_len, uint32_t cw, const uint32_t *perm1,
+                                               const uint32_t *perm2, uint64_t *tmp, uint64_t *out, const FieldDev<L> &f,
+                                               EncElem<L, FIELD> *tot) {
     using El = EncElem<L, FIELD>;
-    El *tot = reinterpret_cast<El *>(enc_smem);  // [blockDim.x]
     const uint32_t T = blockDim.x, tid = threadIdx.x;
     const uint32_t per = (cw + T - 1) / T;
     const uint32_t j0 = tid * per, j1 = min(j0 + per, cw);
@@ -80,7 +83,7 @@ __global__ void __launch_bounds__(1024) encode_row_kernel(const uint64_t *in, ui
     for (int pass = 0; pass < 2; pass++) {
         // source of element j: pass 0 = repeated input row through pi1, pass 1 = tmp through pi2
         auto fetch = [&](uint32_t j, El &x) {
-            if (pass == 0) enc_load<L, FIELD>(x, in + (size_t)(perm1[j] & (row_len - 1)) * L);
+            if (pass == 0) load_in(perm1[j] & (row_len - 1), x);
             else enc_load<L, FIELD>(x, tmp + (size_t)perm2[j] * L);
         };
         El sum;
@@ -111,7 +114,7 @@ __global__ void __launch_bounds__(1024) encode_row_kernel(const uint64_t *in, ui
         if (tid) run = tot[tid - 1];
         uint64_t *dst = pass == 0 ? tmp : out;
         // pass 1 reads tmp while pass 0 of no other thread writes it any more; pass 0 writes tmp
-        // only after every thread has finished READING `in`: no hazard.  Pass 1 writes `out`.
+        // only after every thread has finished READING the input: no hazard.  Pass 1 writes `out`.
         for (uint32_t j = j0; j < j1; j++) {
             El x;
             fetch(j, x);
@@ -121,6 +124,18 @@ __global__ void __launch_bounds__(1024) encode_row_kernel(const uint64_t *in, ui
         __threadfence_block();
         __syncthreads();
     }
+    return ovf;
+}
+
+template <int L, bool FIELD>
+__global__ void __launch_bounds__(1024) encode_row_kernel(const uint64_t *in, uint32_t row_len, uint32_t cw,
+                                                          const uint32_t *perm1, const uint32_t *perm2,
+                                                          uint64_t *tmp, uint64_t *out, FieldDev<L> f,
+                                                          uint32_t *overflow) {
+    extern __shared__ __align__(16) unsigned char enc_smem[];
+    using El = EncElem<L, FIELD>;
+    const bool ovf = raa_encode_row<L, FIELD>([&](uint32_t c, El &x) { enc_load<L, FIELD>(x, in + (size_t)c * L); }, row_len,
+                                              cw, perm1, perm2, tmp, out, f, reinterpret_cast<El *>(enc_smem));
     if (ovf && overflow) atomicOr(overflow, 1u);
 }
 
@@ -164,8 +179,7 @@ __device__ __forceinline__ void field_from_int256(const uint64_t (&v)[4], const 
         mont_mul<FL>(lo, f.r2, f, a);   // lo * R
         mont_mul<FL>(hi, f.r2, f, b);   // hi * R
         mont_mul<FL>(b, f.r2, f, hi);   // hi * R^2 = (hi * 2^(64 FL)) * R
-        const uint64_t c = add_n<FL>(a, hi);
-        if (c || geq_n<FL>(a, f.modulus)) sub_n<FL>(a, f.modulus);
+        fe_add<FL>(a, hi, f);
 #pragma unroll
         for (int i = 0; i < FL; i++) out[i] = a[i];
     }
@@ -182,6 +196,125 @@ __device__ __forceinline__ void field_from_int256(const uint64_t (&v)[4], const 
             for (int i = 0; i < FL; i++) out[i] = q[i];
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// What one opened entry v = column[r] contributes, shared by verify_columns_kernel and
+// batch_verify_columns_kernel (the first assigns the terms, the second accumulates them).
+// ---------------------------------------------------------------------------------------
+// (si, sf) = or += (coeff * expand(v) in 384-bit two's complement, q0r (x) phi(v))   (verify_z.rs:114-120, 176-183).
+// Without coeff / q0r (num_rows == 1) the terms are 0 and phi(v).  The integer term joins si before phi(v) is formed,
+// so that it is not held across the field arithmetic.
+template <int FL, bool ACCUMULATE>
+__device__ __forceinline__ void opening_terms(const uint64_t (&v)[4], const int64_t *coeff, const uint64_t *q0r,
+                                              const FieldDev<FL> &f, const FieldDev<FL> &fq, bool quirk,
+                                              uint64_t (&si)[6], uint64_t (&sf)[FL]) {
+    if (coeff) {
+        uint64_t t[6];
+        const int64_t c = *coeff;
+        const uint64_t cu = (uint64_t)c;
+        uint64_t carry = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const u128 x = (u128)v[i] * cu + carry;
+            t[i] = (uint64_t)x;
+            carry = (uint64_t)(x >> 64);
+        }
+        t[4] = carry;
+        t[5] = 0;
+        if ((int64_t)v[3] < 0) {  // v = v_u - 2^256
+            const u128 x = (u128)t[4] - cu;
+            t[4] = (uint64_t)x;
+            t[5] -= (uint64_t)(x >> 64) & 1;
+        }
+        if (c < 0) {  // c = c_u - 2^64, with v sign-extended to 5 limbs above bit 64
+            uint64_t borrow = 0;
+            const uint64_t ext = (uint64_t)((int64_t)v[3] >> 63);
+#pragma unroll
+            for (int i = 0; i < 5; i++) {
+                const uint64_t sub = i < 4 ? v[i] : ext;
+                const u128 x = (u128)t[i + 1] - sub - borrow;
+                t[i + 1] = (uint64_t)x;
+                borrow = (uint64_t)(x >> 64) & 1;
+            }
+        }
+        if constexpr (ACCUMULATE) add_n<6>(si, t);
+        else fe_store<6>(si, t);
+    } else if constexpr (!ACCUMULATE) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) si[i] = 0;
+    }
+    uint64_t e[FL], t[FL];
+    field_from_int256<FL>(v, f, fq, quirk, e);
+    if (q0r) {
+        uint64_t q[FL];
+        fe_load<FL>(q, q0r);
+        mont_mul<FL>(q, e, f, t);
+    } else {
+        fe_store<FL>(t, e);
+    }
+    if constexpr (ACCUMULATE) fe_add<FL>(sf, t, f);
+    else fe_store<FL>(sf, t);
+}
+
+// MerkleProof::verify of one record (pcs/utils.rs:178-210): be64(depth) | depth siblings, leaf = v at column col
+enum MerkleRecord : uint32_t { kMerkleOk = 0, kMerkleBadPath = 1, kMerkleMalformed = 2 };
+
+__device__ __forceinline__ MerkleRecord check_merkle_record(const uint64_t (&v)[4], const uint64_t *rec, uint32_t depth,
+                                                            uint32_t col, const uint32_t *root) {
+    if (rec[0] != __builtin_bswap64((uint64_t)depth)) return kMerkleMalformed;
+    uint32_t cur[8];
+    blake3_leaf_limbs<4>(v, cur);
+    uint32_t index = col;
+    for (uint32_t l = 0; l < depth; l++) {
+        uint32_t sib[8];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint64_t w = rec[1 + 4 * l + i];
+            sib[2 * i] = (uint32_t)w;
+            sib[2 * i + 1] = (uint32_t)(w >> 32);
+        }
+        uint32_t m[16], h[8];
+        const bool right = index & 1u;  // current node is the right child
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            m[i] = right ? sib[i] : cur[i];
+            m[8 + i] = right ? cur[i] : sib[i];
+        }
+        blake3_block64(m, h);
+#pragma unroll
+        for (int i = 0; i < 8; i++) cur[i] = h[i];
+        index >>= 1;
+    }
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 8; i++) ok &= cur[i] == root[i];
+    return ok ? kMerkleOk : kMerkleBadPath;
+}
+
+// (si, sf) += (y, q): the two column sums, 384-bit wrap-around and modular
+template <int FL>
+__device__ __forceinline__ void column_sums_add(uint64_t (&si)[6], uint64_t (&sf)[FL], const uint64_t (&y)[6],
+                                                const uint64_t (&q)[FL], const FieldDev<FL> &f) {
+    add_n<6>(si, y);
+    fe_add<FL>(sf, q, f);
+}
+
+// The complete sums of an opening against the encoded combined rows at its column (enc_int: m_limbs limbs, or null):
+// bit 0 = proximity test over Z failed (verify_z.rs:122-125), bit 1 = over F_q (:184-186).
+template <int FL>
+__device__ __forceinline__ uint32_t column_flags(const uint64_t (&si)[6], const uint64_t (&sf)[FL], const uint64_t *enc_int,
+                                                 uint32_t m_limbs, const uint64_t *enc_f) {
+    uint32_t fl = 0;
+    if (enc_int) {
+        const uint64_t sign = (uint64_t)((int64_t)si[5] >> 63);
+        for (uint32_t i = 0; i < m_limbs; i++)
+            if (enc_int[i] != (i < 6 ? si[i < 6 ? i : 0] : sign)) fl |= 1u;
+    }
+#pragma unroll
+    for (int i = 0; i < FL; i++)
+        if (enc_f[i] != sf[i]) fl |= 2u;
+    return fl;
 }
 
 struct VerifyColsArgs {
@@ -203,8 +336,7 @@ __global__ void __launch_bounds__(256) verify_columns_kernel(VerifyColsArgs a, F
     __shared__ uint64_t red[256 * (6 + FL)];
     const uint32_t ci = blockIdx.x, tid = threadIdx.x;
     const uint32_t r = blockIdx.y * 256 + tid;
-    const uint32_t col = a.cols[ci];
-    const uint32_t d = a.depth, rec_bytes = 8 + 32 * d;
+    const uint32_t rec_bytes = 8 + 32 * a.depth;
     const size_t col_bytes = (size_t)a.num_rows * (32 + rec_bytes);
     const uint8_t *base = a.wire + (size_t)ci * col_bytes;
     uint64_t si[6] = {0, 0, 0, 0, 0, 0}, sf[FL];
@@ -212,105 +344,28 @@ __global__ void __launch_bounds__(256) verify_columns_kernel(VerifyColsArgs a, F
     for (int i = 0; i < FL; i++) sf[i] = 0;
     if (r < a.num_rows) {
         uint64_t v[4];
-        const uint64_t *vp = reinterpret_cast<const uint64_t *>(base + (size_t)r * 32);
-#pragma unroll
-        for (int i = 0; i < 4; i++) v[i] = vp[i];
-        // ---- coeffs[r] * expand(v) in 384-bit two's complement (verify_z.rs:114-120) ----
-        if (a.coeffs) {
-            const int64_t c = a.coeffs[r];
-            const uint64_t cu = (uint64_t)c;
-            uint64_t carry = 0;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const u128 x = (u128)v[i] * cu + carry;
-                si[i] = (uint64_t)x;
-                carry = (uint64_t)(x >> 64);
-            }
-            si[4] = carry;
-            si[5] = 0;
-            if ((int64_t)v[3] < 0) {  // v = v_u - 2^256
-                const u128 x = (u128)si[4] - cu;
-                si[4] = (uint64_t)x;
-                si[5] -= (uint64_t)(x >> 64) & 1;
-            }
-            if (c < 0) {  // c = c_u - 2^64, with v sign-extended to 5 limbs above bit 64
-                uint64_t borrow = 0;
-                const uint64_t ext = (uint64_t)((int64_t)v[3] >> 63);
-#pragma unroll
-                for (int i = 0; i < 5; i++) {
-                    const uint64_t sub = i < 4 ? v[i] : ext;
-                    const u128 x = (u128)si[i + 1] - sub - borrow;
-                    si[i + 1] = (uint64_t)x;
-                    borrow = (uint64_t)(x >> 64) & 1;
-                }
-            }
-        }
-        // ---- q0[r] (x) phi(v)  (verify_z.rs:176-183) ----
-        uint64_t e[FL];
-        field_from_int256<FL>(v, f, fq, a.quirk != 0, e);
-        if (a.q0) {
-            uint64_t q[FL];
-#pragma unroll
-            for (int i = 0; i < FL; i++) q[i] = a.q0[(size_t)r * FL + i];
-            mont_mul<FL>(q, e, f, sf);
-        } else {
-#pragma unroll
-            for (int i = 0; i < FL; i++) sf[i] = e[i];
-        }
-        // ---- MerkleProof::verify (pcs/utils.rs:178-210) ----
+        fe_load<4>(v, reinterpret_cast<const uint64_t *>(base + (size_t)r * 32));
+        opening_terms<FL, false>(v, a.coeffs ? a.coeffs + r : nullptr, a.q0 ? a.q0 + (size_t)r * FL : nullptr, f, fq,
+                                 a.quirk != 0, si, sf);
         const uint64_t *rec = reinterpret_cast<const uint64_t *>(base + (size_t)a.num_rows * 32 + (size_t)r * rec_bytes);
-        if (rec[0] != __builtin_bswap64((uint64_t)d)) {
-            atomicAdd(&a.malformed[ci], 1u);
-        } else {
-            uint32_t cur[8];
-            blake3_leaf_limbs<4>(v, cur);
-            uint32_t index = col;
-            for (uint32_t l = 0; l < d; l++) {
-                uint32_t sib[8];
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const uint64_t w = rec[1 + 4 * l + i];
-                    sib[2 * i] = (uint32_t)w;
-                    sib[2 * i + 1] = (uint32_t)(w >> 32);
-                }
-                uint32_t m[16], h[8];
-                const bool right = index & 1u;  // current node is the right child
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    m[i] = right ? sib[i] : cur[i];
-                    m[8 + i] = right ? cur[i] : sib[i];
-                }
-                blake3_block64(m, h);
-#pragma unroll
-                for (int i = 0; i < 8; i++) cur[i] = h[i];
-                index >>= 1;
-            }
-            bool ok = true;
-#pragma unroll
-            for (int i = 0; i < 8; i++) ok &= cur[i] == a.roots[(size_t)r * 8 + i];
-            if (!ok) atomicAdd(&a.bad_merkle[ci], 1u);
-        }
+        const MerkleRecord m = check_merkle_record(v, rec, a.depth, a.cols[ci], a.roots + (size_t)r * 8);
+        if (m == kMerkleMalformed) atomicAdd(&a.malformed[ci], 1u);
+        if (m == kMerkleBadPath) atomicAdd(&a.bad_merkle[ci], 1u);
     }
-    // ---- block sums: 384-bit wrap-around adds and modular adds ----
-#pragma unroll
-    for (int i = 0; i < 6; i++) red[tid * (6 + FL) + i] = si[i];
-#pragma unroll
-    for (int i = 0; i < FL; i++) red[tid * (6 + FL) + 6 + i] = sf[i];
+    // ---- block sums ----
+    fe_store<6>(red + tid * (6 + FL), si);
+    fe_store<FL>(red + tid * (6 + FL) + 6, sf);
     __syncthreads();
     for (uint32_t s = 128; s > 0; s >>= 1) {
         if (tid < s) {
             uint64_t x[6], y[6], p[FL], q[FL];
-#pragma unroll
-            for (int i = 0; i < 6; i++) { x[i] = red[tid * (6 + FL) + i]; y[i] = red[(tid + s) * (6 + FL) + i]; }
-#pragma unroll
-            for (int i = 0; i < FL; i++) { p[i] = red[tid * (6 + FL) + 6 + i]; q[i] = red[(tid + s) * (6 + FL) + 6 + i]; }
-            add_n<6>(x, y);
-            const uint64_t c = add_n<FL>(p, q);
-            if (c || geq_n<FL>(p, f.modulus)) sub_n<FL>(p, f.modulus);
-#pragma unroll
-            for (int i = 0; i < 6; i++) red[tid * (6 + FL) + i] = x[i];
-#pragma unroll
-            for (int i = 0; i < FL; i++) red[tid * (6 + FL) + 6 + i] = p[i];
+            fe_load<6>(x, red + tid * (6 + FL));
+            fe_load<6>(y, red + (tid + s) * (6 + FL));
+            fe_load<FL>(p, red + tid * (6 + FL) + 6);
+            fe_load<FL>(q, red + (tid + s) * (6 + FL) + 6);
+            column_sums_add<FL>(x, p, y, q, f);
+            fe_store<6>(red + tid * (6 + FL), x);
+            fe_store<FL>(red + tid * (6 + FL) + 6, p);
         }
         __syncthreads();
     }
@@ -323,8 +378,7 @@ __global__ void __launch_bounds__(256) verify_columns_kernel(VerifyColsArgs a, F
     }
 }
 
-// Per opened column: fold the row-block partials and compare with the encoded combined rows.
-// flags[ci]: bit 0 = proximity test over Z failed (verify_z.rs:122-125), bit 1 = over F_q (:184-186).
+// Per opened column: fold the row-block partials and compare with the encoded combined rows (column_flags).
 template <int FL>
 __global__ void __launch_bounds__(256) verify_finalize_kernel(const uint64_t *part_int, const uint64_t *part_f,
                                                               uint32_t blocks, const uint32_t *cols, uint32_t n_cols,
@@ -333,29 +387,16 @@ __global__ void __launch_bounds__(256) verify_finalize_kernel(const uint64_t *pa
     const uint32_t ci = blockIdx.x * blockDim.x + threadIdx.x;
     if (ci >= n_cols) return;
     const uint32_t col = cols[ci];
-    uint32_t fl = 0;
     uint64_t s[6] = {0, 0, 0, 0, 0, 0}, p[FL];
 #pragma unroll
     for (int i = 0; i < FL; i++) p[i] = 0;
     for (uint32_t b = 0; b < blocks; b++) {
         uint64_t y[6], q[FL];
-#pragma unroll
-        for (int i = 0; i < 6; i++) y[i] = part_int[((size_t)ci * blocks + b) * 6 + i];
-#pragma unroll
-        for (int i = 0; i < FL; i++) q[i] = part_f[((size_t)ci * blocks + b) * FL + i];
-        add_n<6>(s, y);
-        const uint64_t c = add_n<FL>(p, q);
-        if (c || geq_n<FL>(p, f.modulus)) sub_n<FL>(p, f.modulus);
+        fe_load<6>(y, part_int + ((size_t)ci * blocks + b) * 6);
+        fe_load<FL>(q, part_f + ((size_t)ci * blocks + b) * FL);
+        column_sums_add<FL>(s, p, y, q, f);
     }
-    if (enc_int) {
-        const uint64_t sign = (uint64_t)((int64_t)s[5] >> 63);
-        for (uint32_t i = 0; i < m_limbs; i++)
-            if (enc_int[(size_t)col * m_limbs + i] != (i < 6 ? s[i] : sign)) fl |= 1u;
-    }
-#pragma unroll
-    for (int i = 0; i < FL; i++)
-        if (enc_f[(size_t)col * FL + i] != p[i]) fl |= 2u;
-    flags[ci] = fl;
+    flags[ci] = column_flags<FL>(s, p, enc_int ? enc_int + (size_t)col * m_limbs : nullptr, m_limbs, enc_f + (size_t)col * FL);
 }
 
 // out = sum_c a[c] (x) b[c]  (Montgomery values; inner_product, src/zip/utils.rs).  One workgroup.
@@ -369,24 +410,20 @@ __global__ void __launch_bounds__(1024) field_dot_kernel(const uint64_t *a, cons
     for (int i = 0; i < FL; i++) acc[i] = 0;
     for (uint32_t c = tid; c < n; c += blockDim.x) {
         uint64_t x[FL], y[FL], t[FL];
-#pragma unroll
-        for (int i = 0; i < FL; i++) { x[i] = a[(size_t)c * FL + i]; y[i] = b[(size_t)c * FL + i]; }
+        fe_load<FL>(x, a + (size_t)c * FL);
+        fe_load<FL>(y, b + (size_t)c * FL);
         mont_mul<FL>(x, y, f, t);
-        const uint64_t cy = add_n<FL>(acc, t);
-        if (cy || geq_n<FL>(acc, f.modulus)) sub_n<FL>(acc, f.modulus);
+        fe_add<FL>(acc, t, f);
     }
-#pragma unroll
-    for (int i = 0; i < FL; i++) red[tid * FL + i] = acc[i];
+    fe_store<FL>(red + tid * FL, acc);
     __syncthreads();
     for (uint32_t s = blockDim.x / 2; s > 0; s >>= 1) {
         if (tid < s) {
             uint64_t p[FL], q[FL];
-#pragma unroll
-            for (int i = 0; i < FL; i++) { p[i] = red[tid * FL + i]; q[i] = red[(tid + s) * FL + i]; }
-            const uint64_t cy = add_n<FL>(p, q);
-            if (cy || geq_n<FL>(p, f.modulus)) sub_n<FL>(p, f.modulus);
-#pragma unroll
-            for (int i = 0; i < FL; i++) red[tid * FL + i] = p[i];
+            fe_load<FL>(p, red + tid * FL);
+            fe_load<FL>(q, red + (tid + s) * FL);
+            fe_add<FL>(p, q, f);
+            fe_store<FL>(red + tid * FL, p);
         }
         __syncthreads();
     }

@@ -21,6 +21,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/zip_hip.h"
@@ -836,6 +837,16 @@ FieldDev<FL> to_dev(const HostField &h) {
     return d;
 }
 
+// fn(std::integral_constant<int, FL>) for a field of fl limbs (2, 3 or 4: make_field admits no other)
+template <class Fn>
+auto with_fl(uint32_t fl, Fn &&fn) {
+    switch (fl) {
+        case 2: return fn(std::integral_constant<int, 2>{});
+        case 3: return fn(std::integral_constant<int, 3>{});
+        default: return fn(std::integral_constant<int, 4>{});
+    }
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the function ON ONE DEVICE: remembered per
 // (function, device), under a lock -- contexts of different devices (and threads) share these launch helpers.
 int32_t ensure_dynamic_lds(zip_ctx *ctx, const void *kern, size_t bytes) {
@@ -1264,12 +1275,9 @@ int32_t run_combine_fl(zip_ctx *ctx, const int64_t *evals_d, const int64_t *coef
 int32_t run_combine(zip_ctx *ctx, const int64_t *evals_d, const int64_t *coeffs_dv, const uint64_t *q0_dv,
                     const HostField *hf, bool do_int, bool do_field, const CombineOut &out,
                     CombineScratch *ext = nullptr, int phase = 0) {
-    const uint32_t fl = hf ? hf->fl : 4;
-    switch (fl) {
-        case 2: return run_combine_fl<2>(ctx, evals_d, coeffs_dv, q0_dv, hf, do_int, do_field, out, ext, phase);
-        case 3: return run_combine_fl<3>(ctx, evals_d, coeffs_dv, q0_dv, hf, do_int, do_field, out, ext, phase);
-        default: return run_combine_fl<4>(ctx, evals_d, coeffs_dv, q0_dv, hf, do_int, do_field, out, ext, phase);
-    }
+    return with_fl(hf ? hf->fl : 4, [&](auto FL) {
+        return run_combine_fl<decltype(FL)::value>(ctx, evals_d, coeffs_dv, q0_dv, hf, do_int, do_field, out, ext, phase);
+    });
 }
 
 int32_t check_cols(zip_ctx *ctx, const uint32_t *cols_h, uint32_t n_cols) {
@@ -1520,37 +1528,109 @@ bool make_quirk_field(const HostField &hf, HostField *fq) {
     return true;
 }
 
+// FieldDev of the field and of 2^256 - q for the verifier's kernels (fq = fd and quirk = 0 unless the quirk applies)
+template <int FL>
+struct VerifyField {
+    FieldDev<FL> fd, fq;
+    uint32_t quirk;
+};
+template <int FL>
+VerifyField<FL> verify_field(const HostField &hf) {
+    VerifyField<FL> v{to_dev<FL>(hf), to_dev<FL>(hf), 0u};
+    if constexpr (FL == 4) {
+        HostField hq;
+        if (make_quirk_field(hf, &hq)) {
+            v.fq = to_dev<4>(hq);
+            v.quirk = 1u;
+        }
+    }
+    return v;
+}
+
+// The encoders' workgroup: one thread per codeword element up to 1024, at least a wave (a power of two: the batch
+// kernel's dot-product tree needs one), and one element of dynamic LDS per thread.
+struct EncodeShape {
+    uint32_t threads;
+    size_t lds;
+};
+template <int L, bool FIELD>
+EncodeShape encode_shape(uint32_t cw) {
+    const uint32_t threads = cw < 1024 ? (cw < 64 ? 64 : cw) : 1024;
+    return {threads, (size_t)threads * sizeof(EncElem<L, FIELD>)};
+}
+
 template <int L, bool FIELD>
 int32_t launch_encode_row(zip_ctx *ctx, const uint64_t *in, uint64_t *tmp, uint64_t *out, const FieldDev<L> &fd,
                           uint32_t *overflow) {
-    const uint32_t cw = ctx->p.codeword_len;
-    const uint32_t threads = cw < 1024 ? (cw < 64 ? 64 : cw) : 1024;
-    const size_t lds = (size_t)threads * sizeof(EncElem<L, FIELD>);
+    const EncodeShape s = encode_shape<L, FIELD>(ctx->p.codeword_len);
     auto kern = encode_row_kernel<L, FIELD>;
-    if (int32_t rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
+    if (int32_t rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), s.lds)) return rc;
     LaunchTimer t(ctx, "encode_row_kernel");
-    hipLaunchKernelGGL(kern, dim3(1), dim3(threads), lds, ctx->stream, in, ctx->p.row_len, cw, ctx->perm1_d,
+    hipLaunchKernelGGL(kern, dim3(1), dim3(s.threads), s.lds, ctx->stream, in, ctx->p.row_len, ctx->p.codeword_len, ctx->perm1_d,
                        ctx->perm2_d, tmp, out, fd, overflow);
     HIP_TRY(ctx, hipGetLastError());
     return ZIP_OK;
 }
 
+// the device inputs of zip_verify (n_polys = 1, no evals_d) and zip_batch_verify
 struct VerifyIn {
-    const uint8_t *proof_d;  // device
+    const uint8_t *proofs_d;
+    size_t stream_bytes;
     const uint8_t *roots_d;
     const int64_t *coeffs_d;
     const uint32_t *cols_d;
-    const uint64_t *q0_d, *q1_d;
-    uint32_t n_cols;
+    const uint64_t *q0_d, *q1_d, *evals_d;
+    uint32_t n_cols, n_polys;
 };
-struct VerifyCounters {  // one device block, copied back in one piece
-    uint32_t overflow, noncanonical, pad[2];
-    uint64_t dot[4];
-};
+
+// What zip_verify and zip_batch_verify ask of their arguments alike; n_openings: over all the proofs
+int32_t check_verify_args(zip_ctx *ctx, const int64_t *coeffs, const uint32_t *cols, uint32_t n_openings, const uint64_t *q0_mont,
+                          const uint64_t *q1_mont, const zip_field *field, HostField *hf) {
+    if (int32_t rc = make_field(ctx, field, hf)) return rc;
+    if (ctx->p.num_rows > 1 && (!coeffs || !q0_mont)) return fail(ctx, ZIP_ERR_NULL, "coeffs / q0_mont is NULL");
+    if (ctx->p.row_len > 1 && !q1_mont) return fail(ctx, ZIP_ERR_NULL, "q1_mont is NULL");
+    return check_cols(ctx, cols, n_openings);
+}
+
+// k proof streams to the device when they are the host's, and the small inputs of k proofs in one block.
+// q_1 of a one-column matrix is empty in the reference (pcs/utils.rs:253-276): <row, q1> is then 0.
+int32_t stage_verify_inputs(zip_ctx *ctx, uint32_t k, size_t stream_bytes, const uint8_t *proofs, zip_mem_kind proofs_kind,
+                            const uint8_t *roots, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols,
+                            const uint64_t *q0_mont, const uint64_t *q1_mont, const uint64_t *evals_mont, uint32_t fl,
+                            Scratch &pbuf, Scratch &small, VerifyIn *in) {
+    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len;
+    const bool single = R == 1;
+    int32_t rc;
+    in->proofs_d = proofs;
+    if (proofs_kind == ZIP_MEM_HOST) {
+        if ((rc = pbuf.get((size_t)k * stream_bytes))) return rc;
+        if ((rc = copy_h2d_bounced(ctx, pbuf.ptr, proofs, (size_t)k * stream_bytes, ctx->stream))) return rc;
+        in->proofs_d = pbuf.as<uint8_t>();
+    }
+    SmallInputs si;
+    si.src[0] = coeffs;     si.bytes[0] = single ? 0 : (size_t)k * R * 8;
+    si.src[1] = q0_mont;    si.bytes[1] = single ? 0 : (size_t)k * R * fl * 8;
+    si.src[2] = cols;       si.bytes[2] = (size_t)k * n_cols * 4;
+    si.src[3] = q1_mont;    si.bytes[3] = C > 1 ? (size_t)k * C * fl * 8 : 0;
+    si.src[4] = roots;      si.bytes[4] = (size_t)k * R * 32;
+    si.src[5] = evals_mont; si.bytes[5] = evals_mont ? (size_t)k * fl * 8 : 0;
+    unsigned char *sb;
+    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
+    in->stream_bytes = stream_bytes;
+    in->coeffs_d = reinterpret_cast<const int64_t *>(sb + si.off[0]);
+    in->q0_d = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
+    in->cols_d = reinterpret_cast<const uint32_t *>(sb + si.off[2]);
+    in->q1_d = reinterpret_cast<const uint64_t *>(sb + si.off[3]);
+    in->roots_d = sb + si.off[4];
+    in->evals_d = reinterpret_cast<const uint64_t *>(sb + si.off[5]);
+    in->n_cols = n_cols;
+    in->n_polys = k;
+    return ZIP_OK;
+}
 
 template <int FL>
 int32_t run_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, std::vector<uint32_t> &flags,
-                      std::vector<uint32_t> &bad, std::vector<uint32_t> &malformed, VerifyCounters *cnt) {
+                      std::vector<uint32_t> &bad, std::vector<uint32_t> &malformed, VerifyHead *cnt) {
     const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len, M = ctx->p.m_limbs;
     const uint32_t n_cols = in.n_cols;
     const bool single = R == 1;
@@ -1564,24 +1644,18 @@ int32_t run_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, std
     if ((rc = tmp.get((size_t)cw * M * 8))) return rc;
     if ((rc = row.get((size_t)C * FL * 8))) return rc;
     if ((rc = parts.get((size_t)n_cols * blocks * (6 + FL) * 8 + 64))) return rc;
-    // misc: counters | flags[n] | bad[n] | malformed[n]
-    const size_t misc_bytes = sizeof(VerifyCounters) + (size_t)3 * n_cols * 4;
+    // misc: head | flags[n] | bad[n] | malformed[n], one device block, copied back in one piece
+    const size_t misc_bytes = sizeof(VerifyHead) + (size_t)3 * n_cols * 4;
     if ((rc = misc.get(misc_bytes))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(misc.ptr, 0, misc_bytes, ctx->stream));
-    VerifyCounters *cnt_d = misc.as<VerifyCounters>();
+    VerifyHead *cnt_d = misc.as<VerifyHead>();
     uint32_t *flags_d = reinterpret_cast<uint32_t *>(cnt_d + 1), *bad_d = flags_d + n_cols, *mal_d = bad_d + n_cols;
-    const FieldDev<FL> fd = to_dev<FL>(hf);
-    FieldDev<FL> fq = fd;
-    bool quirk = false;
-    if constexpr (FL == 4) {
-        HostField hq;
-        quirk = make_quirk_field(hf, &hq);
-        if (quirk) fq = to_dev<4>(hq);
-    }
+    const VerifyField<FL> vf = verify_field<FL>(hf);
+    const FieldDev<FL> &fd = vf.fd;
     // encode_wide(u') (verify_z.rs:75-77)
     if (!single) {
         FieldDev<8> unused{};
-        if ((rc = launch_encode_row<8, false>(ctx, reinterpret_cast<const uint64_t *>(in.proof_d), tmp.as<uint64_t>(),
+        if ((rc = launch_encode_row<8, false>(ctx, reinterpret_cast<const uint64_t *>(in.proofs_d), tmp.as<uint64_t>(),
                                               enc_u.as<uint64_t>(), unused, &cnt_d->overflow)))
             return rc;
     }
@@ -1589,7 +1663,7 @@ int32_t run_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, std
     {
         LaunchTimer t(ctx, "decode_field_row_kernel");
         hipLaunchKernelGGL(decode_field_row_kernel<FL>, dim3((C + 255) / 256), dim3(256), 0, ctx->stream,
-                           in.proof_d + u_bytes + cols_bytes, C, row.as<uint64_t>(), &cnt_d->noncanonical, fd);
+                           in.proofs_d + u_bytes + cols_bytes, C, row.as<uint64_t>(), &cnt_d->noncanonical, fd);
         HIP_TRY(ctx, hipGetLastError());
     }
     if ((rc = launch_encode_row<FL, true>(ctx, row.as<uint64_t>(), tmp.as<uint64_t>(), enc_f.as<uint64_t>(), fd, nullptr)))
@@ -1602,7 +1676,7 @@ int32_t run_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, std
     }
     if (n_cols) {
         VerifyColsArgs a{};
-        a.wire = in.proof_d + u_bytes;
+        a.wire = in.proofs_d + u_bytes;
         a.cols = in.cols_d;
         a.coeffs = single ? nullptr : in.coeffs_d;
         a.q0 = single ? nullptr : in.q0_d;
@@ -1610,14 +1684,14 @@ int32_t run_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, std
         a.num_rows = R;
         a.depth = ctx->depth;
         a.n_cols = n_cols;
-        a.quirk = quirk ? 1u : 0u;
+        a.quirk = vf.quirk;
         a.part_int = parts.as<uint64_t>();
         a.part_f = a.part_int + (size_t)n_cols * blocks * 6;
         a.bad_merkle = bad_d;
         a.malformed = mal_d;
         {
             LaunchTimer t(ctx, "verify_columns_kernel");
-            hipLaunchKernelGGL(verify_columns_kernel<FL>, dim3(n_cols, blocks), dim3(256), 0, ctx->stream, a, fd, fq);
+            hipLaunchKernelGGL(verify_columns_kernel<FL>, dim3(n_cols, blocks), dim3(256), 0, ctx->stream, a, fd, vf.fq);
             HIP_TRY(ctx, hipGetLastError());
         }
         {
@@ -1631,8 +1705,8 @@ int32_t run_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, std
     std::vector<unsigned char> host(misc_bytes);
     HIP_TRY(ctx, hipMemcpyAsync(host.data(), misc.ptr, misc_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, stream_wait(ctx->stream));
-    memcpy(cnt, host.data(), sizeof(VerifyCounters));
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(host.data() + sizeof(VerifyCounters));
+    memcpy(cnt, host.data(), sizeof(VerifyHead));
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(host.data() + sizeof(VerifyHead));
     flags.assign(w, w + n_cols);
     bad.assign(w + n_cols, w + 2 * n_cols);
     malformed.assign(w + 2 * n_cols, w + 3 * n_cols);
@@ -1641,43 +1715,23 @@ int32_t run_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, std
 
 // ---- the batched verifier (zip_batch_verify): five launches whatever n_polys is -- encode_wide(u'), encode_f(row) with
 // the decode and <row, q1> fused in, the column checks, the reports -- one device-to-host copy of n_polys reports, one wait.
-static_assert(sizeof(BatchVerifyReport) == sizeof(zip_verify_report) && offsetof(BatchVerifyReport, column) == offsetof(zip_verify_report, column) &&
-                  offsetof(BatchVerifyReport, bad_merkle_paths) == offsetof(zip_verify_report, bad_merkle_paths) &&
-                  offsetof(BatchVerifyReport, malformed_paths) == offsetof(zip_verify_report, malformed_paths),
-              "the report kernel writes zip_verify_report");
-static_assert(kVerdictAccept == ZIP_VERIFY_ACCEPT && kVerdictProximityTesting == ZIP_VERIFY_PROXIMITY_TESTING &&
-                  kVerdictEvalConsistency == ZIP_VERIFY_EVAL_CONSISTENCY && kVerdictProximityQ0 == ZIP_VERIFY_PROXIMITY_Q0 &&
-                  kVerdictMerkle == ZIP_VERIFY_MERKLE && kVerdictMalformed == ZIP_VERIFY_MALFORMED && kVerdictOverflow == ZIP_VERIFY_OVERFLOW,
-              "the report kernel writes zip_verify_verdict");
 
 // Process-wide count of zip_batch_verify calls that reached the device (zip_batch_verify_calls)
 std::atomic<uint64_t> g_batch_verify_calls{0};
 
 template <int L, bool FIELD>
 int32_t launch_batch_encode(zip_ctx *ctx, BatchEncodeArgs a, uint32_t n_polys, const FieldDev<L> &fd, const char *name) {
-    const uint32_t cw = ctx->p.codeword_len;
-    const uint32_t threads = cw < 1024 ? (cw < 64 ? 64 : cw) : 1024;  // (a power of two: the dot product's tree needs one)
-    const size_t lds = (size_t)threads * sizeof(EncElem<L, FIELD>);
+    const EncodeShape s = encode_shape<L, FIELD>(ctx->p.codeword_len);
     auto kern = batch_encode_kernel<L, FIELD>;
-    if (int32_t rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
+    if (int32_t rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), s.lds)) return rc;
     LaunchTimer t(ctx, name);
-    hipLaunchKernelGGL(kern, dim3(n_polys), dim3(threads), lds, ctx->stream, a, fd);
+    hipLaunchKernelGGL(kern, dim3(n_polys), dim3(s.threads), s.lds, ctx->stream, a, fd);
     HIP_TRY(ctx, hipGetLastError());
     return ZIP_OK;
 }
 
-struct BatchVerifyIn {
-    const uint8_t *proofs_d;
-    size_t stream_bytes;
-    const uint8_t *roots_d;
-    const int64_t *coeffs_d;
-    const uint32_t *cols_d;
-    const uint64_t *q0_d, *q1_d, *evals_d;
-    uint32_t n_cols, n_polys;
-};
-
 template <int FL>
-int32_t run_batch_verify_fl(zip_ctx *ctx, const BatchVerifyIn &in, const HostField &hf, zip_verify_report *reports) {
+int32_t run_batch_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, zip_verify_report *reports) {
     const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len, M = ctx->p.m_limbs;
     const uint32_t n_cols = in.n_cols, B = in.n_polys;
     const bool single = R == 1;
@@ -1690,20 +1744,14 @@ int32_t run_batch_verify_fl(zip_ctx *ctx, const BatchVerifyIn &in, const HostFie
     if ((rc = tmp.get((size_t)B * cw * (single ? FL : M) * 8))) return rc;  // (the two encodings run one after the other)
     // misc: reports[B] | heads[B] | flags[B n] | bad[B n] | malformed[B n]; every word is written before it is read
     const size_t per_opening = (size_t)B * n_cols * 4;
-    const size_t misc_bytes = (size_t)B * (sizeof(BatchVerifyReport) + sizeof(BatchVerifyHead)) + 3 * per_opening;
+    const size_t misc_bytes = (size_t)B * (sizeof(zip_verify_report) + sizeof(VerifyHead)) + 3 * per_opening;
     if ((rc = misc.get(misc_bytes))) return rc;
-    BatchVerifyReport *reports_d = misc.as<BatchVerifyReport>();
-    BatchVerifyHead *head_d = reinterpret_cast<BatchVerifyHead *>(reports_d + B);
+    zip_verify_report *reports_d = misc.as<zip_verify_report>();
+    VerifyHead *head_d = reinterpret_cast<VerifyHead *>(reports_d + B);
     uint32_t *flags_d = reinterpret_cast<uint32_t *>(head_d + B), *bad_d = flags_d + (size_t)B * n_cols,
              *mal_d = bad_d + (size_t)B * n_cols;
-    const FieldDev<FL> fd = to_dev<FL>(hf);
-    FieldDev<FL> fq = fd;
-    bool quirk = false;
-    if constexpr (FL == 4) {
-        HostField hq;
-        quirk = make_quirk_field(hf, &hq);
-        if (quirk) fq = to_dev<4>(hq);
-    }
+    const VerifyField<FL> vf = verify_field<FL>(hf);
+    const FieldDev<FL> &fd = vf.fd;
     BatchEncodeArgs e{};
     e.proofs = in.proofs_d;
     e.stream_bytes = in.stream_bytes;
@@ -1740,13 +1788,13 @@ int32_t run_batch_verify_fl(zip_ctx *ctx, const BatchVerifyIn &in, const HostFie
         a.depth = ctx->depth;
         a.n_cols = n_cols;
         a.cw = cw;
-        a.quirk = quirk ? 1u : 0u;
+        a.quirk = vf.quirk;
         a.flags = flags_d;
         a.bad_merkle = bad_d;
         a.malformed = mal_d;
         const uint32_t per_wg = R < 256 ? 256 / R : 1;  // openings per workgroup
         LaunchTimer t(ctx, "batch_verify_columns_kernel");
-        hipLaunchKernelGGL(batch_verify_columns_kernel<FL>, dim3((n_cols + per_wg - 1) / per_wg, B), dim3(256), 0, ctx->stream, a, fd, fq);
+        hipLaunchKernelGGL(batch_verify_columns_kernel<FL>, dim3((n_cols + per_wg - 1) / per_wg, B), dim3(256), 0, ctx->stream, a, fd, vf.fq);
         HIP_TRY(ctx, hipGetLastError());
     }
     {
@@ -2132,13 +2180,6 @@ int32_t ccs_eval_matrices_fl(zip_ccs *c, uint64_t *out_d, const HostField &hf) {
     return ZIP_OK;
 }
 
-#define CCS_DISPATCH_FL(fl, fn, ...)                  \
-    switch (fl) {                                     \
-        case 2: rc = fn<2>(__VA_ARGS__); break;       \
-        case 3: rc = fn<3>(__VA_ARGS__); break;       \
-        default: rc = fn<4>(__VA_ARGS__); break;      \
-    }
-
 int32_t ccs_field(zip_ccs *c, HostField *hf) {
     zip_field zf{};
     zf.limbs = c->fl;
@@ -2168,11 +2209,7 @@ int32_t launch_batch_combine_fl(zip_ctx *ctx, BatchCombineArgs a, uint32_t n_pol
     return ZIP_OK;
 }
 int32_t launch_batch_combine(zip_ctx *ctx, const BatchCombineArgs &a, uint32_t n_polys, bool do_int, const HostField &hf) {
-    switch (hf.fl) {
-        case 2: return launch_batch_combine_fl<2>(ctx, a, n_polys, do_int, hf);
-        case 3: return launch_batch_combine_fl<3>(ctx, a, n_polys, do_int, hf);
-        default: return launch_batch_combine_fl<4>(ctx, a, n_polys, do_int, hf);
-    }
+    return with_fl(hf.fl, [&](auto FL) { return launch_batch_combine_fl<decltype(FL)::value>(ctx, a, n_polys, do_int, hf); });
 }
 }  // namespace
 
@@ -4088,11 +4125,10 @@ int32_t zip_mctx_commit_open(zip_mctx *m, const int64_t *evals, const int64_t *c
         const uint64_t *ua = single ? nullptr : m->uparts_all;
         uint8_t *row_be = m->ends + u_bytes;
         LaunchTimer t(lead, "sum_partials_kernel");
-        switch (fl) {
-            case 2: hipLaunchKernelGGL(sum_partials_kernel<2>, grid, block, 0, lead->stream, ua, m->fparts_all, G, C, ml, up, (uint64_t *)nullptr, to_dev<2>(hf), row_be); break;
-            case 3: hipLaunchKernelGGL(sum_partials_kernel<3>, grid, block, 0, lead->stream, ua, m->fparts_all, G, C, ml, up, (uint64_t *)nullptr, to_dev<3>(hf), row_be); break;
-            default: hipLaunchKernelGGL(sum_partials_kernel<4>, grid, block, 0, lead->stream, ua, m->fparts_all, G, C, ml, up, (uint64_t *)nullptr, to_dev<4>(hf), row_be); break;
-        }
+        with_fl(fl, [&](auto FL) {
+            constexpr int N = decltype(FL)::value;
+            hipLaunchKernelGGL(sum_partials_kernel<N>, grid, block, 0, lead->stream, ua, m->fparts_all, G, C, ml, up, (uint64_t *)nullptr, to_dev<N>(hf), row_be);
+        });
         if (hipGetLastError() != hipSuccess) return finish(mfail(m, ZIP_ERR_HIP, "sum_partials launch failed"));
     }
     m->last_cols = n_cols;
@@ -4145,72 +4181,40 @@ int32_t zip_verify(zip_ctx *ctx, const uint8_t *roots, const uint8_t *proof, zip
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_verify needs an unsharded ctx");
     HostField hf;
     int32_t rc;
-    if ((rc = make_field(ctx, field, &hf))) return rc;
-    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len;
-    const bool single = R == 1;
-    if (!single && (!coeffs || !q0_mont)) return fail(ctx, ZIP_ERR_NULL, "coeffs / q0_mont is NULL");
-    if (C > 1 && !q1_mont) return fail(ctx, ZIP_ERR_NULL, "q1_mont is NULL");
-    if ((rc = check_cols(ctx, cols, n_cols))) return rc;
+    if ((rc = check_verify_args(ctx, coeffs, cols, n_cols, q0_mont, q1_mont, field, &hf))) return rc;
     const size_t need = zip_proof_len(ctx, n_cols, hf.fl);
     if (proof_len < need) {  // the reference runs out of stream: read_* fails (pcs_transcript.rs:125-160)
         report->verdict = ZIP_VERIFY_MALFORMED;
         return ZIP_OK;
     }
     Scratch pbuf(ctx), small(ctx);
-    const uint8_t *proof_d = proof;
-    if (proof_kind == ZIP_MEM_HOST) {
-        if ((rc = pbuf.get(need))) return rc;
-        if ((rc = copy_h2d_bounced(ctx, pbuf.ptr, proof, need, ctx->stream))) return rc;
-        proof_d = pbuf.as<uint8_t>();
-    }
-    // q_1 of a one-column matrix is empty in the reference (pcs/utils.rs:253-276): <row, q1> is then 0
-    SmallInputs si;
-    si.src[0] = coeffs;  si.bytes[0] = single ? 0 : (size_t)R * 8;
-    si.src[1] = q0_mont; si.bytes[1] = single ? 0 : (size_t)R * hf.fl * 8;
-    si.src[2] = cols;    si.bytes[2] = (size_t)n_cols * 4;
-    si.src[3] = q1_mont; si.bytes[3] = C > 1 ? (size_t)C * hf.fl * 8 : 0;
-    si.src[4] = roots;   si.bytes[4] = (size_t)R * 32;
-    unsigned char *sb;
-    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
     VerifyIn in{};
-    in.proof_d = proof_d;
-    in.coeffs_d = reinterpret_cast<const int64_t *>(sb + si.off[0]);
-    in.q0_d = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
-    in.cols_d = reinterpret_cast<const uint32_t *>(sb + si.off[2]);
-    in.q1_d = reinterpret_cast<const uint64_t *>(sb + si.off[3]);
-    in.roots_d = sb + si.off[4];
-    in.n_cols = n_cols;
+    if ((rc = stage_verify_inputs(ctx, 1, need, proof, proof_kind, roots, coeffs, cols, n_cols, q0_mont, q1_mont, nullptr, hf.fl,
+                                  pbuf, small, &in)))
+        return rc;
     std::vector<uint32_t> flags, bad, malformed;
-    VerifyCounters cnt{};
-    switch (hf.fl) {
-        case 2: rc = run_verify_fl<2>(ctx, in, hf, flags, bad, malformed, &cnt); break;
-        case 3: rc = run_verify_fl<3>(ctx, in, hf, flags, bad, malformed, &cnt); break;
-        default: rc = run_verify_fl<4>(ctx, in, hf, flags, bad, malformed, &cnt); break;
-    }
-    if (rc) return rc;
+    VerifyHead cnt{};
+    if ((rc = with_fl(hf.fl, [&](auto FL) { return run_verify_fl<decltype(FL)::value>(ctx, in, hf, flags, bad, malformed, &cnt); })))
+        return rc;
+    VerifyFacts x{};
+    x.overflow = cnt.overflow != 0;
+    x.first = x.first_q0 = kNoOpening;
     for (uint32_t i = 0; i < n_cols; i++) {
         report->bad_merkle_paths += bad[i];
         report->malformed_paths += malformed[i];
+        const uint32_t why = opening_fails(flags[i], malformed[i], bad[i]);
+        if (why && x.first == kNoOpening) {
+            x.first = i;
+            x.first_why = why;
+        }
+        if ((flags[i] & 2u) && x.first_q0 == kNoOpening) x.first_q0 = i;
     }
-    // first failing check in the reference's order (verify_z.rs:60-163)
-    if (cnt.overflow) { report->verdict = ZIP_VERIFY_OVERFLOW; return ZIP_OK; }
-    for (uint32_t i = 0; i < n_cols; i++) {
-        if (flags[i] & 1u) { report->verdict = ZIP_VERIFY_PROXIMITY_TESTING; report->column = i; return ZIP_OK; }
-        if (malformed[i]) { report->verdict = ZIP_VERIFY_MALFORMED; report->column = i; return ZIP_OK; }
-        if (bad[i]) { report->verdict = ZIP_VERIFY_MERKLE; report->column = i; return ZIP_OK; }
-    }
-    // <row, q1> is a Montgomery product per element and therefore well defined for elements >= q too:
-    // the consistency check comes first, as in the reference (verify_z.rs:145-149)
-    if (C > 1 ? memcmp(cnt.dot, eval_mont, 8 * hf.fl) != 0 : [&] {
-            for (uint32_t i = 0; i < hf.fl; i++) if (eval_mont[i]) return true;
-            return false; }()) {
-        report->verdict = ZIP_VERIFY_EVAL_CONSISTENCY;
-        return ZIP_OK;
-    }
-    if (cnt.noncanonical) { report->verdict = ZIP_VERIFY_MALFORMED; return ZIP_OK; }
-    for (uint32_t i = 0; i < n_cols; i++)
-        if (flags[i] & 2u) { report->verdict = ZIP_VERIFY_PROXIMITY_Q0; report->column = i; return ZIP_OK; }
-    report->verdict = ZIP_VERIFY_ACCEPT;
+    // <row, q1> is a Montgomery product per element and therefore well defined for elements >= q too; it is 0 for a
+    // one-column matrix
+    const uint64_t zero[4] = {0, 0, 0, 0};
+    x.eval_differs = memcmp(ctx->p.row_len > 1 ? cnt.dot : zero, eval_mont, 8 * hf.fl) != 0;
+    x.noncanonical = cnt.noncanonical != 0;
+    verify_verdict(x, *report);
     return ZIP_OK;
 }
 
@@ -4222,7 +4226,7 @@ int32_t zip_batch_verify(zip_ctx *ctx, uint32_t n_polys, const uint8_t *roots, c
                          const uint64_t *q1_mont, const uint64_t *evals_mont, const zip_field *field, zip_verify_report *reports) {
     if (!ctx || !roots || !proofs || !reports || !evals_mont || (n_cols && !cols)) return ZIP_ERR_NULL;
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
-    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len;
+    const uint32_t R = ctx->p.num_rows, cw = ctx->p.codeword_len;
     if (n_polys == 0 || n_polys > 65535)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "a batch holds 1 .. 65535 polynomials (got %u)", n_polys);
     if (ctx->rows_local != R) return fail(ctx, ZIP_ERR_INVALID_PARAM, "batches need an unsharded ctx");
@@ -4233,11 +4237,7 @@ int32_t zip_batch_verify(zip_ctx *ctx, uint32_t n_polys, const uint8_t *roots, c
         return fail(ctx, ZIP_ERR_UNSUPPORTED, "%u x %u openings exceed 2^32", n_polys, n_cols);
     HostField hf;
     int32_t rc;
-    if ((rc = make_field(ctx, field, &hf))) return rc;
-    const bool single = R == 1;
-    if (!single && (!coeffs || !q0_mont)) return fail(ctx, ZIP_ERR_NULL, "coeffs / q0_mont is NULL");
-    if (C > 1 && !q1_mont) return fail(ctx, ZIP_ERR_NULL, "q1_mont is NULL");
-    if ((rc = check_cols(ctx, cols, n_polys * n_cols))) return rc;
+    if ((rc = check_verify_args(ctx, coeffs, cols, n_polys * n_cols, q0_mont, q1_mont, field, &hf))) return rc;
     memset(reports, 0, (size_t)n_polys * sizeof *reports);
     // the reference runs out of stream in the first polynomial that is not all there (pcs_transcript.rs:125-160)
     const size_t len = zip_proof_len(ctx, n_cols, hf.fl);
@@ -4246,38 +4246,12 @@ int32_t zip_batch_verify(zip_ctx *ctx, uint32_t n_polys, const uint8_t *roots, c
     if (k == 0) return ZIP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Scratch pbuf(ctx), small(ctx);
-    const uint8_t *proofs_d = proofs;
-    if (proofs_kind == ZIP_MEM_HOST) {
-        if ((rc = pbuf.get((size_t)k * len))) return rc;
-        if ((rc = copy_h2d_bounced(ctx, pbuf.ptr, proofs, (size_t)k * len, ctx->stream))) return rc;
-        proofs_d = pbuf.as<uint8_t>();
-    }
-    SmallInputs si;
-    si.src[0] = coeffs;     si.bytes[0] = single ? 0 : (size_t)k * R * 8;
-    si.src[1] = q0_mont;    si.bytes[1] = single ? 0 : (size_t)k * R * hf.fl * 8;
-    si.src[2] = cols;       si.bytes[2] = (size_t)k * n_cols * 4;
-    si.src[3] = q1_mont;    si.bytes[3] = C > 1 ? (size_t)k * C * hf.fl * 8 : 0;
-    si.src[4] = roots;      si.bytes[4] = (size_t)k * R * 32;
-    si.src[5] = evals_mont; si.bytes[5] = (size_t)k * hf.fl * 8;
-    unsigned char *sb;
-    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
-    BatchVerifyIn in{};
-    in.proofs_d = proofs_d;
-    in.stream_bytes = len;
-    in.coeffs_d = reinterpret_cast<const int64_t *>(sb + si.off[0]);
-    in.q0_d = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
-    in.cols_d = reinterpret_cast<const uint32_t *>(sb + si.off[2]);
-    in.q1_d = reinterpret_cast<const uint64_t *>(sb + si.off[3]);
-    in.roots_d = sb + si.off[4];
-    in.evals_d = reinterpret_cast<const uint64_t *>(sb + si.off[5]);
-    in.n_cols = n_cols;
-    in.n_polys = k;
+    VerifyIn in{};
+    if ((rc = stage_verify_inputs(ctx, k, len, proofs, proofs_kind, roots, coeffs, cols, n_cols, q0_mont, q1_mont, evals_mont, hf.fl,
+                                  pbuf, small, &in)))
+        return rc;
     g_batch_verify_calls++;
-    switch (hf.fl) {
-        case 2: return run_batch_verify_fl<2>(ctx, in, hf, reports);
-        case 3: return run_batch_verify_fl<3>(ctx, in, hf, reports);
-        default: return run_batch_verify_fl<4>(ctx, in, hf, reports);
-    }
+    return with_fl(hf.fl, [&](auto FL) { return run_batch_verify_fl<decltype(FL)::value>(ctx, in, hf, reports); });
 }
 
 uint64_t zip_batch_verify_calls(void) { return g_batch_verify_calls.load(); }
@@ -4325,11 +4299,10 @@ int32_t zip_mle_eval(zip_ctx *ctx, const int64_t *evals, zip_mem_kind evals_kind
     {
         LaunchTimer t(ctx, "field_dot_kernel");
         const uint64_t *q1d = reinterpret_cast<const uint64_t *>(sb + si.off[3]);
-        switch (hf.fl) {
-            case 2: hipLaunchKernelGGL(field_dot_kernel<2>, dim3(1), dim3(1024), 0, ctx->stream, o.row_limbs, q1d, C, res.as<uint64_t>(), to_dev<2>(hf)); break;
-            case 3: hipLaunchKernelGGL(field_dot_kernel<3>, dim3(1), dim3(1024), 0, ctx->stream, o.row_limbs, q1d, C, res.as<uint64_t>(), to_dev<3>(hf)); break;
-            default: hipLaunchKernelGGL(field_dot_kernel<4>, dim3(1), dim3(1024), 0, ctx->stream, o.row_limbs, q1d, C, res.as<uint64_t>(), to_dev<4>(hf)); break;
-        }
+        with_fl(hf.fl, [&](auto FL) {
+            constexpr int N = decltype(FL)::value;
+            hipLaunchKernelGGL(field_dot_kernel<N>, dim3(1), dim3(1024), 0, ctx->stream, o.row_limbs, q1d, C, res.as<uint64_t>(), to_dev<N>(hf));
+        });
         HIP_TRY(ctx, hipGetLastError());
     }
     return deliver(ctx, value_out, ZIP_MEM_HOST, res.ptr, (size_t)hf.fl * 8);
@@ -4339,20 +4312,19 @@ int32_t zip_field_map_int256(zip_ctx *ctx, const uint64_t *values, uint32_t n, c
     if (!ctx || !values || !out) return ZIP_ERR_NULL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
-    HostField hf, hq;
+    HostField hf;
     int32_t rc;
     if ((rc = make_field(ctx, field, &hf))) return rc;
-    const bool quirk = make_quirk_field(hf, &hq);
     Scratch in(ctx), res(ctx);
     if ((rc = in.get((size_t)n * 32 + 16))) return rc;
     if ((rc = res.get((size_t)n * hf.fl * 8 + 16))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(in.ptr, values, (size_t)n * 32, hipMemcpyHostToDevice, ctx->stream));
     const dim3 grid((n + 255) / 256), block(256);
-    switch (hf.fl) {
-        case 2: hipLaunchKernelGGL(field_map_int256_kernel<2>, grid, block, 0, ctx->stream, in.as<uint64_t>(), n, res.as<uint64_t>(), to_dev<2>(hf), to_dev<2>(hf), 0u); break;
-        case 3: hipLaunchKernelGGL(field_map_int256_kernel<3>, grid, block, 0, ctx->stream, in.as<uint64_t>(), n, res.as<uint64_t>(), to_dev<3>(hf), to_dev<3>(hf), 0u); break;
-        default: hipLaunchKernelGGL(field_map_int256_kernel<4>, grid, block, 0, ctx->stream, in.as<uint64_t>(), n, res.as<uint64_t>(), to_dev<4>(hf), quirk ? to_dev<4>(hq) : to_dev<4>(hf), quirk ? 1u : 0u); break;
-    }
+    with_fl(hf.fl, [&](auto FL) {
+        constexpr int N = decltype(FL)::value;
+        const VerifyField<N> vf = verify_field<N>(hf);
+        hipLaunchKernelGGL(field_map_int256_kernel<N>, grid, block, 0, ctx->stream, in.as<uint64_t>(), n, res.as<uint64_t>(), vf.fd, vf.fq, vf.quirk);
+    });
     HIP_TRY(ctx, hipGetLastError());
     return deliver(ctx, out, ZIP_MEM_HOST, res.ptr, (size_t)n * hf.fl * 8);
 }
@@ -4560,13 +4532,7 @@ int32_t zip_sumcheck_round_begin(zip_sumcheck *s, const uint64_t *r_prev) {
     memcpy(hf.r, s->mont_r, sizeof hf.r);
     memcpy(hf.r2, s->mont_r2, sizeof hf.r2);
     hf.inv = s->mont_inv;
-    int32_t rc;
-    switch (s->fl) {
-        case 2: rc = sumcheck_round_fl<2>(s, r_prev, hf); break;
-        case 3: rc = sumcheck_round_fl<3>(s, r_prev, hf); break;
-        default: rc = sumcheck_round_fl<4>(s, r_prev, hf); break;
-    }
-    if (rc) return rc;
+    if (int32_t rc = with_fl(s->fl, [&](auto FL) { return sumcheck_round_fl<decltype(FL)::value>(s, r_prev, hf); })) return rc;
     g_sumcheck_round_launches++;
     s->round++;
     s->pending = true;
@@ -4622,12 +4588,7 @@ int32_t zip_sumcheck_prove(zip_sumcheck *s, zip_keccak_state *transcript, uint64
     memcpy(hf.r2, s->mont_r2, sizeof hf.r2);
     hf.inv = s->mont_inv;
     s->proved = true;  // whatever happens from here on, the handle does not start over
-    int32_t rc;
-    switch (s->fl) {
-        case 2: rc = sumcheck_prove_fl<2>(s, transcript, msgs_out, randomness_out, hf); break;
-        case 3: rc = sumcheck_prove_fl<3>(s, transcript, msgs_out, randomness_out, hf); break;
-        default: rc = sumcheck_prove_fl<4>(s, transcript, msgs_out, randomness_out, hf); break;
-    }
+    const int32_t rc = with_fl(s->fl, [&](auto FL) { return sumcheck_prove_fl<decltype(FL)::value>(s, transcript, msgs_out, randomness_out, hf); });
     if (rc) s->round = s->num_vars;
     return rc;
 }
@@ -4715,7 +4676,7 @@ int32_t zip_ccs_create(int32_t device, const zip_sparse_matrix *mats, uint32_t t
                 if ((rc = copy_h2d_bounced(ctx, D.col_idx, M.col_idx, (size_t)nnz * 4, ctx->stream))) break;
                 // SparseMatrix::map_to_field (sparse_matrix.rs:38-58)
                 if ((rc = copy_h2d_bounced(ctx, tmp, M.values, (size_t)nnz * 8, ctx->stream))) break;
-                CCS_DISPATCH_FL(hf.fl, ccs_map_i64, ctx, static_cast<const int64_t *>(tmp), nnz, nnz, D.vals, hf);
+                rc = with_fl(hf.fl, [&](auto FL) { return ccs_map_i64<decltype(FL)::value>(ctx, static_cast<const int64_t *>(tmp), nnz, nnz, D.vals, hf); });
                 if (rc) break;
                 const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)nnz + 255) / 256, 65535);
                 hipLaunchKernelGGL(csc_count_kernel, dim3(blocks), dim3(256), 0, ctx->stream, D.col_idx, nnz, D.col_ptr);
@@ -4729,11 +4690,9 @@ int32_t zip_ccs_create(int32_t device, const zip_sparse_matrix *mats, uint32_t t
             if (hipMemcpyAsync(cursor, D.col_ptr, (size_t)n_cnt * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
             if (nnz) {
                 const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)M.n_rows + 255) / 256, 65535);
-                switch (hf.fl) {
-                    case 2: hipLaunchKernelGGL(csc_fill_kernel<2>, dim3(blocks), dim3(256), 0, ctx->stream, D.row_ptr, D.col_idx, D.vals, M.n_rows, static_cast<uint32_t *>(cursor), D.row_idx, D.vals_t); break;
-                    case 3: hipLaunchKernelGGL(csc_fill_kernel<3>, dim3(blocks), dim3(256), 0, ctx->stream, D.row_ptr, D.col_idx, D.vals, M.n_rows, static_cast<uint32_t *>(cursor), D.row_idx, D.vals_t); break;
-                    default: hipLaunchKernelGGL(csc_fill_kernel<4>, dim3(blocks), dim3(256), 0, ctx->stream, D.row_ptr, D.col_idx, D.vals, M.n_rows, static_cast<uint32_t *>(cursor), D.row_idx, D.vals_t); break;
-                }
+                with_fl(hf.fl, [&](auto FL) {
+                    hipLaunchKernelGGL(csc_fill_kernel<decltype(FL)::value>, dim3(blocks), dim3(256), 0, ctx->stream, D.row_ptr, D.col_idx, D.vals, M.n_rows, static_cast<uint32_t *>(cursor), D.row_idx, D.vals_t);
+                });
             }
             if (hipGetLastError() != hipSuccess || stream_wait(ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
             pool_release(ctx, tmp);
@@ -4785,8 +4744,7 @@ int32_t zip_ccs_set_z(zip_ccs *c, const int64_t *z, size_t z_len, zip_mem_kind k
         if ((rc = copy_h2d_bounced(ctx, in.ptr, z, z_len * 8, ctx->stream))) return rc;
         z_d = in.as<int64_t>();
     }
-    CCS_DISPATCH_FL(c->fl, ccs_set_z_fl, c, z_d, z_len, hf);
-    if (rc) return rc;
+    if ((rc = with_fl(c->fl, [&](auto FL) { return ccs_set_z_fl<decltype(FL)::value>(c, z_d, z_len, hf); }))) return rc;
     HIP_TRY(ctx, stream_wait(ctx->stream));
     c->have_z = true;
     c->have_second = false;
@@ -4803,8 +4761,7 @@ int32_t zip_ccs_eq_table(zip_ccs *c, const uint64_t *r, uint32_t slot) {
     int32_t rc;
     if ((rc = ccs_field(c, &hf))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(c->small_d, r, (size_t)c->s * c->fl * 8, hipMemcpyHostToDevice, ctx->stream));
-    CCS_DISPATCH_FL(c->fl, ccs_eq_table_fl, c, c->small_d, slot, hf);
-    if (rc) return rc;
+    if ((rc = with_fl(c->fl, [&](auto FL) { return ccs_eq_table_fl<decltype(FL)::value>(c, c->small_d, slot, hf); }))) return rc;
     HIP_TRY(ctx, stream_wait(ctx->stream));
     c->have_eq[slot] = true;
     return ZIP_OK;
@@ -4822,8 +4779,7 @@ int32_t zip_ccs_second_table(zip_ccs *c, const uint64_t *r_x, const uint64_t *ga
     if ((rc = ccs_field(c, &hf))) return rc;
     uint64_t *gamma_d = c->small_d + (size_t)32 * 8, *vs_d = c->small_d + (size_t)33 * 8;
     HIP_TRY(ctx, hipMemcpyAsync(gamma_d, gamma, (size_t)c->fl * 8, hipMemcpyHostToDevice, ctx->stream));
-    CCS_DISPATCH_FL(c->fl, ccs_second_fl, c, gamma_d, vs_d, hf);
-    if (rc) return rc;
+    if ((rc = with_fl(c->fl, [&](auto FL) { return ccs_second_fl<decltype(FL)::value>(c, gamma_d, vs_d, hf); }))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(v_s_out, vs_d, (size_t)c->t * c->fl * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, stream_wait(ctx->stream));
     c->have_second = true;
@@ -4842,8 +4798,7 @@ int32_t zip_ccs_eval_matrices(zip_ccs *c, const uint64_t *r_x, const uint64_t *r
     HostField hf;
     if ((rc = ccs_field(c, &hf))) return rc;
     uint64_t *out_d = c->small_d + (size_t)33 * 8;
-    CCS_DISPATCH_FL(c->fl, ccs_eval_matrices_fl, c, out_d, hf);
-    if (rc) return rc;
+    if ((rc = with_fl(c->fl, [&](auto FL) { return ccs_eval_matrices_fl<decltype(FL)::value>(c, out_d, hf); }))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(v_xy_out, out_d, (size_t)c->t * c->fl * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, stream_wait(ctx->stream));
     return ZIP_OK;
@@ -4898,20 +4853,11 @@ int32_t zip_sum_partials(zip_ctx *ctx, const uint64_t *uparts, const uint64_t *f
     const uint32_t C = ctx->p.row_len;
     const dim3 grid((C + 255) / 256), block(256);
     LaunchTimer t(ctx, "sum_partials_kernel");
-    switch (hf.fl) {
-        case 2:
-            hipLaunchKernelGGL(sum_partials_kernel<2>, grid, block, 0, ctx->stream, uparts, fparts, n_parts, C,
-                               ctx->p.m_limbs, uprime_out, row_out, to_dev<2>(hf));
-            break;
-        case 3:
-            hipLaunchKernelGGL(sum_partials_kernel<3>, grid, block, 0, ctx->stream, uparts, fparts, n_parts, C,
-                               ctx->p.m_limbs, uprime_out, row_out, to_dev<3>(hf));
-            break;
-        default:
-            hipLaunchKernelGGL(sum_partials_kernel<4>, grid, block, 0, ctx->stream, uparts, fparts, n_parts, C,
-                               ctx->p.m_limbs, uprime_out, row_out, to_dev<4>(hf));
-            break;
-    }
+    with_fl(hf.fl, [&](auto FL) {
+        constexpr int N = decltype(FL)::value;
+        hipLaunchKernelGGL(sum_partials_kernel<N>, grid, block, 0, ctx->stream, uparts, fparts, n_parts, C,
+                           ctx->p.m_limbs, uprime_out, row_out, to_dev<N>(hf));
+    });
     HIP_TRY(ctx, hipGetLastError());
     return ZIP_OK;
 }
