@@ -42,6 +42,20 @@ int32_t zinc_transcript_get_challenge(zinc_transcript *t, const uint64_t *modulu
 int32_t zinc_transcript_export(const zinc_transcript *t, uint64_t *st, uint8_t *buf, uint32_t *buflen);
 int32_t zinc_transcript_import(zinc_transcript *t, const uint64_t *st, const uint8_t *buf, uint32_t buflen);
 
+/* The random field.  zinc_get_prime: prime_gen::get_prime::<RandomField<limbs>> (src/prime_gen.rs:15-28), limbs in
+ * {2, 3, 4}: the candidate chain on the host, the primality tests of a batch of candidates in one launch on the device
+ * (zip_hip.h); the transcript ends where the reference's loop leaves it.  prime_out: limbs little-endian limbs;
+ * candidates_tried_out (may be NULL): the winner's 1-based position in the chain.
+ * zinc_draw_random_field: draw_random_field (src/zinc/utils.rs:161-171) with I = Int<1> -- every public input absorbed
+ * as its 8 little-endian bytes, then get_prime -> modulus_out, the modulus of the FieldConfig (limbs limbs).
+ * ZINC_ERR_INVALID_PARAM for other limb counts, ZINC_ERR_DEVICE when the device call fails (there is no host path).
+ * ZINC_ERR_FIELD_CONFIG is ZincError::FieldConfigError: what Verifier::verify returns (src/zinc/verifier.rs:53-57) when
+ * the field it draws this way is not the configuration it was handed. */
+#define ZINC_ERR_FIELD_CONFIG (-7)
+int32_t zinc_get_prime(zinc_transcript *t, uint32_t limbs, int32_t device, uint64_t *prime_out, uint32_t *candidates_tried_out);
+int32_t zinc_draw_random_field(const int64_t *public_input, size_t l, zinc_transcript *t, uint32_t limbs, int32_t device,
+                               uint64_t *modulus_out);
+
 /* field helpers (src/field/config.rs, src/conversion.rs, src/sumcheck/utils.rs) */
 int32_t zinc_field_constants(const uint64_t *modulus, uint32_t limbs, uint64_t *r, uint64_t *r2, uint64_t *inv);
 int32_t zinc_field_mul(const uint64_t *modulus, uint32_t limbs, const uint64_t *a, const uint64_t *b, uint64_t *out);
@@ -236,7 +250,8 @@ int32_t zinc_prover_prove(const zip_sparse_matrix *constraints, uint32_t t, uint
 
 /* ZincVerifier (src/zinc/verifier.rs): SpartanVerifier::verify (:105-139), and with with_pcs != 0 also
  * verify_pcs_proof (:221-273: RaaCode::new from the transcript, MultilinearZip::verify, the matrix MLEs at
- * (r_x, r_y) on the device, the final equation) -- Verifier::verify without its draw_random_field check.
+ * (r_x, r_y) on the device, the final equation) -- Verifier::verify without its draw_random_field check (with it:
+ * the _checked entry below).
  * Proof fields as zinc_prover_prove returns them.  rx_ry_out: 2 s elements; e_y_out, gamma_out: one element (any
  * may be NULL).  ZINC_ERR_SPARTAN: a sumcheck or the final equation failed; ZINC_ERR_INVALID_OPEN: the Zip
  * verifier rejected; zinc_last_error() has the message. */
@@ -246,6 +261,17 @@ int32_t zinc_verifier_verify(const zip_sparse_matrix *constraints, uint32_t t, u
                              const uint64_t *msgs2, const uint64_t *v_s, int32_t with_pcs, const uint8_t *roots,
                              size_t n_roots, const uint64_t *v, const uint8_t *pcs_proof, size_t pcs_proof_len,
                              uint64_t *rx_ry_out, uint64_t *e_y_out, uint64_t *gamma_out);
+/* The same with the check Verifier::verify starts with (src/zinc/verifier.rs:53-57) when check_field != 0: the field
+ * is drawn from the l public inputs on `transcript` (zinc_draw_random_field above) and must be `modulus`, else
+ * ZINC_ERR_FIELD_CONFIG before any other work; the verification then continues on that transcript.  check_field == 0:
+ * zinc_verifier_verify, the public input is not read. */
+int32_t zinc_verifier_verify_checked(const int64_t *public_input, size_t l, int32_t check_field,
+                                     const zip_sparse_matrix *constraints, uint32_t t, uint32_t s, uint32_t d, uint32_t q,
+                                     const uint32_t *s_masks, const int64_t *c, zinc_transcript *transcript,
+                                     const uint64_t *modulus, uint32_t limbs, int32_t device, zinc_prepared_ccs *prepared,
+                                     const uint64_t *msgs1, const uint64_t *msgs2, const uint64_t *v_s, int32_t with_pcs,
+                                     const uint8_t *roots, size_t n_roots, const uint64_t *v, const uint8_t *pcs_proof,
+                                     size_t pcs_proof_len, uint64_t *rx_ry_out, uint64_t *e_y_out, uint64_t *gamma_out);
 
 #ifdef __cplusplus
 }

@@ -43,7 +43,7 @@ extern "C" {
  * changed, so the version stays 3; a caller that needs them looks the symbol up.  Likewise zip_sumcheck_init taking
  * up to 8 tables instead of 4: a widening, every call that was valid means what it meant.  The batch entry points,
  * zip_batch_commit and the five beside it, are additive in the same way, and so are zip_batch_verify and
- * zip_batch_verify_calls.) */
+ * zip_batch_verify_calls.  So are zip_prime_test_base2, zip_get_prime and zip_prime_launch_counts.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -442,6 +442,39 @@ int32_t zip_sumcheck_prove(zip_sumcheck *s, zip_keccak_state *transcript, uint64
  * point) and launches of the tail kernel.  Every path gives the same bytes; tests and tools read the path taken here.
  * Either pointer may be NULL. */
 void zip_sumcheck_launch_counts(uint64_t *round_kernel_rounds, uint64_t *tail_kernel_launches);
+
+/* ---- the random field: prime_gen::get_prime (src/prime_gen.rs:15-28) ---------------------------------------------
+ * draw_random_field (src/zinc/utils.rs:161-171) absorbs the public inputs and calls get_prime: hash a candidate of
+ * 8 * limbs bytes out of the transcript (get_random_bytes: one squeeze with the 4-byte big-endian counter 0,
+ * truncated), absorb those bytes, read them big-endian, subtract 1 if even, and repeat until
+ * MillerRabin::test_base_two (src/field/uint.rs:66-76) accepts one.  The hash chain does not depend on the tests, and
+ * the tests are independent modular exponentiations: the host hashes candidates in batches, the device tests a batch in
+ * ONE launch with one candidate per lane, and the next batch is hashed while the current one is on the device.
+ *
+ * zip_prime_test_base2: the strong probable-prime test to base 2 of n candidates of `limbs` limbs each (HOST,
+ * candidate-major, little-endian limbs; any odd value >= 3 up to 2^(64 limbs) - 1) -> verdicts_out (HOST, n bytes,
+ * 1 = probably prime).  What the reference's test accepts is accepted: strong pseudoprimes to base 2 included.
+ *   ZIP_ERR_NULL           candidates or verdicts_out is NULL
+ *   ZIP_ERR_INVALID_PARAM  limbs not in {2, 3, 4}, n == 0, an even candidate or one below 3 -- nothing reaches the device
+ *
+ * zip_get_prime: get_prime::<RandomField<limbs>> on the caller's transcript.  For this call the library owns the
+ * transcript (as zip_sumcheck_prove does for a sumcheck): on return *transcript is exactly what the reference's loop
+ * leaves -- the sponge after absorbing the winner's bytes, nothing of the candidates hashed ahead beyond it.
+ *   prime_out             HOST, `limbs` little-endian limbs: the first candidate the test accepts
+ *   candidates_tried_out  the winner's 1-based position in the chain; may be NULL
+ *   ZIP_ERR_NULL           transcript or prime_out is NULL
+ *   ZIP_ERR_INVALID_PARAM  limbs not in {2, 3, 4}, buflen >= 136 -- before the device is touched
+ *   ZIP_ERR_UNSUPPORTED    no candidate among the first 65536 was accepted (one line on stderr says so).  The reference
+ *                          would loop for ever; the primes of 128 .. 256 bits are dense enough that this is a defect
+ *                          of the device, not of the input.  *transcript is then unchanged.
+ * ZIP_HIP_PRIME_BATCH=n (1 .. 4096) sets the candidates per launch; read per call.
+ *
+ * zip_prime_launch_counts: process-wide, monotonic -- launches of the test kernel (from either entry point) and the
+ * candidates they tested, kept like zip_batch_verify_calls.  Either pointer may be NULL. */
+int32_t zip_prime_test_base2(int32_t device, const uint64_t *candidates, uint32_t n, uint32_t limbs, uint8_t *verdicts_out);
+int32_t zip_get_prime(int32_t device, zip_keccak_state *transcript, uint32_t limbs, uint64_t *prime_out,
+                      uint32_t *candidates_tried_out);
+void zip_prime_launch_counts(uint64_t *launches, uint64_t *candidates_tested);
 
 /* ---- the field loops of SpartanProver::prove around its sumchecks (BASELINE configs[4]) ---------
  * A zip_ccs holds the constraint matrices of a CCS (Statement_Z.constraints, src/ccs/ccs_z.rs:155-158,

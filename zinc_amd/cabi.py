@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "zip_ccs_second_table", "zip_ccs_table", "zip_ccs_download", "zip_ccs_eval_matrices",
     "zip_batch_commit", "zip_batch_size", "zip_batch_free", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open",
     "zip_batch_verify", "zip_batch_verify_calls",
+    "zip_prime_test_base2", "zip_get_prime", "zip_prime_launch_counts",
 )
 
 
@@ -226,6 +227,12 @@ def lib():
     L.zip_sumcheck_prove.argtypes = [vp, C.POINTER(KeccakState), u64p, u64p]
     L.zip_sumcheck_launch_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.zip_sumcheck_launch_counts.restype = None
+    L.zip_prime_test_base2.argtypes = [C.c_int32, u64p, C.c_uint32, C.c_uint32, u8p]
+    L.zip_prime_test_base2.restype = C.c_int32
+    L.zip_get_prime.argtypes = [C.c_int32, C.POINTER(KeccakState), C.c_uint32, u64p, C.POINTER(C.c_uint32)]
+    L.zip_get_prime.restype = C.c_int32
+    L.zip_prime_launch_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.zip_prime_launch_counts.restype = None
     L.zip_sumcheck_last_error.argtypes = [vp]
     L.zip_sumcheck_last_error.restype = C.c_char_p
     L.zip_sumcheck_free.argtypes = [vp]
@@ -882,6 +889,40 @@ def sumcheck_launch_counts():
     """(rounds played through the round kernels, launches of the sumcheck tail kernel) in this process so far"""
     a, b = C.c_uint64(0), C.c_uint64(0)
     lib().zip_sumcheck_launch_counts(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def prime_test_base2(candidates, limbs: int, device: int = 0) -> np.ndarray:
+    """zip_prime_test_base2: the strong probable-prime test to base 2 (MillerRabin::test_base_two) of every candidate,
+    one per lane.  candidates: Python ints (odd, >= 3, below 2^(64 limbs)) or a [n, limbs] uint64 array of little-endian
+    limbs.  -> n verdict bytes, 1 = probably prime."""
+    if isinstance(candidates, np.ndarray):
+        c = np.ascontiguousarray(candidates, dtype=np.uint64).reshape(-1, limbs)
+    else:
+        c = np.array([[(int(v) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(limbs)] for v in candidates],
+                     dtype=np.uint64).reshape(-1, limbs)
+    out = np.zeros(c.shape[0], dtype=np.uint8)
+    rc = lib().zip_prime_test_base2(device, c.ctypes.data, c.shape[0], limbs, out.ctypes.data)
+    if rc != ZIP_OK:
+        raise ZipError(rc, "zip_prime_test_base2")
+    return out
+
+
+def get_prime(state: "KeccakState", limbs: int, device: int = 0):
+    """zip_get_prime: prime_gen::get_prime on the transcript in `state`, which is updated in place to what the
+    reference's loop leaves.  -> (the prime as a Python int, the winner's 1-based position in the candidate chain)."""
+    prime = np.zeros(limbs, dtype=np.uint64)
+    tried = C.c_uint32(0)
+    rc = lib().zip_get_prime(device, C.byref(state), limbs, prime.ctypes.data, C.byref(tried))
+    if rc != ZIP_OK:
+        raise ZipError(rc, "zip_get_prime")
+    return sum(int(w) << (64 * i) for i, w in enumerate(prime)), tried.value
+
+
+def prime_launch_counts():
+    """(launches of the primality-test kernel, candidates they tested) in this process so far"""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    lib().zip_prime_launch_counts(C.byref(a), C.byref(b))
     return a.value, b.value
 
 

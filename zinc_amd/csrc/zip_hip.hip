@@ -34,6 +34,7 @@
 #include "kernels_sumcheck_tail.cuh"
 #include "kernels_sumcheck_wide.cuh"
 #include "kernels_spartan.cuh"
+#include "kernels_prime.cuh"
 #include "rccl_dyn.h"
 
 using namespace zipk;
@@ -2083,6 +2084,147 @@ int32_t sumcheck_prove_fl(zip_sumcheck *s, zip_keccak_state *transcript, uint64_
     return ZIP_OK;
 }
 
+// ---- zip_get_prime / zip_prime_test_base2: prime_gen::get_prime (src/prime_gen.rs:15-28) -------------------------------
+// The candidate chain (prime_next_candidate, prime_dev.cuh) does not depend on any verdict, so this thread hashes a
+// batch ahead, hands it to prime_test_base2_kernel -- one candidate per lane -- and hashes the next batch while that one
+// is on the device.  Per candidate it keeps the sponge as the reference's loop holds it when it tests that candidate:
+// the call ends with the winner's, and nothing of the candidates speculated beyond it is left.
+// Per device, made at the first call and kept: a stream, and two slots (the batch in flight and the batch being hashed)
+// of pinned host and of device memory, each [kPrimeMaxBatch candidates of 4 limbs | kPrimeMaxBatch verdict bytes].
+constexpr uint32_t kPrimeMaxBatch = 4096, kPrimeMaxCandidates = 65536;
+// (the default width: the lowest SUM of the three per-limb-count medians of the zip_get_prime time over the twelve
+// transcripts of profiles/prime_gen.md -- 64 has the lower median at 2 and 3 limbs, 128 at 4 limbs and on the sum)
+constexpr uint32_t kPrimeDefaultBatch = 128;
+constexpr size_t kPrimeVerdictsAt = (size_t)kPrimeMaxBatch * 4 * 8, kPrimeSlotBytes = kPrimeVerdictsAt + kPrimeMaxBatch;
+struct PrimeDev {
+    std::mutex mu;  // one call at a time per device
+    hipStream_t stream = nullptr;
+    unsigned char *host = nullptr, *dev = nullptr;
+};
+PrimeDev g_prime[kMaxDevices];
+// Process-wide (zip_prime_launch_counts): launches of prime_test_base2_kernel and the candidates they tested
+std::atomic<uint64_t> g_prime_launches{0}, g_prime_candidates{0};
+
+// zip_prime_test_base2 / zip_get_prime take a device ordinal, not a ctx: the calling thread's current device is put
+// back when they return
+struct CurrentDeviceGuard {
+    int prev = -1;
+    CurrentDeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
+    ~CurrentDeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+// a failed enqueue or wait: nothing of this call may still be queued on the slots the next call reuses
+int32_t prime_fail_drained(PrimeDev &pd) {
+    (void)hipStreamSynchronize(pd.stream);
+    return ZIP_ERR_HIP;
+}
+
+int32_t prime_dev_ready(PrimeDev &pd, int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev || device >= kMaxDevices) return ZIP_ERR_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
+    if (!pd.stream && hipStreamCreateWithFlags(&pd.stream, hipStreamNonBlocking) != hipSuccess) {
+        pd.stream = nullptr;
+        return ZIP_ERR_HIP;
+    }
+    if (!pd.host && hipHostMalloc((void **)&pd.host, 2 * kPrimeSlotBytes, hipHostMallocDefault) != hipSuccess) {
+        pd.host = nullptr;
+        return ZIP_ERR_ALLOC;
+    }
+    if (!pd.dev && hipMalloc((void **)&pd.dev, 2 * kPrimeSlotBytes) != hipSuccess) {
+        pd.dev = nullptr;
+        return ZIP_ERR_ALLOC;
+    }
+    return ZIP_OK;
+}
+void prime_dev_release(int device) {  // (the device is current)
+    PrimeDev &pd = g_prime[device];
+    std::lock_guard<std::mutex> g(pd.mu);
+    if (pd.stream) (void)hipStreamSynchronize(pd.stream);
+    if (pd.dev) (void)hipFree(pd.dev);
+    if (pd.host) (void)hipHostFree(pd.host);
+    if (pd.stream) (void)hipStreamDestroy(pd.stream);
+    pd.dev = pd.host = nullptr;
+    pd.stream = nullptr;
+}
+
+// the n <= kPrimeMaxBatch candidates in the host half of `slot`: up, one launch, the verdicts down -- enqueued, not waited for
+template <int FL>
+hipError_t prime_enqueue(PrimeDev &pd, uint32_t slot, uint32_t n) {
+    unsigned char *h = pd.host + slot * kPrimeSlotBytes, *d = pd.dev + slot * kPrimeSlotBytes;
+    hipError_t e = hipMemcpyAsync(d, h, (size_t)n * FL * 8, hipMemcpyHostToDevice, pd.stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(prime_test_base2_kernel<FL>, dim3((n + kPrimeThreads - 1) / kPrimeThreads), dim3(kPrimeThreads), 0,
+                       pd.stream, reinterpret_cast<const uint64_t *>(d), n, d + kPrimeVerdictsAt);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    g_prime_launches++;
+    g_prime_candidates += n;
+    return hipMemcpyAsync(h + kPrimeVerdictsAt, d + kPrimeVerdictsAt, n, hipMemcpyDeviceToHost, pd.stream);
+}
+
+template <int FL>
+int32_t prime_test_fl(PrimeDev &pd, const uint64_t *candidates, uint32_t n, uint8_t *verdicts_out) {
+    for (uint32_t at = 0; at < n; at += kPrimeMaxBatch) {
+        const uint32_t take = std::min(n - at, kPrimeMaxBatch);
+        memcpy(pd.host, candidates + (size_t)at * FL, (size_t)take * FL * 8);
+        if (prime_enqueue<FL>(pd, 0, take) != hipSuccess || stream_wait(pd.stream) != hipSuccess) return prime_fail_drained(pd);
+        memcpy(verdicts_out + at, pd.host + kPrimeVerdictsAt, take);
+    }
+    return ZIP_OK;
+}
+
+template <int FL>
+int32_t get_prime_fl(PrimeDev &pd, zip_keccak_state *transcript, uint32_t batch, uint64_t *prime_out, uint32_t *tried_out) {
+    TrSponge sp;
+    memcpy(sp.st, transcript->st, sizeof sp.st);
+    {
+        uint8_t pending[kKeccakRate] = {0};
+        memcpy(pending, transcript->buf, transcript->buflen);
+        memcpy(sp.blk, pending, kKeccakRate);  // little-endian host
+    }
+    sp.buflen = transcript->buflen;
+    std::vector<TrSponge> after[2];  // after[slot][k]: the sponge once candidate k of that slot's batch is absorbed
+    after[0].resize(batch);
+    after[1].resize(batch);
+    auto hash = [&](uint32_t slot, uint32_t from, uint32_t to) {  // candidates [from, to) of the batch in `slot`
+        uint64_t *c = reinterpret_cast<uint64_t *>(pd.host + slot * kPrimeSlotBytes);
+        for (uint32_t k = from; k < to; k++) {
+            uint64_t cand[FL];
+            prime_next_candidate<FL>(sp, cand);
+            memcpy(c + (size_t)k * FL, cand, sizeof cand);
+            after[slot][k] = sp;
+        }
+    };
+    for (uint32_t done = 0, slot = 0, ahead = 0; done < kPrimeMaxCandidates; done += batch, slot ^= 1) {
+        hash(slot, ahead, batch);  // (the first batch; later, what the previous round left of this one)
+        const uint32_t n = std::min(batch, kPrimeMaxCandidates - done);
+        if (prime_enqueue<FL>(pd, slot, n) != hipSuccess) return prime_fail_drained(pd);
+        // the next batch's chain while this one is on the device -- eight candidates between two looks at the stream,
+        // and no further once the verdicts are in: a winner among them ends the call without the rest of the hashing
+        hipError_t q = hipErrorNotReady;
+        for (ahead = 0; ahead < batch && q == hipErrorNotReady; ahead = std::min(ahead + 8, batch)) {
+            hash(slot ^ 1, ahead, std::min(ahead + 8, batch));
+            q = hipStreamQuery(pd.stream);
+        }
+        clear_not_ready();
+        if (q == hipErrorNotReady) q = stream_wait(pd.stream);
+        if (q != hipSuccess) return prime_fail_drained(pd);
+        const unsigned char *h = pd.host + slot * kPrimeSlotBytes;
+        for (uint32_t k = 0; k < n; k++) {
+            if (!h[kPrimeVerdictsAt + k]) continue;
+            memcpy(prime_out, h + (size_t)k * FL * 8, (size_t)FL * 8);
+            if (tried_out) *tried_out = done + k + 1;
+            const TrSponge &w = after[slot][k];
+            memcpy(transcript->st, w.st, sizeof w.st);
+            memcpy(transcript->buf, w.blk, sizeof transcript->buf);  // zero beyond buflen
+            transcript->buflen = w.buflen;
+            return ZIP_OK;
+        }
+    }
+    fprintf(stderr, "zip_get_prime: no probable prime among the first %u candidates of %d limbs; giving up\n",
+            kPrimeMaxCandidates, FL);
+    return ZIP_ERR_UNSUPPORTED;
+}
+
 // ------------------------------------------------------------------ Spartan pieces
 template <int FL>
 int32_t ccs_map_i64(zip_ctx *ctx, const int64_t *in_d, uint64_t n_in, uint64_t n_out, uint64_t *out_d, const HostField &hf) {
@@ -2250,6 +2392,7 @@ void zip_release_cached_memory(void) {
     for (int d = 0; d < n && d < kMaxDevices; d++) {
         if (hipSetDevice(d) != hipSuccess) continue;
         recycle_flush(d);
+        prime_dev_release(d);
     }
 }
 
@@ -4596,6 +4739,44 @@ int32_t zip_sumcheck_prove(zip_sumcheck *s, zip_keccak_state *transcript, uint64
 void zip_sumcheck_launch_counts(uint64_t *rounds, uint64_t *tails) {
     if (rounds) *rounds = g_sumcheck_round_launches.load();
     if (tails) *tails = g_sumcheck_tail_launches.load();
+}
+
+int32_t zip_prime_test_base2(int32_t device, const uint64_t *candidates, uint32_t n, uint32_t limbs, uint8_t *verdicts_out) {
+    if (!candidates || !verdicts_out) return ZIP_ERR_NULL;
+    if (limbs < 2 || limbs > 4 || n == 0) return ZIP_ERR_INVALID_PARAM;
+    for (uint32_t i = 0; i < n; i++) {  // the lane function's contract: odd, at least 3
+        const uint64_t *c = candidates + (size_t)i * limbs;
+        uint64_t hi = 0;
+        for (uint32_t k = 1; k < limbs; k++) hi |= c[k];
+        if (!(c[0] & 1) || (hi == 0 && c[0] < 3)) return ZIP_ERR_INVALID_PARAM;
+    }
+    if (device < 0 || device >= kMaxDevices) return ZIP_ERR_NO_DEVICE;
+    PrimeDev &pd = g_prime[device];
+    std::lock_guard<std::mutex> g(pd.mu);
+    CurrentDeviceGuard restore;
+    if (int32_t rc = prime_dev_ready(pd, device)) return rc;
+    return with_fl(limbs, [&](auto FL) { return prime_test_fl<decltype(FL)::value>(pd, candidates, n, verdicts_out); });
+}
+
+int32_t zip_get_prime(int32_t device, zip_keccak_state *transcript, uint32_t limbs, uint64_t *prime_out,
+                      uint32_t *candidates_tried_out) {
+    if (!transcript || !prime_out) return ZIP_ERR_NULL;
+    if (limbs < 2 || limbs > 4 || transcript->buflen >= kKeccakRate) return ZIP_ERR_INVALID_PARAM;
+    if (device < 0 || device >= kMaxDevices) return ZIP_ERR_NO_DEVICE;
+    PrimeDev &pd = g_prime[device];
+    std::lock_guard<std::mutex> g(pd.mu);
+    CurrentDeviceGuard restore;
+    if (int32_t rc = prime_dev_ready(pd, device)) return rc;
+    // (per call: the tests flip it)
+    const uint32_t batch = prime_batch_knob(getenv("ZIP_HIP_PRIME_BATCH"), kPrimeDefaultBatch, kPrimeMaxBatch);
+    return with_fl(limbs, [&](auto FL) {
+        return get_prime_fl<decltype(FL)::value>(pd, transcript, batch, prime_out, candidates_tried_out);
+    });
+}
+
+void zip_prime_launch_counts(uint64_t *launches, uint64_t *candidates_tested) {
+    if (launches) *launches = g_prime_launches.load();
+    if (candidates_tested) *candidates_tested = g_prime_candidates.load();
 }
 
 const char *zip_sumcheck_last_error(const zip_sumcheck *s) { return s && s->ctx ? s->ctx->last_error.c_str() : ""; }

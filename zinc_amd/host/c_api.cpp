@@ -20,6 +20,9 @@ int32_t guarded(F &&f) {
     try {
         f();
         return ZINC_OK;
+    } catch (const zinc::FieldConfigError &e) {
+        g_err = e.what();
+        return ZINC_ERR_FIELD_CONFIG;
     } catch (const zinc::SpartanError &e) {
         g_err = e.what();
         return ZINC_ERR_SPARTAN;
@@ -84,6 +87,22 @@ int32_t zinc_transcript_import(zinc_transcript *t, const uint64_t *st, const uin
     k.buflen = buflen;
     t->t.import_state(k);
     return ZINC_OK;
+}
+
+int32_t zinc_get_prime(zinc_transcript *t, uint32_t limbs, int32_t device, uint64_t *prime_out, uint32_t *candidates_tried_out) {
+    if (!t || !prime_out) return ZINC_ERR_NULL;
+    return guarded([&] {
+        const Limbs p = prime_gen::get_prime(t->t, limbs, device, candidates_tried_out);
+        for (uint32_t i = 0; i < limbs; i++) prime_out[i] = p[i];
+    });
+}
+int32_t zinc_draw_random_field(const int64_t *public_input, size_t l, zinc_transcript *t, uint32_t limbs, int32_t device,
+                               uint64_t *modulus_out) {
+    if (!t || !modulus_out || (l && !public_input)) return ZINC_ERR_NULL;
+    return guarded([&] {
+        const FieldConfig f = draw_random_field(public_input, l, t->t, limbs, device);
+        for (uint32_t i = 0; i < limbs; i++) modulus_out[i] = f.modulus[i];
+    });
 }
 
 int32_t zinc_field_constants(const uint64_t *modulus, uint32_t limbs, uint64_t *r, uint64_t *r2, uint64_t *inv) {
@@ -571,11 +590,25 @@ int32_t zinc_verifier_verify(const zip_sparse_matrix *constraints, uint32_t t, u
                              const uint64_t *msgs2, const uint64_t *v_s, int32_t with_pcs, const uint8_t *roots,
                              size_t n_roots, const uint64_t *v, const uint8_t *pcs_proof, size_t pcs_proof_len,
                              uint64_t *rx_ry_out, uint64_t *e_y_out, uint64_t *gamma_out) {
+    return zinc_verifier_verify_checked(nullptr, 0, 0, constraints, t, s, d, q, s_masks, c, transcript, modulus, limbs, device,
+                                        prepared, msgs1, msgs2, v_s, with_pcs, roots, n_roots, v, pcs_proof, pcs_proof_len,
+                                        rx_ry_out, e_y_out, gamma_out);
+}
+
+int32_t zinc_verifier_verify_checked(const int64_t *public_input, size_t l, int32_t check_field,
+                                     const zip_sparse_matrix *constraints, uint32_t t, uint32_t s, uint32_t d, uint32_t q,
+                                     const uint32_t *s_masks, const int64_t *c, zinc_transcript *transcript,
+                                     const uint64_t *modulus, uint32_t limbs, int32_t device, zinc_prepared_ccs *prepared,
+                                     const uint64_t *msgs1, const uint64_t *msgs2, const uint64_t *v_s, int32_t with_pcs,
+                                     const uint8_t *roots, size_t n_roots, const uint64_t *v, const uint8_t *pcs_proof,
+                                     size_t pcs_proof_len, uint64_t *rx_ry_out, uint64_t *e_y_out, uint64_t *gamma_out) {
     if ((!constraints && !prepared && with_pcs) || !s_masks || !c || !transcript || !msgs1 || !msgs2 || !v_s ||
-        (with_pcs && (!roots || !v || !pcs_proof)))
+        (with_pcs && (!roots || !v || !pcs_proof)) || (check_field && l && !public_input))
         return ZINC_ERR_NULL;
     return guarded([&] {
         const FieldConfig f = FieldConfig::make(modulus, limbs);
+        if (check_field)  // verifier.rs:53-57, before any other work
+            zinc::ZincVerifier(LinearCodeSpec{}, device).check_field(public_input, l, transcript->t, f);
         zinc::ccs::CCS_Z ccs = square_ccs(t, s);
         ccs.q = q;
         ccs.d = d;

@@ -1704,6 +1704,42 @@ void ZincVerifier::verify_pcs_proof(const ccs::Statement_Z &statement, const zip
         throw SpartanError(SpartanError::PcsVerification, "linear combination of powers of gamma and V_x != e_y");
 }
 
+// ---------------------------------------------------------------------------- the random field
+Limbs prime_gen::get_prime(KeccakTranscript &transcript, uint32_t limbs, int device, uint32_t *candidates_tried) {
+    if (limbs < 2 || limbs > 4) throw ZipError(ZipError::InvalidPcsParam, "get_prime: FIELD_LIMBS must be 2, 3 or 4");
+    zip_keccak_state k;
+    transcript.export_state(&k);
+    Limbs prime{};
+    const int32_t rc = zip_get_prime(device, &k, limbs, prime.data(), candidates_tried);
+    if (rc) throw ZipError(ZipError::Device, std::string("zip_get_prime: ") + zip_strerror(rc));
+    transcript.import_state(k);
+    return prime;
+}
+
+FieldConfig draw_random_field(const int64_t *public_input, size_t l, KeccakTranscript &transcript, uint32_t limbs, int device) {
+    for (size_t i = 0; i < l; i++) {  // cast_slice(input.as_words()): the one word of an Int<1>, little-endian
+        uint8_t b[8];
+        const uint64_t w = (uint64_t)public_input[i];
+        for (int j = 0; j < 8; j++) b[j] = (uint8_t)(w >> (8 * j));
+        transcript.absorb(b, 8);
+    }
+    const Limbs prime = prime_gen::get_prime(transcript, limbs, device);
+    return FieldConfig::make(prime.data(), limbs);
+}
+
+void ZincVerifier::check_field(const int64_t *public_input, size_t l, KeccakTranscript &transcript,
+                               const FieldConfig &config) const {
+    const FieldConfig drawn = draw_random_field(public_input, l, transcript, config.limbs, device_);  // :53-57
+    if (drawn.limbs != config.limbs || drawn.modulus != config.modulus)
+        throw FieldConfigError("the field drawn from the public input and the transcript is not the given field configuration");
+}
+
+void ZincVerifier::verify_checked(const ccs::Statement_Z &statement, const ZincProof &proof, KeccakTranscript &transcript,
+                                  const ccs::CCS_Z &ccs, const FieldConfig &config, PreparedCcs *prepared) const {
+    check_field(statement.public_input.data(), statement.public_input.size(), transcript, config);
+    verify(statement, proof, transcript, ccs, config, prepared);
+}
+
 void ZincVerifier::verify(const ccs::Statement_Z &statement, const ZincProof &proof, KeccakTranscript &transcript,
                           const ccs::CCS_Z &ccs, const FieldConfig &config, PreparedCcs *prepared) const {
     if (ccs.s == 0 || ccs.s > 28 || ccs.m != ((size_t)1 << ccs.s) || ccs.n != ccs.m || ccs.s_prime != ccs.s)

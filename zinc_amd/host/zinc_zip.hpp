@@ -143,6 +143,25 @@ class KeccakTranscript {
     Keccak256 hasher_;
 };
 
+// ---------------------------------------------------------------------------- the random field
+// prime_gen::get_prime (src/prime_gen.rs:15-28) with F = RandomField<limbs>, limbs in {2, 3, 4}: candidates are hashed
+// out of the transcript (hash_int, :8-13) until MillerRabin::test_base_two accepts one.  The chain is hashed on the
+// host, in batches ahead of the tests; the tests of a batch are one launch on the device (zip_get_prime, zip_hip.h).
+// The transcript ends where the reference's loop leaves it.  Returns the prime's words; candidates_tried (may be
+// null): the winner's 1-based position.  Throws ZipError{InvalidPcsParam} for other limb counts, ZipError{Device} when
+// the device call fails -- there is no host path for the tests.
+namespace prime_gen {
+Limbs get_prime(KeccakTranscript &transcript, uint32_t limbs, int device = 0, uint32_t *candidates_tried = nullptr);
+}
+// draw_random_field (src/zinc/utils.rs:161-171) with I = Int<1>: every public input is absorbed as its 8 little-endian
+// bytes (:165-167), then FieldConfig::new(get_prime(transcript)).
+FieldConfig draw_random_field(const int64_t *public_input, size_t l, KeccakTranscript &transcript, uint32_t limbs,
+                              int device = 0);
+// ZincError::FieldConfigError (src/zinc/errors.rs): the field the verifier draws is not the one it was handed
+struct FieldConfigError : std::runtime_error {
+    explicit FieldConfigError(const std::string &what) : std::runtime_error(what) {}
+};
+
 namespace zip {
 
 // shuffle_seeded applied to the identity: shuffle_seeded(x, seed)[j] == x[perm[j]].
@@ -467,14 +486,21 @@ struct VerificationPoints {
     Limbs e_y{}, gamma{};
 };
 // ZincVerifier (src/zinc/verifier.rs).  The sumcheck verifiers are O(s * d) field operations on the host; the
-// Zip verifier and the evaluation of the matrix MLEs at (r_x, r_y) run on the device.  Not mirrored: the
-// draw_random_field check of Verifier::verify (:53-57, prime generation is out of scope).
+// Zip verifier and the evaluation of the matrix MLEs at (r_x, r_y) run on the device.  The draw_random_field check
+// of Verifier::verify (:53-57) is verify_checked's; verify itself takes the field it is handed.
 class ZincVerifier {
   public:
     explicit ZincVerifier(zip::LinearCodeSpec spec = {}, int device = 0) : lc_spec_(spec), device_(device) {}
     // Verifier::verify (:45-76) without the field check; throws SpartanError / ZipError{InvalidPcsOpen}
     void verify(const ccs::Statement_Z &statement, const ZincProof &proof, KeccakTranscript &transcript, const ccs::CCS_Z &ccs,
                 const FieldConfig &config, PreparedCcs *prepared = nullptr) const;
+    // Verifier::verify (:45-76) whole: first draw_random_field(statement.public_input, transcript) (:53-57) and throw
+    // FieldConfigError if it is not `config` (same limbs, same modulus) -- before any other work --, then verify
+    void verify_checked(const ccs::Statement_Z &statement, const ZincProof &proof, KeccakTranscript &transcript,
+                        const ccs::CCS_Z &ccs, const FieldConfig &config, PreparedCcs *prepared = nullptr) const;
+    // the check alone (:53-57): draws the field of `config.limbs` limbs from the public input on `transcript` and throws
+    // FieldConfigError unless it is `config`; the transcript is then where the reference's verify continues
+    void check_field(const int64_t *public_input, size_t l, KeccakTranscript &transcript, const FieldConfig &config) const;
     // SpartanVerifier::verify (:105-139)
     VerificationPoints spartan_verify(const SpartanProof &proof, const ccs::CCS_Z &ccs, KeccakTranscript &transcript,
                                       const FieldConfig &config) const;

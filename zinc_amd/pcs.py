@@ -11,6 +11,7 @@ from . import cabi
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", "libzinc_zip.so")
 OK, ERR_INVALID_PARAM, ERR_PANIC, ERR_DEVICE, ERR_NULL, ERR_INVALID_OPEN, ERR_SPARTAN = 0, -1, -2, -3, -4, -5, -6
+ERR_FIELD_CONFIG = -7
 
 EXPORTED_SYMBOLS = (
     "zinc_last_error", "zinc_transcript_new", "zinc_transcript_free", "zinc_transcript_absorb",
@@ -27,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "zinc_sumcheck_prove_products", "zinc_sumcheck_verify",
     "zinc_zip_batch_commit", "zinc_zip_batch_open", "zinc_zip_batch_open_challenges",
     "zinc_zip_batch_verify", "zinc_zip_batch_verify_challenges",
+    "zinc_get_prime", "zinc_draw_random_field", "zinc_verifier_verify_checked",
 )
 
 
@@ -40,6 +42,11 @@ class InvalidPcsOpen(ValueError):
 
 class SpartanError(ValueError):
     """SpartanError / SumCheckError of the verifier (src/zinc/errors.rs)"""
+
+
+class FieldConfigError(ValueError):
+    """ZincError::FieldConfigError: the field the verifier draws from the public input and the transcript
+    (draw_random_field, src/zinc/verifier.rs:53-57) is not the configuration it was handed."""
 
 
 class ReferencePanic(AssertionError):
@@ -76,6 +83,8 @@ def lib():
         L.zinc_transcript_get_challenge.argtypes = [vp, vp, C.c_uint32, vp]
         L.zinc_transcript_export.argtypes = [vp, vp, vp, vp]
         L.zinc_transcript_import.argtypes = [vp, vp, vp, C.c_uint32]
+        L.zinc_get_prime.argtypes = [vp, C.c_uint32, C.c_int32, vp, C.POINTER(C.c_uint32)]
+        L.zinc_draw_random_field.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_int32, vp]
         L.zinc_field_constants.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.zinc_field_mul.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.zinc_map_to_field_i64.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp]
@@ -138,6 +147,7 @@ def lib():
         L.zinc_verifier_verify.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32,
                                            C.c_int32, vp, vp, vp, vp, C.c_int32, vp, C.c_size_t, vp, vp, C.c_size_t,
                                            vp, vp, vp]
+        L.zinc_verifier_verify_checked.argtypes = [vp, C.c_size_t, C.c_int32] + L.zinc_verifier_verify.argtypes
         _lib = L
     return _lib
 
@@ -154,6 +164,8 @@ def _check(rc):
         raise ReferencePanic(msg)
     if rc == ERR_SPARTAN:
         raise SpartanError(msg)
+    if rc == ERR_FIELD_CONFIG:
+        raise FieldConfigError(msg)
     raise DeviceError(msg)
 
 
@@ -236,6 +248,28 @@ class KeccakTranscript:
         room = np.zeros(136, np.uint8)
         room[: min(len(buf), 136)] = np.frombuffer(bytes(buf[:136]), np.uint8)
         _check(lib().zinc_transcript_import(self._h, st.ctypes.data, room.ctypes.data, len(buf)))
+
+
+def get_prime(transcript: KeccakTranscript, limbs: int, device: int = 0, want_tried: bool = False):
+    """prime_gen::get_prime::<RandomField<limbs>>(transcript) (src/prime_gen.rs:15-28): the first candidate of the
+    transcript's hash chain that MillerRabin::test_base_two accepts, as a Python int; the candidates of a batch are
+    tested in one launch on the device.  The transcript ends where the reference's loop leaves it.
+    want_tried: -> (prime, the winner's 1-based position in the chain)."""
+    out = np.zeros(limbs, np.uint64)
+    tried = C.c_uint32(0)
+    _check(lib().zinc_get_prime(transcript._h, limbs, device, out.ctypes.data, C.byref(tried)))
+    prime = sum(int(w) << (64 * i) for i, w in enumerate(out))
+    return (prime, tried.value) if want_tried else prime
+
+
+def draw_random_field(public_input, transcript: KeccakTranscript, limbs: int, device: int = 0) -> FieldConfig:
+    """draw_random_field::<Int<1>, RandomField<limbs>> (src/zinc/utils.rs:161-171): absorbs every public input as its 8
+    little-endian bytes, then FieldConfig::new(get_prime(transcript))."""
+    x = np.ascontiguousarray(public_input, dtype=np.int64).reshape(-1)
+    out = np.zeros(limbs, np.uint64)
+    _check(lib().zinc_draw_random_field(x.ctypes.data if x.size else None, x.size, transcript._h, limbs, device,
+                                        out.ctypes.data))
+    return FieldConfig(sum(int(w) << (64 * i) for i, w in enumerate(out)), limbs)
 
 
 def kat_seed_from_u64(seed: int, n_words: int):
@@ -632,13 +666,15 @@ class ZincProver:
 
 
 class ZincVerifier:
-    """ZincVerifier (src/zinc/verifier.rs) without the draw_random_field check of Verifier::verify."""
+    """ZincVerifier (src/zinc/verifier.rs).  The draw_random_field check of Verifier::verify (:53-57) runs when `verify`
+    is given the public input; without it the verifier takes the field it is handed."""
 
     def __init__(self, device: int = 0):
         self.device = device
 
-    def _run(self, matrices, s, d, S, c, proof, transcript, field, with_pcs, prepared):
+    def _run(self, matrices, s, d, S, c, proof, transcript, field, with_pcs, prepared, public_input=None):
         t, fl = len(matrices), field.limbs
+        x = None if public_input is None else np.ascontiguousarray(public_input, dtype=np.int64).reshape(-1)
         arr, _keep = ZincProver._abi_matrices(matrices)
         masks = np.array([sum(1 << j for j in Si) for Si in S], dtype=np.uint32)
         cv = np.array(c, dtype=np.int64)
@@ -653,7 +689,8 @@ class ZincVerifier:
             roots = np.ascontiguousarray(zp["z_comm"], dtype=np.uint8)
             v = np.ascontiguousarray(zp["v"], dtype=np.uint64)
             pp = np.ascontiguousarray(zp["pcs_proof"], dtype=np.uint8)
-        _check(lib().zinc_verifier_verify(arr, t, s, d, len(S), masks.ctypes.data, cv.ctypes.data, transcript._h,
+        _check(lib().zinc_verifier_verify_checked(x.ctypes.data if x is not None and x.size else None, x.size if x is not None else 0,
+                                                  0 if x is None else 1, arr, t, s, d, len(S), masks.ctypes.data, cv.ctypes.data, transcript._h,
                                           field._m.ctypes.data, fl, self.device,
                                           prepared._h if prepared is not None else None, m1.ctypes.data, m2.ctypes.data,
                                           vs.ctypes.data, 1 if with_pcs else 0,
@@ -667,9 +704,14 @@ class ZincVerifier:
         """SpartanVerifier::verify (verifier.rs:105-139) -> VerificationPoints; raises SpartanError."""
         return self._run(matrices, s, d, S, c, proof, transcript, field, False, None)
 
-    def verify(self, matrices, s, d, S, c, proof, transcript: KeccakTranscript, field: FieldConfig, prepared=None):
-        """Verifier::verify (verifier.rs:45-76); raises SpartanError / InvalidPcsOpen."""
-        return self._run(matrices, s, d, S, c, proof, transcript, field, True, prepared)
+    def verify(self, matrices, s, d, S, c, proof, transcript: KeccakTranscript, field: FieldConfig, prepared=None,
+               public_input=None):
+        """Verifier::verify (verifier.rs:45-76); raises SpartanError / InvalidPcsOpen.
+        public_input (Statement_Z.public_input): when given, the reference's first check runs first, on the same
+        transcript -- draw_random_field(public_input, transcript) must be `field`, else FieldConfigError before any
+        other work (:53-57; the check is the C++ mirror's, ZincVerifier::check_field).  None: no such check, the field
+        is taken as handed."""
+        return self._run(matrices, s, d, S, c, proof, transcript, field, True, prepared, public_input)
 
 
 class PreparedCcs:
