@@ -74,6 +74,15 @@ typedef struct {
     uint64_t perm_1_seed, perm_2_seed;
 } zinc_raa_code;
 int32_t zinc_raa_code_new(uint64_t poly_size, zinc_transcript *transcript, zinc_raa_code *out);
+/* LinearCodeSpec (src/zip/code.rs:217-242).  The functions without _spec pass DefaultLinearCodeSpec {1000, 2, 1}, and so
+ * does a NULL spec.  num_proximity_testing = T in 1 .. 8 reaches the device (zip_ctx_set_proximity_tests, zip_hip.h): the
+ * proof carries T proximity rows and the verifier checks every one; another T is ZINC_ERR_INVALID_PARAM from open and
+ * verify when the matrix has more than one row (a one-row matrix has no test at all). */
+typedef struct {
+    uint32_t num_column_opening, repetition_factor, num_proximity_testing;
+} zinc_linear_code_spec;
+int32_t zinc_raa_code_new_spec(const zinc_linear_code_spec *spec, uint64_t poly_size, zinc_transcript *transcript,
+                               zinc_raa_code *out);
 
 /* MultilinearZip::setup / commit / open (src/zip/pcs/structs.rs:79-91, commit.rs:50-119, open_z.rs:22-40) */
 typedef struct zinc_zip_params zinc_zip_params;
@@ -114,6 +123,17 @@ uint64_t zinc_pcs_transcript_probe(const zinc_pcs_transcript *t);
 int32_t zinc_zip_open(const zinc_zip_params *pp, const int64_t *evals, size_t n_evals, uint32_t poly_num_vars,
                       const zinc_zip_data *data, const uint64_t *point, size_t point_len, const uint64_t *modulus,
                       uint32_t limbs, zinc_pcs_transcript *transcript);
+
+/* The squeezes of prove_testing_phase / verify_testing and nothing else (open_z.rs:100-120, verify_z.rs:66-90) -- host
+ * only, the Fiat-Shamir work a shim does in front of zip_open / zip_verify: per proximity test, in order,
+ * get_integer_challenges over num_rows (only if num_rows > 1), then num_column_opening times squeeze_challenge_idx over
+ * codeword_len.
+ *   coeffs_out  num_proximity_testing * num_rows, test-major (untouched when num_rows == 1; may then be NULL)
+ *   cols_out    num_column_opening
+ * ZINC_ERR_INVALID_PARAM: num_proximity_testing outside 1 .. 8 with num_rows > 1 (nothing is squeezed). */
+int32_t zinc_zip_open_challenges(uint32_t num_rows, uint32_t codeword_len, uint32_t num_column_opening,
+                                 uint32_t num_proximity_testing, const uint64_t *modulus, uint32_t limbs,
+                                 zinc_pcs_transcript *transcript, int64_t *coeffs_out, uint32_t *cols_out);
 
 /* ---- batch_commit / batch_open (commit.rs:134-142, open_z.rs:43-58) -------------------------
  * polys[i]: n_evals[i] evaluations with poly_num_vars[i] variables.
@@ -187,6 +207,10 @@ typedef struct zinc_zip_proof zinc_zip_proof;
 int32_t zinc_commit_z_mle_and_prove_evaluation(const int64_t *z_evals, size_t m, const uint64_t *r_y, size_t r_y_len,
                                                zinc_transcript *transcript, const uint64_t *modulus, uint32_t limbs,
                                                int32_t device, zinc_zip_proof **out);
+int32_t zinc_commit_z_mle_and_prove_evaluation_spec(const zinc_linear_code_spec *spec, const int64_t *z_evals, size_t m,
+                                                    const uint64_t *r_y, size_t r_y_len, zinc_transcript *transcript,
+                                                    const uint64_t *modulus, uint32_t limbs, int32_t device,
+                                                    zinc_zip_proof **out);
 size_t zinc_zip_proof_len(const zinc_zip_proof *p);
 size_t zinc_zip_proof_num_roots(const zinc_zip_proof *p);
 void zinc_zip_proof_read(const zinc_zip_proof *p, uint8_t *roots_out, uint64_t *v_out, uint8_t *pcs_proof_out);
@@ -247,6 +271,12 @@ int32_t zinc_prover_prove(const zip_sparse_matrix *constraints, uint32_t t, uint
                           uint32_t limbs, int32_t device, zinc_prepared_ccs *prepared, int32_t with_pcs,
                           uint64_t *msgs1_out, uint64_t *msgs2_out, uint64_t *v_s_out, uint64_t *r_y_out,
                           zinc_zip_proof **zip_proof_out);
+int32_t zinc_prover_prove_spec(const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                               uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c, const int64_t *public_input,
+                               size_t l, const int64_t *w_ccs, size_t w_len, zinc_transcript *transcript,
+                               const uint64_t *modulus, uint32_t limbs, int32_t device, zinc_prepared_ccs *prepared,
+                               int32_t with_pcs, uint64_t *msgs1_out, uint64_t *msgs2_out, uint64_t *v_s_out,
+                               uint64_t *r_y_out, zinc_zip_proof **zip_proof_out);
 
 /* ZincVerifier (src/zinc/verifier.rs): SpartanVerifier::verify (:105-139), and with with_pcs != 0 also
  * verify_pcs_proof (:221-273: RaaCode::new from the transcript, MultilinearZip::verify, the matrix MLEs at
@@ -272,6 +302,21 @@ int32_t zinc_verifier_verify_checked(const int64_t *public_input, size_t l, int3
                                      const uint64_t *msgs1, const uint64_t *msgs2, const uint64_t *v_s, int32_t with_pcs,
                                      const uint8_t *roots, size_t n_roots, const uint64_t *v, const uint8_t *pcs_proof,
                                      size_t pcs_proof_len, uint64_t *rx_ry_out, uint64_t *e_y_out, uint64_t *gamma_out);
+/* Both with the verifier's LinearCodeSpec (the spec argument first, everything else as above) */
+int32_t zinc_verifier_verify_spec(const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                                  uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c, zinc_transcript *transcript,
+                                  const uint64_t *modulus, uint32_t limbs, int32_t device, zinc_prepared_ccs *prepared,
+                                  const uint64_t *msgs1, const uint64_t *msgs2, const uint64_t *v_s, int32_t with_pcs,
+                                  const uint8_t *roots, size_t n_roots, const uint64_t *v, const uint8_t *pcs_proof,
+                                  size_t pcs_proof_len, uint64_t *rx_ry_out, uint64_t *e_y_out, uint64_t *gamma_out);
+int32_t zinc_verifier_verify_checked_spec(const zinc_linear_code_spec *spec, const int64_t *public_input, size_t l,
+                                          int32_t check_field, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                                          uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c,
+                                          zinc_transcript *transcript, const uint64_t *modulus, uint32_t limbs, int32_t device,
+                                          zinc_prepared_ccs *prepared, const uint64_t *msgs1, const uint64_t *msgs2,
+                                          const uint64_t *v_s, int32_t with_pcs, const uint8_t *roots, size_t n_roots,
+                                          const uint64_t *v, const uint8_t *pcs_proof, size_t pcs_proof_len, uint64_t *rx_ry_out,
+                                          uint64_t *e_y_out, uint64_t *gamma_out);
 
 #ifdef __cplusplus
 }

@@ -43,7 +43,8 @@ extern "C" {
  * changed, so the version stays 3; a caller that needs them looks the symbol up.  Likewise zip_sumcheck_init taking
  * up to 8 tables instead of 4: a widening, every call that was valid means what it meant.  The batch entry points,
  * zip_batch_commit and the five beside it, are additive in the same way, and so are zip_batch_verify and
- * zip_batch_verify_calls.  So are zip_prime_test_base2, zip_get_prime and zip_prime_launch_counts.) */
+ * zip_batch_verify_calls.  So are zip_prime_test_base2, zip_get_prime and zip_prime_launch_counts, and
+ * zip_ctx_set_proximity_tests / zip_ctx_proximity_tests: a ctx that never calls the setter behaves as before.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -155,6 +156,26 @@ int32_t zip_ctx_set_speculation(zip_ctx *ctx, int32_t on);
 int32_t zip_commit_hinted(zip_ctx *ctx, const int64_t *evals, size_t n_evals, zip_mem_kind evals_kind,
                           const uint32_t *cols, uint32_t n_cols, uint8_t *roots_out, zip_commitment **out);
 
+/* ---- proximity tests beyond one: LinearCodeSpec::num_proximity_testing (src/zip/code.rs:217-242) --------------------
+ * The proximity coefficients are 64-bit challenges; repeating the test is how a spec buys more proximity soundness
+ * (open_z.rs:103 and verify_z.rs:71 loop over the tests).  T = n_tests, default 1, accepted 1 .. 8; 0 or above 8 is
+ * ZIP_ERR_UNSUPPORTED, and so is T > 1 on a row-sharded ctx.  With T set, and num_rows > 1 (a one-row matrix has no
+ * test at all, whatever T is):
+ *   stream     u'_0 | ... | u'_{T-1} | columns | evaluation row (commit.rs:726): the column section and the row do not
+ *              depend on T, they only start (T - 1) * row_len * m_limbs * 8 bytes later
+ *   coeffs     T * num_rows values, test-major, in the order they are squeezed: test 0 .. test T-1, then the columns
+ *              (nothing between the first squeeze and the evaluation row absorbs)
+ * honoured by zip_proof_len, zip_open_testing (uprime_out: T * row_len * m_limbs), zip_open, zip_commit_open,
+ * zip_commit_open_begin / zip_job_wait, zip_open_stream (the first piece carries all T rows) and zip_verify, on every
+ * kind of handle.  The prover computes tests 1 .. T-1 in ONE extra pass over the witness; the verifier checks them
+ * from the column values alone, nothing is hashed again.  In zip_verify ZIP_VERIFY_PROXIMITY_TESTING at opening i
+ * means that ANY test failed there (verify_z.rs:92-97 checks every test of a column before its Merkle records), and
+ * ZIP_VERIFY_OVERFLOW that encode_wide overflowed for ANY u'_t.
+ * These stay ONE-test paths and return ZIP_ERR_UNSUPPORTED on a ctx with T > 1, before anything reaches the device:
+ * zip_batch_open, zip_batch_verify, zip_open_shard, zip_mctx_commit_open. */
+int32_t zip_ctx_set_proximity_tests(zip_ctx *ctx, uint32_t n_tests);
+uint32_t zip_ctx_proximity_tests(const zip_ctx *ctx); /* 0 for NULL */
+
 /* Device views of the handle (zero-copy interop).  rows: row_count*cw*4 u64 -- asking for them expands the
  * 16-byte entries a commitment keeps internally into this array once (a copy of row_count*cw*32 bytes on the
  * device); pass rows == NULL if only the layers / roots are wanted.
@@ -177,7 +198,8 @@ int32_t zip_commitment_upload(zip_ctx *ctx, const uint64_t *rows, const uint8_t 
  * last log2(num_rows) point coordinates (pcs/utils.rs:279-292).  Shard-local slices
  * (row_count entries) when the ctx is a row shard. */
 
-/* prove_testing_phase, proximity row (open_z.rs:103-112): uprime_out row_len * m_limbs u64. */
+/* prove_testing_phase, proximity rows (open_z.rs:103-112): coeffs T * num_rows, uprime_out T * row_len * m_limbs u64
+ * (T = zip_ctx_proximity_tests, 1 unless set). */
 int32_t zip_open_testing(zip_ctx *ctx, const int64_t *evals, zip_mem_kind evals_kind, const int64_t *coeffs,
                          uint64_t *uprime_out, zip_mem_kind out_kind);
 /* open_merkle_trees_for_column for n_cols columns (open_z.rs:116-120,124-143): wire_out gets
@@ -202,7 +224,7 @@ int32_t zip_open_eval(zip_ctx *ctx, const int64_t *evals, zip_mem_kind evals_kin
 /* proof length in bytes for n_cols openings (commit.rs:712-737) */
 size_t zip_proof_len(const zip_ctx *ctx, uint32_t n_cols, uint32_t field_limbs);
 /* Whole proof stream of open() in one call, witness read once:
- *   [u' : row_len*m_limbs*8 B, only if num_rows > 1] [n_cols column openings] [row_len field
+ *   [u'_0 .. u'_{T-1} : row_len*m_limbs*8 B each, only if num_rows > 1] [n_cols column openings] [row_len field
  *   elements, big-endian bytes of the Montgomery value (pcs_transcript.rs:107-113)].
  * The caller still absorbs the field elements into its transcript afterwards.
  * Only valid on an unsharded ctx. */
@@ -312,8 +334,8 @@ int32_t zip_open_stream(zip_commitment *c, const int64_t *evals, zip_mem_kind ev
 
 /* ---- verifier side ---------------------------------------------
  * MultilinearZip::verify (src/zip/pcs/verify_z.rs:19-188) on the device.  The caller (the Rust
- * shim / zinc_amd/host) keeps the Fiat-Shamir work: it squeezes `coeffs` (num_rows, only when
- * num_rows > 1) and the `cols`, builds (q0, q1) = point_to_tensor (pcs/utils.rs:252-276) and, after
+ * shim / zinc_amd/host) keeps the Fiat-Shamir work: it squeezes `coeffs` (T * num_rows, test-major, only when
+ * num_rows > 1; T = zip_ctx_proximity_tests) and the `cols`, builds (q0, q1) = point_to_tensor (pcs/utils.rs:252-276) and, after
  * the call, absorbs the row_len field elements at the end of the stream
  * (read_field_elements, pcs_transcript.rs:138-160).
  *   roots      HOST, num_rows * 32 bytes (MultilinearZipCommitment.roots)

@@ -25,7 +25,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 
 EXPORTED_SYMBOLS = (
     "zip_abi_version", "zip_strerror", "zip_device_count", "zip_release_cached_memory", "zip_host_register", "zip_host_unregister", "zip_ctx_create", "zip_ctx_destroy",
-    "zip_ctx_last_error", "zip_ctx_synchronize", "zip_ctx_stream", "zip_ctx_set_speculation", "zip_commit", "zip_commit_hinted", "zip_commit_open", "zip_commit_open_begin", "zip_job_wait", "zip_commitment_free",
+    "zip_ctx_last_error", "zip_ctx_synchronize", "zip_ctx_stream", "zip_ctx_set_speculation", "zip_ctx_set_proximity_tests", "zip_ctx_proximity_tests", "zip_commit", "zip_commit_hinted", "zip_commit_open", "zip_commit_open_begin", "zip_job_wait", "zip_commitment_free",
     "zip_commitment_device_ptrs", "zip_commit_download", "zip_commitment_upload", "zip_open_testing",
     "zip_open_columns", "zip_open_eval", "zip_proof_len", "zip_open", "zip_open_shard", "zip_sum_partials", "zip_merkle_trees",
     "zip_ctx_set_profiling", "zip_ctx_profile_read", "zip_ctx_commit_clock",
@@ -198,6 +198,9 @@ def lib():
     L.zip_ctx_synchronize.argtypes = [vp]
     L.zip_ctx_stream.argtypes = [vp]
     L.zip_ctx_stream.restype = vp
+    L.zip_ctx_set_proximity_tests.argtypes = [vp, C.c_uint32]
+    L.zip_ctx_proximity_tests.argtypes = [vp]
+    L.zip_ctx_proximity_tests.restype = C.c_uint32
     L.zip_commit.argtypes = [vp, i64p, C.c_size_t, C.c_int, C.c_int32, u8p, C.POINTER(vp)]
     L.zip_commit_hinted.argtypes = [vp, i64p, C.c_size_t, C.c_int, u32p, C.c_uint32, u8p, C.POINTER(vp)]
     L.zip_commit_open.argtypes = [vp, i64p, C.c_size_t, C.c_int, i64p, u32p, C.c_uint32, u64p, C.POINTER(ZipField), u8p, vp,
@@ -503,10 +506,14 @@ class ZipContext:
         return Commitment(self, h, layers is not None)
 
     def open_testing(self, evals, coeffs, out=None):
+        """The proximity rows alone.  coeffs [num_rows], or [T, num_rows] on a ctx set to T > 1 proximity tests (and
+        num_rows > 1); the result is then [T, row_len, m_limbs]."""
         ptr, kind = _ptr(evals)
         coeffs = np.ascontiguousarray(coeffs, dtype=np.int64)
-        assert coeffs.size == self.rows_local
-        res = out if out is not None else np.zeros((self.row_len, self.m_limbs), dtype=np.uint64)
+        t = self.proximity_tests if self.num_rows > 1 else 1
+        assert coeffs.size == t * self.rows_local
+        shape = (self.row_len, self.m_limbs) if t == 1 else (t, self.row_len, self.m_limbs)
+        res = out if out is not None else np.zeros(shape, dtype=np.uint64)
         optr, okind = _ptr(res)
         self._check(lib().zip_open_testing(self._h, ptr, kind, coeffs.ctypes.data, optr, okind), "zip_open_testing")
         return res
@@ -524,7 +531,8 @@ class ZipContext:
         return res
 
     def verify(self, roots, proof, coeffs, cols, q0_mont, q1_mont, eval_mont, field: ZipField):
-        """MultilinearZip::verify on the device; returns the zip_verify_report as a dict."""
+        """MultilinearZip::verify on the device; returns the zip_verify_report as a dict.  coeffs [num_rows], or
+        [T, num_rows] on a ctx set to T > 1 proximity tests."""
         roots_c = np.ascontiguousarray(roots, dtype=np.uint8)
         cols_c = np.ascontiguousarray(cols, dtype=np.uint32)
         coeffs_c = None if coeffs is None else np.ascontiguousarray(coeffs, dtype=np.int64)
@@ -607,6 +615,16 @@ class ZipContext:
 
     def set_profiling(self, on=True):
         self._check(lib().zip_ctx_set_profiling(self._h, int(on)), "zip_ctx_set_profiling")
+
+    def set_proximity_tests(self, n):
+        """zip_ctx_set_proximity_tests: LinearCodeSpec::num_proximity_testing = n (1 .. 8) for the single-context paths --
+        open, commit_open, the jobs, open_stream, open_testing, verify and proof_len; their coeffs are [n, num_rows],
+        test-major.  The batch, shard and multi-GPU paths stay one-test paths and refuse such a ctx."""
+        self._check(lib().zip_ctx_set_proximity_tests(self._h, int(n)), "zip_ctx_set_proximity_tests")
+
+    @property
+    def proximity_tests(self):
+        return int(lib().zip_ctx_proximity_tests(self._h))
 
     def set_speculation(self, on=True):
         """zip_ctx_set_speculation: plain commits hint themselves with the columns of the ctx's last opening.  Default: only

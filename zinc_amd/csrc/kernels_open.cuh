@@ -394,6 +394,109 @@ __global__ void __launch_bounds__(256) combine_rows_kernel(CombineArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Proximity tests 1 .. T-1 of a spec with num_proximity_testing = T > 1 (open_z.rs:103-112 loops over the tests):
+// u'_t = sum_r coeffs_t[r] * w[r][.] for NT = T - 1 further coefficient vectors in ONE pass over the witness.  Test 0
+// stays in combine_rows_kernel.  Per witness entry a test costs the four multiply-adds of mad_words<2> on top of the
+// one 8-byte load all of them share, so the tests ride one pass instead of taking one each.  Integer only: the same
+// biased-unsigned form as above, sum w' kept once for all tests, and per test the partials in the layout the integer
+// instance of combine_finalize_kernel folds (part_int [chunks][row_len][3]; part_k [chunks][k_stride] with sum_r c'_t
+// in its last two limbs, the limbs below them zero).
+// ---------------------------------------------------------------------------
+struct CombineExtraArgs {
+    const int64_t *evals;   // [num_rows][row_len]
+    const int64_t *coeffs;  // [NT][num_rows]        (device) tests 1 .. T-1, test-major
+    uint32_t num_rows, row_len, rows_per_chunk, chunks;
+    uint32_t prio;      // s_setprio level (see CombineArgs)
+    uint32_t k_stride;  // limbs per chunk of part_k: FL + 3 of the fold instance that reads it
+    uint64_t *part_int;  // [NT][chunks][row_len][3]
+    uint64_t *part_k;    // [NT][chunks][k_stride]
+};
+
+template <int NT>
+__global__ void __launch_bounds__(256) combine_rows_extra_kernel(CombineExtraArgs a) {
+    static_assert(NT >= 1 && NT <= 7, "tests 1 .. 7 beside test 0");
+    if (a.prio) __builtin_amdgcn_s_setprio(3);
+    const uint32_t col = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t chunk = blockIdx.y;
+    const uint32_t r0 = chunk * a.rows_per_chunk;
+    const uint32_t r1 = min(r0 + a.rows_per_chunk, a.num_rows);
+    const bool lead = __builtin_amdgcn_readfirstlane((uint32_t)(blockIdx.x == 0 && threadIdx.x < 64)) != 0;
+    constexpr uint64_t kBias = 1ull << 63;
+
+    WideAcc<3> P[NT];  // sum c'_t w'   < rows 2^128
+    WideAcc<1> W;      // sum w'        < rows 2^64, shared by the tests
+#pragma unroll
+    for (int t = 0; t < NT; t++) P[t].clear();
+    W.clear();
+
+    const bool live = col < a.row_len;
+    const int64_t *p = a.evals + (size_t)r0 * a.row_len + (live ? col : 0);
+    // (wave-uniform: scalar loads through the constant address space, multiplied from SGPRs, as in combine_rows_kernel)
+    const auto *coeffs_k = (const __attribute__((address_space(4))) int64_t *)(uintptr_t)a.coeffs;
+    auto one_row = [&](int64_t w, uint32_t r) {
+        const uint64_t wb = (uint64_t)w ^ kBias;
+        const uint32_t w0 = (uint32_t)wb, w1 = (uint32_t)(wb >> 32);
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            const uint64_t cb = (uint64_t)coeffs_k[(size_t)t * a.num_rows + r] ^ kBias;
+            const uint32_t c[2] = {(uint32_t)cb, (uint32_t)(cb >> 32)};
+            mad_words<2>(P[t], c, w0, w1);
+        }
+        W.template add<0>(wb);
+    };
+    uint32_t r = r0;
+    for (; r + kCombineUnroll <= r1; r += kCombineUnroll, p += (size_t)kCombineUnroll * a.row_len) {
+        int64_t w[kCombineUnroll];
+#pragma unroll
+        for (int k = 0; k < kCombineUnroll; k++) w[k] = p[(size_t)k * a.row_len];
+#pragma unroll
+        for (int k = 0; k < kCombineUnroll; k++) one_row(w[k], r + k);
+    }
+    for (; r < r1; r++, p += a.row_len) one_row(*p, r);
+    if (live) {
+        // P_t -= W << 63   (192-bit, wraps)
+        uint64_t ws[2], wl[3];
+        W.template pack<2>(ws);
+        wl[0] = ws[0] << 63;
+        wl[1] = (ws[0] >> 1) | (ws[1] << 63);
+        wl[2] = ws[1] >> 1;
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            uint64_t pl[3];
+            P[t].template pack<3>(pl);
+            sub_n<3>(pl, wl);
+            const size_t slot = ((size_t)t * a.chunks + chunk) * a.row_len + col;
+#pragma unroll
+            for (int i = 0; i < 3; i++) a.part_int[slot * 3 + i] = pl[i];
+        }
+    }
+    if (!lead) return;
+    // the chunk's sum_r c'_t per test: the lanes share the rows, then meet through xor shuffles
+    const uint32_t lane = threadIdx.x;
+#pragma unroll 1
+    for (int t = 0; t < NT; t++) {
+        uint64_t C[2] = {0, 0};
+        for (uint32_t rr = r0 + lane; rr < r1; rr += 64) {
+            const uint64_t x[2] = {(uint64_t)a.coeffs[(size_t)t * a.num_rows + rr] ^ kBias, 0};
+            add_n<2>(C, x);
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            uint64_t u[2];
+            u[0] = (uint64_t)__shfl_xor((unsigned long long)C[0], off, 64);
+            u[1] = (uint64_t)__shfl_xor((unsigned long long)C[1], off, 64);
+            add_n<2>(C, u);
+        }
+        if (lane == 0) {
+            uint64_t *k = a.part_k + ((size_t)t * a.chunks + chunk) * a.k_stride;
+            for (uint32_t i = 0; i + 2 < a.k_stride; i++) k[i] = 0;
+            k[a.k_stride - 2] = C[0];
+            k[a.k_stride - 1] = C[1];
+        }
+    }
+}
+
 struct FinalizeArgs {
     const uint64_t *part_int, *part_a, *part_k;
     uint32_t chunks, row_len, m_limbs;

@@ -202,13 +202,11 @@ __device__ __forceinline__ void field_from_int256(const uint64_t (&v)[4], const 
 // What one opened entry v = column[r] contributes, shared by verify_columns_kernel and
 // batch_verify_columns_kernel (the first assigns the terms, the second accumulates them).
 // ---------------------------------------------------------------------------------------
-// (si, sf) = or += (coeff * expand(v) in 384-bit two's complement, q0r (x) phi(v))   (verify_z.rs:114-120, 176-183).
-// Without coeff / q0r (num_rows == 1) the terms are 0 and phi(v).  The integer term joins si before phi(v) is formed,
-// so that it is not held across the field arithmetic.
-template <int FL, bool ACCUMULATE>
-__device__ __forceinline__ void opening_terms(const uint64_t (&v)[4], const int64_t *coeff, const uint64_t *q0r,
-                                              const FieldDev<FL> &f, const FieldDev<FL> &fq, bool quirk,
-                                              uint64_t (&si)[6], uint64_t (&sf)[FL]) {
+// The integer half of opening_terms, and all that the further proximity tests of a spec with num_proximity_testing > 1
+// need of an opened entry (verify_extra_tests_kernel): si = or += coeff * expand(v) in 384-bit two's complement
+// (verify_z.rs:114-120); without coeff (num_rows == 1) the term is 0.
+template <bool ACCUMULATE>
+__device__ __forceinline__ void opening_int_term(const uint64_t (&v)[4], const int64_t *coeff, uint64_t (&si)[6]) {
     if (coeff) {
         uint64_t t[6];
         const int64_t c = *coeff;
@@ -244,6 +242,16 @@ __device__ __forceinline__ void opening_terms(const uint64_t (&v)[4], const int6
 #pragma unroll
         for (int i = 0; i < 6; i++) si[i] = 0;
     }
+}
+
+// (si, sf) = or += (coeff * expand(v) in 384-bit two's complement, q0r (x) phi(v))   (verify_z.rs:114-120, 176-183).
+// Without coeff / q0r (num_rows == 1) the terms are 0 and phi(v).  The integer term joins si before phi(v) is formed,
+// so that it is not held across the field arithmetic.
+template <int FL, bool ACCUMULATE>
+__device__ __forceinline__ void opening_terms(const uint64_t (&v)[4], const int64_t *coeff, const uint64_t *q0r,
+                                              const FieldDev<FL> &f, const FieldDev<FL> &fq, bool quirk,
+                                              uint64_t (&si)[6], uint64_t (&sf)[FL]) {
+    opening_int_term<ACCUMULATE>(v, coeff, si);
     uint64_t e[FL], t[FL];
     field_from_int256<FL>(v, f, fq, quirk, e);
     if (q0r) {
@@ -397,6 +405,63 @@ __global__ void __launch_bounds__(256) verify_finalize_kernel(const uint64_t *pa
         column_sums_add<FL>(s, p, y, q, f);
     }
     flags[ci] = column_flags<FL>(s, p, enc_int ? enc_int + (size_t)col * m_limbs : nullptr, m_limbs, enc_f + (size_t)col * FL);
+}
+
+// ---------------------------------------------------------------------------------------
+// Proximity tests 1 .. T-1 of a spec with num_proximity_testing = T > 1 (verify_z.rs:66-103: every test of an opened
+// column is checked before its Merkle records).  Nothing is hashed again: one workgroup per opening reads only the
+// opening's num_rows column values (contiguous at the head of its block), thread t walks rows t, t + 256, ..., and per
+// test the terms coeffs_t[r] * v[r] are summed over the workgroup -- wave shuffles, then four LDS slots -- and compared
+// with encode_wide(u'_t) at the column, sign-extended as column_flags does.  A mismatch ORs bit 0 into flags[opening]
+// ("any test failed at this opening"): runs behind verify_finalize_kernel, which writes the flags, on its stream.
+// ---------------------------------------------------------------------------------------
+struct VerifyExtraArgs {
+    const uint8_t *wire;    // column section of the proof (device)
+    const uint32_t *cols;   // [n_cols]
+    const int64_t *coeffs;  // [n_tests][num_rows], test-major: tests 1 .. T-1
+    const uint64_t *enc_u;  // [n_tests][cw][m_limbs]: encode_wide(u'_t)
+    uint32_t num_rows, depth, n_cols, cw, m_limbs, n_tests;
+    uint32_t *flags;        // [n_cols]
+};
+
+__global__ void __launch_bounds__(256) verify_extra_tests_kernel(VerifyExtraArgs a) {
+    __shared__ uint64_t wave_sum[4][6];
+    const uint32_t ci = blockIdx.x, tid = threadIdx.x;
+    const uint32_t rec_bytes = 8 + 32 * a.depth;
+    const size_t col_bytes = (size_t)a.num_rows * (32 + rec_bytes);
+    const uint64_t *vals = reinterpret_cast<const uint64_t *>(a.wire + (size_t)ci * col_bytes);
+    const uint32_t col = a.cols[ci];
+    uint32_t failed = 0;  // (thread 0's)
+    for (uint32_t t = 0; t < a.n_tests; t++) {
+        const int64_t *coeffs = a.coeffs + (size_t)t * a.num_rows;
+        uint64_t si[6] = {0, 0, 0, 0, 0, 0};
+        for (uint32_t r = tid; r < a.num_rows; r += 256) {
+            uint64_t v[4];
+            fe_load<4>(v, vals + (size_t)r * 4);
+            opening_int_term<true>(v, coeffs + r, si);
+        }
+        for (uint32_t off = 1; off < 64; off <<= 1) {
+            uint64_t y[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++) y[i] = __shfl_xor(si[i], (int)off);
+            add_n<6>(si, y);
+        }
+        if ((tid & 63) == 0) fe_store<6>(wave_sum[tid >> 6], si);
+        __syncthreads();
+        if (tid == 0) {
+            for (uint32_t w = 1; w < 4; w++) {
+                uint64_t y[6];
+                fe_load<6>(y, wave_sum[w]);
+                add_n<6>(si, y);
+            }
+            const uint64_t *enc = a.enc_u + ((size_t)t * a.cw + col) * a.m_limbs;
+            const uint64_t sign = (uint64_t)((int64_t)si[5] >> 63);
+            for (uint32_t i = 0; i < a.m_limbs; i++)
+                if (enc[i] != (i < 6 ? si[i < 6 ? i : 0] : sign)) failed = 1u;
+        }
+        __syncthreads();  // wave_sum is free again
+    }
+    if (tid == 0 && failed) atomicOr(&a.flags[ci], 1u);
 }
 
 // out = sum_c a[c] (x) b[c]  (Montgomery values; inner_product, src/zip/utils.rs).  One workgroup.

@@ -118,6 +118,9 @@ struct zip_ctx {
     zip_params p{};
     uint32_t depth = 0;
     uint32_t rows_local = 0;
+    // LinearCodeSpec::num_proximity_testing (zip_ctx_set_proximity_tests): proximity rows the single-context open and
+    // verify paths write and check.  1 launches exactly what a ctx without the notion launched.
+    uint32_t n_tests = 1;
     int device = 0;
     // Three HIP streams form a row-chunked pipeline: `s_commit` runs the fused
     // encode+hash kernel chunk by chunk, `s_upper` the upper Merkle levels of each finished
@@ -1186,6 +1189,23 @@ struct CombineScratch {
     explicit CombineScratch(zip_ctx *c) : pint(c), pa(c), pb(c) {}
 };
 
+// Row chunks of the combination passes: enough workgroups to fill the chip, but few enough that the (latency-bound)
+// fold of the partials in combine_finalize_kernel stays short -- 128 chunks at 2^20 cost 0.32 ms there
+struct CombineChunks {
+    uint32_t bx, chunks, rpc;
+};
+CombineChunks combine_chunks(const zip_ctx *ctx) {
+    const uint32_t R = ctx->rows_local, C = ctx->p.row_len;
+    const uint32_t bx = (C + 255) / 256;
+    uint32_t chunks = 512 / bx;
+    if (chunks > 32) chunks = 32;
+    if (chunks < 1) chunks = 1;
+    if (chunks > R) chunks = R;
+    const uint32_t rpc = (R + chunks - 1) / chunks;
+    chunks = (R + rpc - 1) / rpc;
+    return {bx, chunks, rpc};
+}
+
 // coeffs_d / q0_d: DEVICE pointers (already staged)
 template <int FL>
 int32_t run_combine_fl(zip_ctx *ctx, const int64_t *evals_d, const int64_t *coeffs_dv,
@@ -1194,15 +1214,8 @@ int32_t run_combine_fl(zip_ctx *ctx, const int64_t *evals_d, const int64_t *coef
     // phase 0: both kernels; 1: only the pass over the witness (partial sums into `ext`); 2: only the fold of the
     // partial sums `ext` already holds.  zip_open runs them at the two ends of its pipeline.
     const uint32_t R = ctx->rows_local, C = ctx->p.row_len;
-    const uint32_t bx = (C + 255) / 256;
-    // row chunks: enough workgroups to fill the chip, but few enough that the (latency-bound) fold of
-    // the partials in combine_finalize_kernel stays short -- 128 chunks at 2^20 cost 0.32 ms there
-    uint32_t chunks = 512 / bx;
-    if (chunks > 32) chunks = 32;
-    if (chunks < 1) chunks = 1;
-    if (chunks > R) chunks = R;
-    const uint32_t rpc = (R + chunks - 1) / chunks;
-    chunks = (R + rpc - 1) / rpc;
+    const CombineChunks g = combine_chunks(ctx);
+    const uint32_t bx = g.bx, chunks = g.chunks, rpc = g.rpc;
 
     const hipStream_t st = ctx->stream;
     CombineScratch own(ctx);
@@ -1279,6 +1292,80 @@ int32_t run_combine(zip_ctx *ctx, const int64_t *evals_d, const int64_t *coeffs_
     return with_fl(hf ? hf->fl : 4, [&](auto FL) {
         return run_combine_fl<decltype(FL)::value>(ctx, evals_d, coeffs_dv, q0_dv, hf, do_int, do_field, out, ext, phase);
     });
+}
+
+// ---- proximity tests beyond the first (zip_ctx_set_proximity_tests) ----
+// What the single-context paths make of the ctx's count: a one-row matrix has no test at all, whatever the spec says
+// (open_z.rs:100, verify_z.rs:66).
+uint32_t proximity_tests(const zip_ctx *ctx) { return ctx->p.num_rows > 1 ? ctx->n_tests : 1; }
+// bytes of u'_0 .. u'_{T-1} at the head of a proof stream (commit.rs:726)
+size_t uprime_bytes(const zip_ctx *ctx) {
+    return ctx->p.num_rows > 1 ? (size_t)proximity_tests(ctx) * ctx->p.row_len * ctx->p.m_limbs * 8 : 0;
+}
+// The paths that stay one-test paths (batches, row shards, several GPUs)
+int32_t refuse_extra_tests(zip_ctx *ctx, const char *what) {
+    if (ctx->n_tests > 1)
+        return fail(ctx, ZIP_ERR_UNSUPPORTED, "%s serves one proximity test; the ctx is set to %u (use zip_open / zip_verify)", what,
+                    ctx->n_tests);
+    return ZIP_OK;
+}
+
+// u'_1 .. u'_{nt}: ONE pass over the witness for all of them (combine_rows_extra_kernel), then per test the integer fold
+// that test 0 takes too, straight to the test's place in the stream.  Enqueued on ctx->stream behind test 0.
+// coeffs_dv: [nt][rows] (device), uprime: [nt][row_len][m_limbs] (device).
+constexpr int kExtraFoldFL = 4;  // the fold instance (its field half is compiled out; FL only sets the part_k stride)
+int32_t run_combine_extra(zip_ctx *ctx, const int64_t *evals_d, const int64_t *coeffs_dv, uint32_t nt, uint64_t *uprime) {
+    if (nt == 0) return ZIP_OK;
+    if (nt > 7) return fail(ctx, ZIP_ERR_UNSUPPORTED, "%u proximity tests beside the first (at most 7)", nt);
+    const uint32_t R = ctx->rows_local, C = ctx->p.row_len, M = ctx->p.m_limbs;
+    const CombineChunks g = combine_chunks(ctx);
+    const hipStream_t st = ctx->stream;
+    Scratch pint(ctx), pk(ctx);
+    int32_t rc;
+    if ((rc = pint.get((size_t)nt * g.chunks * C * 3 * 8))) return rc;
+    if ((rc = pk.get((size_t)nt * g.chunks * (kExtraFoldFL + 3) * 8))) return rc;
+    CombineExtraArgs a{};
+    a.evals = evals_d;
+    a.coeffs = coeffs_dv;
+    a.num_rows = R;
+    a.row_len = C;
+    a.rows_per_chunk = g.rpc;
+    a.chunks = g.chunks;
+    a.prio = 1;
+    a.k_stride = kExtraFoldFL + 3;
+    a.part_int = pint.as<uint64_t>();
+    a.part_k = pk.as<uint64_t>();
+    {
+        LaunchTimer t(ctx, "combine_rows_extra_kernel", st);
+        const dim3 grid(g.bx, g.chunks), block(256);
+        switch (nt) {
+            case 1: hipLaunchKernelGGL(combine_rows_extra_kernel<1>, grid, block, 0, st, a); break;
+            case 2: hipLaunchKernelGGL(combine_rows_extra_kernel<2>, grid, block, 0, st, a); break;
+            case 3: hipLaunchKernelGGL(combine_rows_extra_kernel<3>, grid, block, 0, st, a); break;
+            case 4: hipLaunchKernelGGL(combine_rows_extra_kernel<4>, grid, block, 0, st, a); break;
+            case 5: hipLaunchKernelGGL(combine_rows_extra_kernel<5>, grid, block, 0, st, a); break;
+            case 6: hipLaunchKernelGGL(combine_rows_extra_kernel<6>, grid, block, 0, st, a); break;
+            default: hipLaunchKernelGGL(combine_rows_extra_kernel<7>, grid, block, 0, st, a); break;
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    const FieldDev<kExtraFoldFL> unused{};
+    for (uint32_t t = 0; t < nt; t++) {
+        FinalizeArgs fa{};
+        fa.part_int = a.part_int + (size_t)t * g.chunks * C * 3;
+        fa.part_k = a.part_k + (size_t)t * g.chunks * a.k_stride;
+        fa.num_rows = R;
+        fa.chunks = g.chunks;
+        fa.row_len = C;
+        fa.m_limbs = M;
+        fa.prio = a.prio;
+        fa.uprime = uprime + (size_t)t * C * M;
+        LaunchTimer tm(ctx, "combine_finalize_kernel", st);
+        const dim3 grid((C + kFinalizeCols - 1) / kFinalizeCols), block(kFinalizeCols * kFinalizeGroups);
+        hipLaunchKernelGGL((combine_finalize_kernel<kExtraFoldFL, true, false>), grid, block, 0, st, fa, unused);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return ZIP_OK;
 }
 
 int32_t check_cols(zip_ctx *ctx, const uint32_t *cols_h, uint32_t n_cols) {
@@ -1598,7 +1685,7 @@ int32_t check_verify_args(zip_ctx *ctx, const int64_t *coeffs, const uint32_t *c
 int32_t stage_verify_inputs(zip_ctx *ctx, uint32_t k, size_t stream_bytes, const uint8_t *proofs, zip_mem_kind proofs_kind,
                             const uint8_t *roots, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols,
                             const uint64_t *q0_mont, const uint64_t *q1_mont, const uint64_t *evals_mont, uint32_t fl,
-                            Scratch &pbuf, Scratch &small, VerifyIn *in) {
+                            Scratch &pbuf, Scratch &small, VerifyIn *in, uint32_t n_tests = 1) {
     const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len;
     const bool single = R == 1;
     int32_t rc;
@@ -1609,7 +1696,7 @@ int32_t stage_verify_inputs(zip_ctx *ctx, uint32_t k, size_t stream_bytes, const
         in->proofs_d = pbuf.as<uint8_t>();
     }
     SmallInputs si;
-    si.src[0] = coeffs;     si.bytes[0] = single ? 0 : (size_t)k * R * 8;
+    si.src[0] = coeffs;     si.bytes[0] = single ? 0 : (size_t)k * n_tests * R * 8;  // (n_tests > 1: zip_verify, k = 1)
     si.src[1] = q0_mont;    si.bytes[1] = single ? 0 : (size_t)k * R * fl * 8;
     si.src[2] = cols;       si.bytes[2] = (size_t)k * n_cols * 4;
     si.src[3] = q1_mont;    si.bytes[3] = C > 1 ? (size_t)k * C * fl * 8 : 0;
@@ -1635,12 +1722,13 @@ int32_t run_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, std
     const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len, M = ctx->p.m_limbs;
     const uint32_t n_cols = in.n_cols;
     const bool single = R == 1;
-    const size_t u_bytes = single ? 0 : (size_t)C * M * 8;
+    const uint32_t T = proximity_tests(ctx);   // u'_0 .. u'_{T-1} head the stream; coeffs_d is [T][R]
+    const size_t u_bytes = uprime_bytes(ctx);
     const size_t cols_bytes = (size_t)n_cols * column_bytes(ctx);
     const uint32_t blocks = (R + 255) / 256;
     Scratch enc_u(ctx), enc_f(ctx), tmp(ctx), row(ctx), parts(ctx), misc(ctx);
     int32_t rc;
-    if ((rc = enc_u.get((size_t)cw * M * 8))) return rc;
+    if ((rc = enc_u.get((size_t)T * cw * M * 8))) return rc;  // encode_wide(u'_t), test-major
     if ((rc = enc_f.get((size_t)cw * FL * 8))) return rc;
     if ((rc = tmp.get((size_t)cw * M * 8))) return rc;
     if ((rc = row.get((size_t)C * FL * 8))) return rc;
@@ -1656,9 +1744,12 @@ int32_t run_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, std
     // encode_wide(u') (verify_z.rs:75-77)
     if (!single) {
         FieldDev<8> unused{};
-        if ((rc = launch_encode_row<8, false>(ctx, reinterpret_cast<const uint64_t *>(in.proofs_d), tmp.as<uint64_t>(),
-                                              enc_u.as<uint64_t>(), unused, &cnt_d->overflow)))
-            return rc;
+        // (per test, one after the other on the stream: they share `tmp`; an overflow in any test is the one fact)
+        for (uint32_t t = 0; t < T; t++)
+            if ((rc = launch_encode_row<8, false>(ctx, reinterpret_cast<const uint64_t *>(in.proofs_d) + (size_t)t * C * M,
+                                                  tmp.as<uint64_t>(), enc_u.as<uint64_t>() + (size_t)t * cw * M, unused,
+                                                  &cnt_d->overflow)))
+                return rc;
     }
     // read_field_elements + encode_f + <row, q1> (verify_z.rs:139-149)
     {
@@ -1700,6 +1791,23 @@ int32_t run_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &hf, std
             hipLaunchKernelGGL(verify_finalize_kernel<FL>, dim3((n_cols + 255) / 256), dim3(256), 0, ctx->stream,
                                a.part_int, a.part_f, blocks, in.cols_d, n_cols,
                                single ? nullptr : enc_u.as<uint64_t>(), M, enc_f.as<uint64_t>(), flags_d, fd);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        if (T > 1) {  // tests 1 .. T-1 of every opening: bit 0 becomes "any test failed here" (verify_z.rs:92-97)
+            VerifyExtraArgs x{};
+            x.wire = a.wire;
+            x.cols = in.cols_d;
+            x.coeffs = in.coeffs_d + R;
+            x.enc_u = enc_u.as<uint64_t>() + (size_t)cw * M;
+            x.num_rows = R;
+            x.depth = ctx->depth;
+            x.n_cols = n_cols;
+            x.cw = cw;
+            x.m_limbs = M;
+            x.n_tests = T - 1;
+            x.flags = flags_d;
+            LaunchTimer t(ctx, "verify_extra_tests_kernel");
+            hipLaunchKernelGGL(verify_extra_tests_kernel, dim3(n_cols), dim3(256), 0, ctx->stream, x);
             HIP_TRY(ctx, hipGetLastError());
         }
     }
@@ -2945,6 +3053,18 @@ int32_t zip_ctx_set_speculation(zip_ctx *ctx, int32_t on) {
     return ZIP_OK;
 }
 
+int32_t zip_ctx_set_proximity_tests(zip_ctx *ctx, uint32_t n_tests) {
+    if (!ctx) return ZIP_ERR_NULL;
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (n_tests < 1 || n_tests > 8)
+        return fail(ctx, ZIP_ERR_UNSUPPORTED, "num_proximity_testing %u is outside the supported range 1 .. 8", n_tests);
+    if (n_tests > 1 && ctx->rows_local != ctx->p.num_rows)
+        return fail(ctx, ZIP_ERR_UNSUPPORTED, "a row-sharded ctx serves one proximity test (got %u)", n_tests);
+    ctx->n_tests = n_tests;
+    return ZIP_OK;
+}
+uint32_t zip_ctx_proximity_tests(const zip_ctx *ctx) { return ctx ? ctx->n_tests : 0; }
+
 int32_t zip_commit_hinted(zip_ctx *ctx, const int64_t *evals, size_t n_evals, zip_mem_kind evals_kind,
                           const uint32_t *cols, uint32_t n_cols, uint8_t *roots_out, zip_commitment **out) {
     if (!ctx || !out) return ZIP_ERR_NULL;
@@ -3185,7 +3305,8 @@ int32_t zip_open_testing(zip_ctx *ctx, const int64_t *evals, zip_mem_kind evals_
     const int64_t *evals_d;
     int32_t rc;
     if ((rc = stage_evals(ctx, evals, evals_kind, (size_t)ctx->rows_local * ctx->p.row_len, ev, &evals_d))) return rc;
-    const size_t bytes = (size_t)ctx->p.row_len * ctx->p.m_limbs * 8;
+    const uint32_t T = proximity_tests(ctx);
+    const size_t bytes = (size_t)T * ctx->p.row_len * ctx->p.m_limbs * 8;
     CombineOut o{};
     if (out_kind == ZIP_MEM_DEVICE) {
         o.uprime = uprime_out;
@@ -3196,11 +3317,13 @@ int32_t zip_open_testing(zip_ctx *ctx, const int64_t *evals, zip_mem_kind evals_
     Scratch small(ctx);
     SmallInputs si;
     si.src[0] = coeffs;
-    si.bytes[0] = (size_t)ctx->rows_local * 8;
+    si.bytes[0] = (size_t)T * ctx->rows_local * 8;
     unsigned char *sb;
     if ((rc = stage_small(ctx, si, small, &sb))) return rc;
-    if ((rc = run_combine(ctx, evals_d, reinterpret_cast<const int64_t *>(sb + si.off[0]), nullptr, nullptr, true,
-                          false, o)))
+    const int64_t *coeffs_dv = reinterpret_cast<const int64_t *>(sb + si.off[0]);
+    if ((rc = run_combine(ctx, evals_d, coeffs_dv, nullptr, nullptr, true, false, o))) return rc;
+    if ((rc = run_combine_extra(ctx, evals_d, coeffs_dv + ctx->rows_local, T - 1,
+                                o.uprime + (size_t)ctx->p.row_len * ctx->p.m_limbs)))
         return rc;
     if (out_kind == ZIP_MEM_HOST) return deliver(ctx, uprime_out, ZIP_MEM_HOST, o.uprime, bytes);
     HIP_TRY(ctx, stream_wait(ctx->stream));  // coeffs were read from host memory
@@ -3275,7 +3398,7 @@ int32_t zip_open_eval(zip_ctx *ctx, const int64_t *evals, zip_mem_kind evals_kin
 size_t zip_proof_len(const zip_ctx *ctx, uint32_t n_cols, uint32_t field_limbs) {
     if (!ctx) return 0;
     size_t len = 0;
-    if (ctx->p.num_rows > 1) len += (size_t)ctx->p.row_len * ctx->p.m_limbs * 8;
+    len += uprime_bytes(ctx);
     len += (size_t)n_cols * column_bytes(ctx);
     len += (size_t)ctx->p.row_len * field_limbs * 8;
     return len;
@@ -3298,7 +3421,7 @@ constexpr size_t kJobStageBytes = (size_t)1 << 20;
 static size_t job_stage_bytes(const zip_ctx *ctx, uint32_t n_cols, uint32_t fl) {
     auto r = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const bool single = ctx->p.num_rows == 1;
-    size_t t = (single ? 0 : r((size_t)ctx->rows_local * 8)) + r((size_t)ctx->rows_local * fl * 8) + r((size_t)n_cols * 4);
+    size_t t = (single ? 0 : r((size_t)proximity_tests(ctx) * ctx->rows_local * 8)) + r((size_t)ctx->rows_local * fl * 8) + r((size_t)n_cols * 4);
     if (n_cols > 1) t += r((size_t)n_cols * 4);
     if (n_cols <= 65536) t += r((size_t)n_cols * 16);
     return std::max(t, kJobStageBytes);
@@ -3310,7 +3433,8 @@ static int32_t open_enqueue(zip_commitment *c, const int64_t *evals_d, const int
     zip_ctx *ctx = c->ctx;
     int32_t rc;
     const bool single = ctx->p.num_rows == 1;
-    const size_t u_bytes = single ? 0 : (size_t)ctx->p.row_len * ctx->p.m_limbs * 8;
+    const uint32_t T = proximity_tests(ctx);
+    const size_t u_bytes = uprime_bytes(ctx);  // u'_0 .. u'_{T-1}
     const size_t col_bytes = (size_t)n_cols * column_bytes(ctx);
     CombineOut o{};
     o.uprime = single ? nullptr : reinterpret_cast<uint64_t *>(out_d);
@@ -3318,8 +3442,8 @@ static int32_t open_enqueue(zip_commitment *c, const int64_t *evals_d, const int
     Scratch &small = st.small;
     SmallInputs si;
     if (!single) {
-        si.src[0] = coeffs;
-        si.bytes[0] = (size_t)ctx->rows_local * 8;
+        si.src[0] = coeffs;  // [T][num_rows], test-major
+        si.bytes[0] = (size_t)T * ctx->rows_local * 8;
     }
     si.src[1] = single ? hf.r : q0_mont;
     si.bytes[1] = (size_t)ctx->rows_local * hf.fl * 8;
@@ -3364,6 +3488,10 @@ static int32_t open_enqueue(zip_commitment *c, const int64_t *evals_d, const int
     const int64_t *coeffs_dv = reinterpret_cast<const int64_t *>(sb + si.off[0]);
     const uint64_t *q0_dv = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
     if ((rc = run_combine(ctx, evals_d, coeffs_dv, q0_dv, &hf, !single, true, o))) return rc;
+    // tests 1 .. T-1: one more pass over the witness behind them, same stream, same wave priority
+    if (T > 1 && (rc = run_combine_extra(ctx, evals_d, coeffs_dv + ctx->rows_local, T - 1,
+                                         o.uprime + (size_t)ctx->p.row_len * ctx->p.m_limbs)))
+        return rc;
     return run_open_columns_pipelined(c, st.cols_dv, n_cols, st.openings_d);
 }
 // synchronises: the small host inputs (coeffs, cols, q0) have been consumed, every launch has run
@@ -3435,6 +3563,7 @@ int32_t zip_open_shard(zip_commitment *c, const int64_t *evals_d, const int64_t 
     if (!c->layers) return fail(ctx, ZIP_ERR_INVALID_PARAM, "commitment has no Merkle trees (commit_no_merkle)");
     HostField hf;
     int32_t rc;
+    if ((rc = refuse_extra_tests(ctx, "zip_open_shard"))) return rc;
     if ((rc = make_field(ctx, field, &hf))) return rc;
     const bool single = ctx->p.num_rows == 1;
     if (!single && (!coeffs || !q0_mont || !uprime_part_d)) return fail(ctx, ZIP_ERR_NULL, "coeffs / q0_mont / uprime_part is NULL");
@@ -3792,6 +3921,7 @@ int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
     HostField hf;
     int32_t rc;
+    if ((rc = refuse_extra_tests(ctx, "zip_batch_open"))) return rc;
     if ((rc = make_field(ctx, field, &hf))) return rc;
     const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, B = b->n_polys;
     const bool single = R == 1;
@@ -4094,6 +4224,8 @@ int32_t zip_mctx_commit_open(zip_mctx *m, const int64_t *evals, const int64_t *c
     const bool single = R == 1;
     HostField hf;
     int32_t rc;
+    for (zip_ctx *sc : m->shard)  // (reachable through zip_mctx_shard_ctx on a one-shard mctx only)
+        if ((rc = refuse_extra_tests(sc, "zip_mctx_commit_open"))) return mfail(m, rc, "proximity tests", sc);
     if ((rc = make_field(lead, field, &hf))) return mfail(m, rc, "field", lead);
     if (!single && (!coeffs || !q0_mont)) return mfail(m, ZIP_ERR_NULL, "coeffs / q0_mont is NULL");
     if ((rc = check_cols(lead, cols, n_cols))) return mfail(m, rc, "cols", lead);
@@ -4333,7 +4465,7 @@ int32_t zip_verify(zip_ctx *ctx, const uint8_t *roots, const uint8_t *proof, zip
     Scratch pbuf(ctx), small(ctx);
     VerifyIn in{};
     if ((rc = stage_verify_inputs(ctx, 1, need, proof, proof_kind, roots, coeffs, cols, n_cols, q0_mont, q1_mont, nullptr, hf.fl,
-                                  pbuf, small, &in)))
+                                  pbuf, small, &in, proximity_tests(ctx))))
         return rc;
     std::vector<uint32_t> flags, bad, malformed;
     VerifyHead cnt{};
@@ -4373,6 +4505,7 @@ int32_t zip_batch_verify(zip_ctx *ctx, uint32_t n_polys, const uint8_t *roots, c
     if (n_polys == 0 || n_polys > 65535)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "a batch holds 1 .. 65535 polynomials (got %u)", n_polys);
     if (ctx->rows_local != R) return fail(ctx, ZIP_ERR_INVALID_PARAM, "batches need an unsharded ctx");
+    if (int32_t r = refuse_extra_tests(ctx, "zip_batch_verify")) return r;
     if (cw > 16384)
         return fail(ctx, ZIP_ERR_UNSUPPORTED, "batches serve codewords up to 16384 (got %u): larger proofs are not launch-bound, "
                     "use zip_verify", cw);
@@ -4497,7 +4630,8 @@ int32_t zip_open_stream(zip_commitment *c, const int64_t *evals, zip_mem_kind ev
     }
     if ((rc = ensure_columns(c, cols, n_cols, evals_d))) return rc;
     note_columns(ctx, cols, n_cols);
-    const size_t u_bytes = single ? 0 : (size_t)ctx->p.row_len * ctx->p.m_limbs * 8;
+    const uint32_t T = proximity_tests(ctx);
+    const size_t u_bytes = uprime_bytes(ctx);  // u'_0 .. u'_{T-1}: the first piece
     const size_t row_bytes = (size_t)ctx->p.row_len * hf.fl * 8;
     const size_t colb = column_bytes(ctx);
     // columns per group: as many as fit the hint (default 64 MiB), at least one
@@ -4514,7 +4648,7 @@ int32_t zip_open_stream(zip_commitment *c, const int64_t *evals, zip_mem_kind ev
     SmallInputs si;
     if (!single) {
         si.src[0] = coeffs;
-        si.bytes[0] = (size_t)ctx->rows_local * 8;
+        si.bytes[0] = (size_t)T * ctx->rows_local * 8;
     }
     si.src[1] = single ? hf.r : q0_mont;
     si.bytes[1] = (size_t)ctx->rows_local * hf.fl * 8;
@@ -4529,6 +4663,9 @@ int32_t zip_open_stream(zip_commitment *c, const int64_t *evals, zip_mem_kind ev
     o.row_be = ends.as<uint8_t>() + u_bytes;
     if ((rc = run_combine(ctx, evals_d, reinterpret_cast<const int64_t *>(sb + si.off[0]),
                           reinterpret_cast<const uint64_t *>(sb + si.off[1]), &hf, !single, true, o)))
+        return rc;
+    if (T > 1 && (rc = run_combine_extra(ctx, evals_d, reinterpret_cast<const int64_t *>(sb + si.off[0]) + ctx->rows_local, T - 1,
+                                         o.uprime + (size_t)ctx->p.row_len * ctx->p.m_limbs)))
         return rc;
     hipStream_t s_copy = ctx->s_upper;  // D2H copies run beside the next group's gather
     hipEvent_t gathered[2] = {take_dep_event(ctx), take_dep_event(ctx)};

@@ -150,16 +150,31 @@ void zinc_shuffle_seeded_perm(uint64_t seed, uint32_t len, uint32_t *perm) {
 
 void zinc_kat_seed_from_u64(uint64_t seed, uint32_t *words, uint32_t n_words) { kat_seed_from_u64(seed, words, n_words); }
 
+// NULL: DefaultLinearCodeSpec
+static LinearCodeSpec spec_of(const zinc_linear_code_spec *spec) {
+    LinearCodeSpec s;
+    if (spec) {
+        s.num_column_opening = spec->num_column_opening;
+        s.repetition_factor = spec->repetition_factor;
+        s.num_proximity_testing = spec->num_proximity_testing;
+    }
+    return s;
+}
+
 int32_t zinc_raa_code_new(uint64_t poly_size, zinc_transcript *transcript, zinc_raa_code *out) {
+    return zinc_raa_code_new_spec(nullptr, poly_size, transcript, out);
+}
+int32_t zinc_raa_code_new_spec(const zinc_linear_code_spec *spec, uint64_t poly_size, zinc_transcript *transcript,
+                               zinc_raa_code *out) {
     if (!out) return ZINC_ERR_NULL;
     return guarded([&] {
         RaaCode c;
         if (transcript) {
             KeccakSeedSource src(transcript->t);
-            c = RaaCode::make(LinearCodeSpec{}, poly_size, src);
+            c = RaaCode::make(spec_of(spec), poly_size, src);
         } else {
             MockTranscript mock;
-            c = RaaCode::make(LinearCodeSpec{}, poly_size, mock);
+            c = RaaCode::make(spec_of(spec), poly_size, mock);
         }
         *out = {c.row_len, c.repetition_factor, c.num_column_opening, c.num_proximity_testing, c.perm_1_seed, c.perm_2_seed};
     });
@@ -315,6 +330,21 @@ int32_t zinc_zip_batch_open_challenges(uint32_t num_rows, uint32_t row_len, uint
     });
 }
 
+int32_t zinc_zip_open_challenges(uint32_t num_rows, uint32_t codeword_len, uint32_t num_column_opening,
+                                 uint32_t num_proximity_testing, const uint64_t *modulus, uint32_t limbs,
+                                 zinc_pcs_transcript *transcript, int64_t *coeffs_out, uint32_t *cols_out) {
+    if (!modulus || !transcript || (num_column_opening && !cols_out)) return ZINC_ERR_NULL;
+    return guarded([&] {
+        if (!codeword_len) throw ZipError(ZipError::InvalidPcsParam, "codeword_len is 0");
+        const FieldConfig f = FieldConfig::make(modulus, limbs);
+        const auto ch = MultilinearZip::open_challenges(num_rows, codeword_len, num_column_opening, num_proximity_testing, f,
+                                                        transcript->t);
+        if (!ch.first.empty() && !coeffs_out) throw ZipError(ZipError::InvalidPcsParam, "coeffs_out is NULL");
+        std::copy(ch.first.begin(), ch.first.end(), coeffs_out);
+        std::copy(ch.second.begin(), ch.second.end(), cols_out);
+    });
+}
+
 zinc_pcs_transcript *zinc_pcs_transcript_from_proof(const uint8_t *proof, size_t len) {
     auto *t = new zinc_pcs_transcript();
     t->t = PcsTranscript::from_proof(proof, len);
@@ -395,6 +425,12 @@ struct zinc_zip_proof {
 int32_t zinc_commit_z_mle_and_prove_evaluation(const int64_t *z_evals, size_t m, const uint64_t *r_y, size_t r_y_len,
                                                zinc_transcript *transcript, const uint64_t *modulus, uint32_t limbs,
                                                int32_t device, zinc_zip_proof **out) {
+    return zinc_commit_z_mle_and_prove_evaluation_spec(nullptr, z_evals, m, r_y, r_y_len, transcript, modulus, limbs, device, out);
+}
+int32_t zinc_commit_z_mle_and_prove_evaluation_spec(const zinc_linear_code_spec *spec, const int64_t *z_evals, size_t m,
+                                                    const uint64_t *r_y, size_t r_y_len, zinc_transcript *transcript,
+                                                    const uint64_t *modulus, uint32_t limbs, int32_t device,
+                                                    zinc_zip_proof **out) {
     if (!z_evals || !transcript || !out) return ZINC_ERR_NULL;
     *out = nullptr;
     return guarded([&] {
@@ -402,7 +438,7 @@ int32_t zinc_commit_z_mle_and_prove_evaluation(const int64_t *z_evals, size_t m,
         std::vector<Limbs> pt(r_y_len);
         for (size_t i = 0; i < r_y_len; i++) pt[i] = load(r_y + i * limbs, limbs);
         auto *res = new zinc_zip_proof{
-            zinc::zip::commit_z_mle_and_prove_evaluation(LinearCodeSpec{}, z_evals, m, pt.data(), r_y_len, transcript->t, f, device),
+            zinc::zip::commit_z_mle_and_prove_evaluation(spec_of(spec), z_evals, m, pt.data(), r_y_len, transcript->t, f, device),
             limbs};
         *out = res;
     });
@@ -537,6 +573,15 @@ int32_t zinc_prover_prove(const zip_sparse_matrix *constraints, uint32_t t, uint
                           uint32_t limbs, int32_t device, zinc_prepared_ccs *prepared, int32_t with_pcs,
                           uint64_t *msgs1_out, uint64_t *msgs2_out, uint64_t *v_s_out, uint64_t *r_y_out,
                           zinc_zip_proof **zip_proof_out) {
+    return zinc_prover_prove_spec(nullptr, constraints, t, s, d, q, s_masks, c, public_input, l, w_ccs, w_len, transcript, modulus,
+                                  limbs, device, prepared, with_pcs, msgs1_out, msgs2_out, v_s_out, r_y_out, zip_proof_out);
+}
+int32_t zinc_prover_prove_spec(const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                               uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c, const int64_t *public_input,
+                               size_t l, const int64_t *w_ccs, size_t w_len, zinc_transcript *transcript,
+                               const uint64_t *modulus, uint32_t limbs, int32_t device, zinc_prepared_ccs *prepared,
+                               int32_t with_pcs, uint64_t *msgs1_out, uint64_t *msgs2_out, uint64_t *v_s_out,
+                               uint64_t *r_y_out, zinc_zip_proof **zip_proof_out) {
     if ((!constraints && !prepared) || !s_masks || !c || !transcript || !msgs1_out || !msgs2_out || !v_s_out || !r_y_out ||
         (l && !public_input) || (w_len && !w_ccs) || (with_pcs && !zip_proof_out))
         return ZINC_ERR_NULL;
@@ -560,7 +605,7 @@ int32_t zinc_prover_prove(const zip_sparse_matrix *constraints, uint32_t t, uint
         if (!prepared) own = std::make_unique<zinc::PreparedCcs>(constraints, t, s, f, device);
         zinc::PreparedCcs *prep = prepared ? prepared->p.get() : own.get();
         const zinc::IntVec z = zinc::ZincProver::get_z_ccs(public_input, l, w_ccs, w_len, ccs.m);  // x || 1 || w
-        const zinc::ZincProver prover(LinearCodeSpec{}, device);
+        const zinc::ZincProver prover(spec_of(spec), device);
         zinc::SpartanProof sp;
         std::vector<Limbs> r_y;
         if (with_pcs) {
@@ -594,6 +639,16 @@ int32_t zinc_verifier_verify(const zip_sparse_matrix *constraints, uint32_t t, u
                                         prepared, msgs1, msgs2, v_s, with_pcs, roots, n_roots, v, pcs_proof, pcs_proof_len,
                                         rx_ry_out, e_y_out, gamma_out);
 }
+int32_t zinc_verifier_verify_spec(const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                                  uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c, zinc_transcript *transcript,
+                                  const uint64_t *modulus, uint32_t limbs, int32_t device, zinc_prepared_ccs *prepared,
+                                  const uint64_t *msgs1, const uint64_t *msgs2, const uint64_t *v_s, int32_t with_pcs,
+                                  const uint8_t *roots, size_t n_roots, const uint64_t *v, const uint8_t *pcs_proof,
+                                  size_t pcs_proof_len, uint64_t *rx_ry_out, uint64_t *e_y_out, uint64_t *gamma_out) {
+    return zinc_verifier_verify_checked_spec(spec, nullptr, 0, 0, constraints, t, s, d, q, s_masks, c, transcript, modulus, limbs,
+                                             device, prepared, msgs1, msgs2, v_s, with_pcs, roots, n_roots, v, pcs_proof,
+                                             pcs_proof_len, rx_ry_out, e_y_out, gamma_out);
+}
 
 int32_t zinc_verifier_verify_checked(const int64_t *public_input, size_t l, int32_t check_field,
                                      const zip_sparse_matrix *constraints, uint32_t t, uint32_t s, uint32_t d, uint32_t q,
@@ -602,13 +657,25 @@ int32_t zinc_verifier_verify_checked(const int64_t *public_input, size_t l, int3
                                      const uint64_t *msgs1, const uint64_t *msgs2, const uint64_t *v_s, int32_t with_pcs,
                                      const uint8_t *roots, size_t n_roots, const uint64_t *v, const uint8_t *pcs_proof,
                                      size_t pcs_proof_len, uint64_t *rx_ry_out, uint64_t *e_y_out, uint64_t *gamma_out) {
+    return zinc_verifier_verify_checked_spec(nullptr, public_input, l, check_field, constraints, t, s, d, q, s_masks, c, transcript,
+                                             modulus, limbs, device, prepared, msgs1, msgs2, v_s, with_pcs, roots, n_roots, v,
+                                             pcs_proof, pcs_proof_len, rx_ry_out, e_y_out, gamma_out);
+}
+int32_t zinc_verifier_verify_checked_spec(const zinc_linear_code_spec *spec, const int64_t *public_input, size_t l,
+                                          int32_t check_field, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                                          uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c,
+                                          zinc_transcript *transcript, const uint64_t *modulus, uint32_t limbs, int32_t device,
+                                          zinc_prepared_ccs *prepared, const uint64_t *msgs1, const uint64_t *msgs2,
+                                          const uint64_t *v_s, int32_t with_pcs, const uint8_t *roots, size_t n_roots,
+                                          const uint64_t *v, const uint8_t *pcs_proof, size_t pcs_proof_len, uint64_t *rx_ry_out,
+                                          uint64_t *e_y_out, uint64_t *gamma_out) {
     if ((!constraints && !prepared && with_pcs) || !s_masks || !c || !transcript || !msgs1 || !msgs2 || !v_s ||
         (with_pcs && (!roots || !v || !pcs_proof)) || (check_field && l && !public_input))
         return ZINC_ERR_NULL;
     return guarded([&] {
         const FieldConfig f = FieldConfig::make(modulus, limbs);
         if (check_field)  // verifier.rs:53-57, before any other work
-            zinc::ZincVerifier(LinearCodeSpec{}, device).check_field(public_input, l, transcript->t, f);
+            zinc::ZincVerifier(spec_of(spec), device).check_field(public_input, l, transcript->t, f);
         zinc::ccs::CCS_Z ccs = square_ccs(t, s);
         ccs.q = q;
         ccs.d = d;
@@ -630,7 +697,7 @@ int32_t zinc_verifier_verify_checked(const int64_t *public_input, size_t l, int3
         sp.linearization_sumcheck = take(msgs1, s, d + 2);
         sp.second_sumcheck = take(msgs2, s, 3);
         for (uint32_t k = 0; k < t; k++) sp.V_s.push_back(load(v_s + (size_t)k * limbs, limbs));
-        const zinc::ZincVerifier verifier(LinearCodeSpec{}, device);
+        const zinc::ZincVerifier verifier(spec_of(spec), device);
         const zinc::VerificationPoints pts = verifier.spartan_verify(sp, ccs, transcript->t, f);
         auto put = [&](uint64_t *dst, const Limbs &x) {
             if (dst)

@@ -700,12 +700,14 @@ struct CtxKey {
     int device;
     uint32_t num_vars, row_len, rep;
     uint64_t seed1, seed2;
+    uint32_t tests;  // zip_ctx_set_proximity_tests of the ctx: two specs never share one
     bool operator==(const CtxKey &o) const {
         return device == o.device && num_vars == o.num_vars && row_len == o.row_len && rep == o.rep &&
-               seed1 == o.seed1 && seed2 == o.seed2;
+               seed1 == o.seed1 && seed2 == o.seed2 && tests == o.tests;
     }
 };
 constexpr size_t kCtxCacheSize = 4;
+constexpr uint32_t kMaxProximityTests = 8;  // zip_ctx_set_proximity_tests accepts 1 .. 8
 std::mutex &ctx_cache_mu() {
     static std::mutex m;
     return m;
@@ -727,7 +729,11 @@ MultilinearZipParams MultilinearZip::setup(uint64_t poly_size, const RaaCode &co
     pp.perm1 = shuffle_seeded_perm(code.perm_1_seed, code.codeword_len());
     pp.perm2 = shuffle_seeded_perm(code.perm_2_seed, code.codeword_len());
     // cached device context for this (device, geometry, seeds)
-    const CtxKey key{device, pp.num_vars, code.row_len, code.repetition_factor, code.perm_1_seed, code.perm_2_seed};
+    // (a count the device does not serve is open's and verify's to refuse, as the reference's errors are: the ctx of
+    // such a spec, and of a one-row matrix, which has no test at all, is a one-test ctx)
+    const uint32_t tests = pp.num_rows > 1 && code.num_proximity_testing >= 1 && code.num_proximity_testing <= kMaxProximityTests
+                               ? code.num_proximity_testing : 1;
+    const CtxKey key{device, pp.num_vars, code.row_len, code.repetition_factor, code.perm_1_seed, code.perm_2_seed, tests};
     {
         std::lock_guard<std::mutex> g(ctx_cache_mu());
         auto &cache = ctx_cache();
@@ -754,6 +760,7 @@ MultilinearZipParams MultilinearZip::setup(uint64_t poly_size, const RaaCode &co
     zip_ctx *ctx = nullptr;
     check(nullptr, zip_ctx_create(&zp, &ctx), "zip_ctx_create");
     pp.ctx = std::shared_ptr<zip_ctx>(ctx, zip_ctx_destroy);
+    if (tests != 1) check(ctx, zip_ctx_set_proximity_tests(ctx, tests), "zip_ctx_set_proximity_tests");
     {
         std::lock_guard<std::mutex> g(ctx_cache_mu());
         auto &cache = ctx_cache();
@@ -811,6 +818,28 @@ MultilinearZipData MultilinearZip::commit_no_merkle(const MultilinearZipParams &
     return commit_impl(pp, evals, n_evals, poly_num_vars, false).first;
 }
 
+std::pair<std::vector<int64_t>, std::vector<uint32_t>> MultilinearZip::open_challenges(uint32_t num_rows, uint32_t codeword_len,
+                                                                                      uint32_t num_column_opening,
+                                                                                      uint32_t num_proximity_testing,
+                                                                                      const FieldConfig &field,
+                                                                                      PcsTranscript &transcript) {
+    std::pair<std::vector<int64_t>, std::vector<uint32_t>> out;
+    if (num_rows > 1) {  // prove_testing_phase, open_z.rs:100-113; verify_testing, verify_z.rs:66-77
+        if (num_proximity_testing < 1 || num_proximity_testing > kMaxProximityTests)
+            throw ZipError(ZipError::InvalidPcsParam, "num_proximity_testing " + std::to_string(num_proximity_testing) +
+                                                          " is outside the supported range 1 .. " +
+                                                          std::to_string(kMaxProximityTests) + " of the device path");
+        out.first.reserve((size_t)num_proximity_testing * num_rows);
+        for (uint32_t t = 0; t < num_proximity_testing; t++) {
+            const auto c = transcript.fs_transcript.get_integer_challenges_i64(num_rows);
+            out.first.insert(out.first.end(), c.begin(), c.end());
+        }
+    }
+    out.second.resize(num_column_opening);
+    for (auto &c : out.second) c = (uint32_t)transcript.squeeze_challenge_idx(field, codeword_len);  // open_z.rs:116-120
+    return out;
+}
+
 void MultilinearZip::open(const MultilinearZipParams &pp, const int64_t *evals, size_t n_evals, uint32_t poly_num_vars,
                           const MultilinearZipData &commit_data, const Limbs *point, size_t point_len,
                           const FieldConfig &field, PcsTranscript &transcript) {
@@ -821,14 +850,11 @@ void MultilinearZip::open(const MultilinearZipParams &pp, const int64_t *evals, 
 
     // ---- everything the transcript yields BEFORE the first absorb (write_integers and
     // write_merkle_proof never absorb: pcs_transcript.rs:115-135,198-211), in the reference's order
-    std::vector<int64_t> coeffs;
-    if (num_rows > 1) {  // prove_testing_phase, open_z.rs:100-113 (num_proximity_testing == 1 on this path)
-        if (pp.linear_code.num_proximity_testing != 1)
-            throw ZipError(ZipError::InvalidPcsParam, "only one proximity test is supported on the device path");
-        coeffs = transcript.fs_transcript.get_integer_challenges_i64(num_rows);
-    }
-    std::vector<uint32_t> cols(pp.linear_code.num_column_opening);
-    for (auto &c : cols) c = (uint32_t)transcript.squeeze_challenge_idx(field, cw);  // open_z.rs:116-120
+    // (the ctx of setup() carries the spec's count of proximity tests: the stream gets one u' per test)
+    auto challenges = open_challenges(num_rows, cw, pp.linear_code.num_column_opening, pp.linear_code.num_proximity_testing,
+                                      field, transcript);
+    const std::vector<int64_t> &coeffs = challenges.first;   // [tests][num_rows]
+    const std::vector<uint32_t> &cols = challenges.second;
     // left_point_to_tensor (pcs/utils.rs:279-292): eq over the LAST log2(num_rows) coordinates
     std::vector<uint64_t> q0;
     if (num_rows > 1) {
@@ -1028,14 +1054,10 @@ void MultilinearZip::verify(const MultilinearZipParams &vp, const MultilinearZip
     if (comm.roots.size() != num_rows) throw ZipError(ZipError::InvalidPcsOpen, "commitment has the wrong number of roots");
     zip_ctx *ctx = vp.ctx.get();
     // the challenges in the order verify_testing draws them (verify_z.rs:69-90); reads never absorb
-    std::vector<int64_t> coeffs;
-    if (num_rows > 1) {
-        if (vp.linear_code.num_proximity_testing != 1)
-            throw ZipError(ZipError::InvalidPcsParam, "only one proximity test is supported on the device path");
-        coeffs = transcript.fs_transcript.get_integer_challenges_i64(num_rows);
-    }
-    std::vector<uint32_t> cols(vp.linear_code.num_column_opening);
-    for (auto &c : cols) c = (uint32_t)transcript.squeeze_challenge_idx(field, cw);
+    auto challenges = open_challenges(num_rows, cw, vp.linear_code.num_column_opening, vp.linear_code.num_proximity_testing,
+                                      field, transcript);
+    const std::vector<int64_t> &coeffs = challenges.first;   // [tests][num_rows]
+    const std::vector<uint32_t> &cols = challenges.second;
     std::vector<uint64_t> q0, q1;
     point_to_tensor(field, num_rows, point, point_len, q0, q1);
     const zip_field zf = field.to_abi();

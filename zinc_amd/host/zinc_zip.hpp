@@ -274,7 +274,19 @@ struct MultilinearZip {
     // commit.rs:104-119
     static MultilinearZipData commit_no_merkle(const MultilinearZipParams &pp, const int64_t *evals, size_t n_evals,
                                                uint32_t poly_num_vars);
-    // open_z.rs:22-40.  point: num_vars field elements in Montgomery form.
+    // The squeezes of prove_testing_phase / verify_testing and nothing else (open_z.rs:100-120, verify_z.rs:66-90): per
+    // proximity test, in order, get_integer_challenges(num_rows) -- only if num_rows > 1: a one-row matrix has no test
+    // whatever the spec says --, then num_column_opening times squeeze_challenge_idx(codeword_len).  Nothing between the
+    // first squeeze and the evaluation row absorbs, so this is all the Fiat-Shamir work in front of the device call.
+    // Returns (coeffs [tests][num_rows], cols).  Throws ZipError{InvalidPcsParam} for num_proximity_testing outside
+    // 1 .. 8 when num_rows > 1 (what the device path serves).  Host only; open and verify call it.
+    static std::pair<std::vector<int64_t>, std::vector<uint32_t>> open_challenges(uint32_t num_rows, uint32_t codeword_len,
+                                                                                 uint32_t num_column_opening,
+                                                                                 uint32_t num_proximity_testing,
+                                                                                 const FieldConfig &field,
+                                                                                 PcsTranscript &transcript);
+    // open_z.rs:22-40.  point: num_vars field elements in Montgomery form.  A spec with num_proximity_testing = T > 1
+    // writes T proximity rows (the ctx of setup() is set to T: zip_ctx_set_proximity_tests).
     static void open(const MultilinearZipParams &pp, const int64_t *evals, size_t n_evals, uint32_t poly_num_vars,
                      const MultilinearZipData &commit_data, const Limbs *point, size_t point_len,
                      const FieldConfig &field, PcsTranscript &transcript);

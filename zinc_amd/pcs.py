@@ -14,6 +14,8 @@ OK, ERR_INVALID_PARAM, ERR_PANIC, ERR_DEVICE, ERR_NULL, ERR_INVALID_OPEN, ERR_SP
 ERR_FIELD_CONFIG = -7
 
 EXPORTED_SYMBOLS = (
+    "zinc_raa_code_new_spec", "zinc_zip_open_challenges", "zinc_commit_z_mle_and_prove_evaluation_spec",
+    "zinc_prover_prove_spec", "zinc_verifier_verify_spec", "zinc_verifier_verify_checked_spec",
     "zinc_last_error", "zinc_transcript_new", "zinc_transcript_free", "zinc_transcript_absorb",
     "zinc_transcript_get_u64", "zinc_transcript_get_integer_challenges", "zinc_transcript_get_challenge",
     "zinc_transcript_export", "zinc_transcript_import",
@@ -55,6 +57,19 @@ class ReferencePanic(AssertionError):
 
 class DeviceError(RuntimeError):
     pass
+
+
+class LinearCodeSpec(C.Structure):
+    """LinearCodeSpec (src/zip/code.rs:217-242); the defaults are DefaultLinearCodeSpec.  num_proximity_testing = T in
+    1 .. 8 reaches the device: T proximity rows in the proof, every one checked by the verifier."""
+    _fields_ = [("num_column_opening", C.c_uint32), ("repetition_factor", C.c_uint32), ("num_proximity_testing", C.c_uint32)]
+
+    def __init__(self, num_column_opening=1000, repetition_factor=2, num_proximity_testing=1):
+        super().__init__(num_column_opening, repetition_factor, num_proximity_testing)
+
+
+def _spec_ptr(spec):
+    return C.byref(spec) if spec is not None else None
 
 
 class RaaCodeStruct(C.Structure):
@@ -148,6 +163,14 @@ def lib():
                                            C.c_int32, vp, vp, vp, vp, C.c_int32, vp, C.c_size_t, vp, vp, C.c_size_t,
                                            vp, vp, vp]
         L.zinc_verifier_verify_checked.argtypes = [vp, C.c_size_t, C.c_int32] + L.zinc_verifier_verify.argtypes
+        # the _spec variants: the LinearCodeSpec first (NULL = the default), then the arguments of the plain function
+        sp = C.POINTER(LinearCodeSpec)
+        L.zinc_raa_code_new_spec.argtypes = [sp] + L.zinc_raa_code_new.argtypes
+        L.zinc_commit_z_mle_and_prove_evaluation_spec.argtypes = [sp] + L.zinc_commit_z_mle_and_prove_evaluation.argtypes
+        L.zinc_prover_prove_spec.argtypes = [sp] + L.zinc_prover_prove.argtypes
+        L.zinc_verifier_verify_spec.argtypes = [sp] + L.zinc_verifier_verify.argtypes
+        L.zinc_verifier_verify_checked_spec.argtypes = [sp] + L.zinc_verifier_verify_checked.argtypes
+        L.zinc_zip_open_challenges.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -285,11 +308,11 @@ def shuffle_seeded_perm(seed: int, length: int) -> np.ndarray:
 
 
 class RaaCode:
-    """RaaCode::new(&DefaultLinearCodeSpec, poly_size, transcript); transcript=None -> MockTranscript."""
+    """RaaCode::new(spec, poly_size, transcript); spec=None -> DefaultLinearCodeSpec, transcript=None -> MockTranscript."""
 
-    def __init__(self, poly_size: int, transcript: KeccakTranscript = None):
+    def __init__(self, poly_size: int, transcript: KeccakTranscript = None, spec: "LinearCodeSpec" = None):
         self.s = RaaCodeStruct()
-        _check(lib().zinc_raa_code_new(poly_size, transcript._h if transcript else None, C.byref(self.s)))
+        _check(lib().zinc_raa_code_new_spec(_spec_ptr(spec), poly_size, transcript._h if transcript else None, C.byref(self.s)))
         self.poly_size = poly_size
 
     row_len = property(lambda self: self.s.row_len)
@@ -490,6 +513,20 @@ class MultilinearZip:
                                            field.limbs, transcript._h))
 
     @staticmethod
+    def open_challenges(num_rows: int, codeword_len: int, num_column_opening: int, num_proximity_testing: int,
+                        field: "FieldConfig", transcript: "PcsTranscript"):
+        """The squeezes of prove_testing_phase / verify_testing and nothing else (host only): per proximity test
+        get_integer_challenges(num_rows) if num_rows > 1, then the column indices -> (coeffs [T, num_rows] or None, cols).
+        InvalidPcsParam for num_proximity_testing outside 1 .. 8 when num_rows > 1."""
+        n_coeffs = num_proximity_testing * num_rows if num_rows > 1 and 1 <= num_proximity_testing <= 8 else 0
+        coeffs = np.zeros(max(n_coeffs, 1), np.int64)
+        cols = np.zeros(max(num_column_opening, 1), np.uint32)
+        _check(lib().zinc_zip_open_challenges(num_rows, codeword_len, num_column_opening, num_proximity_testing,
+                                              field._m.ctypes.data, field.limbs, transcript._h, coeffs.ctypes.data,
+                                              cols.ctypes.data))
+        return (coeffs[:n_coeffs].reshape(num_proximity_testing, num_rows) if n_coeffs else None), cols[:num_column_opening]
+
+    @staticmethod
     def open(pp: MultilinearZipParams, evaluations, commit_data: MultilinearZipData, point: np.ndarray,
              field: FieldConfig, transcript: PcsTranscript, num_vars: int = None):
         ev = np.ascontiguousarray(evaluations, dtype=np.int64)
@@ -520,14 +557,14 @@ class MultilinearZip:
 
 
 def commit_z_mle_and_prove_evaluation(z_evals, r_y: np.ndarray, transcript: KeccakTranscript, field: FieldConfig,
-                                      device: int = 0):
+                                      device: int = 0, spec: "LinearCodeSpec" = None):
     """ZincProver::commit_z_mle_and_prove_evaluation (src/zinc/prover.rs:305-327) -> (roots, v, pcs_proof)."""
     ev = np.ascontiguousarray(z_evals, dtype=np.int64)
     pt = np.ascontiguousarray(r_y, dtype=np.uint64).reshape(-1, field.limbs) if np.size(r_y) else np.zeros((0, field.limbs), np.uint64)
     h = C.c_void_p()
-    _check(lib().zinc_commit_z_mle_and_prove_evaluation(ev.ctypes.data, ev.size, pt.ctypes.data, pt.shape[0],
-                                                        transcript._h, field._m.ctypes.data, field.limbs, device,
-                                                        C.byref(h)))
+    _check(lib().zinc_commit_z_mle_and_prove_evaluation_spec(_spec_ptr(spec), ev.ctypes.data, ev.size, pt.ctypes.data,
+                                                             pt.shape[0], transcript._h, field._m.ctypes.data, field.limbs,
+                                                             device, C.byref(h)))
     try:
         roots = np.zeros((lib().zinc_zip_proof_num_roots(h), 32), np.uint8)
         v = np.zeros(field.limbs, np.uint64)
@@ -608,10 +645,12 @@ class ZincProver:
     """ZincProver (src/zinc/structs.rs:33-47, src/zinc/prover.rs).  A CCS is given as
       matrices  Statement_Z.constraints: objects with n_rows, n_cols, row_ptr, col_idx (uint32), values (int64)  [CSR]
       s, d, S, c  CCS_Z with m = n = 2^s = 2^s_prime
-      public_input, w_ccs  Statement_Z.public_input, Witness_Z.w_ccs (z = x || 1 || w)"""
+      public_input, w_ccs  Statement_Z.public_input, Witness_Z.w_ccs (z = x || 1 || w)
+    spec: the LinearCodeSpec of ZincProver::new (None: the default)."""
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, spec: "LinearCodeSpec" = None):
         self.device = device
+        self.spec = spec
 
     @staticmethod
     def _abi_matrices(matrices):
@@ -639,7 +678,7 @@ class ZincProver:
         out = dict(msgs1=np.zeros((s, d + 2, fl), np.uint64), msgs2=np.zeros((s, 3, fl), np.uint64),
                    V_s=np.zeros((t, fl), np.uint64), r_y=np.zeros((s, fl), np.uint64))
         h = C.c_void_p()
-        _check(lib().zinc_prover_prove(arr, t, s, d, len(S), masks.ctypes.data, cv.ctypes.data, x.ctypes.data, x.size,
+        _check(lib().zinc_prover_prove_spec(_spec_ptr(self.spec), arr, t, s, d, len(S), masks.ctypes.data, cv.ctypes.data, x.ctypes.data, x.size,
                                        w.ctypes.data, w.size, transcript._h, field._m.ctypes.data, fl, self.device,
                                        prepared._h if prepared is not None else None, 1 if with_pcs else 0, out["msgs1"].ctypes.data, out["msgs2"].ctypes.data,
                                        out["V_s"].ctypes.data, out["r_y"].ctypes.data, C.byref(h)))
@@ -667,10 +706,12 @@ class ZincProver:
 
 class ZincVerifier:
     """ZincVerifier (src/zinc/verifier.rs).  The draw_random_field check of Verifier::verify (:53-57) runs when `verify`
-    is given the public input; without it the verifier takes the field it is handed."""
+    is given the public input; without it the verifier takes the field it is handed.
+    spec: the LinearCodeSpec of ZincVerifier::new (None: the default); it must be the prover's."""
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, spec: "LinearCodeSpec" = None):
         self.device = device
+        self.spec = spec
 
     def _run(self, matrices, s, d, S, c, proof, transcript, field, with_pcs, prepared, public_input=None):
         t, fl = len(matrices), field.limbs
@@ -689,7 +730,7 @@ class ZincVerifier:
             roots = np.ascontiguousarray(zp["z_comm"], dtype=np.uint8)
             v = np.ascontiguousarray(zp["v"], dtype=np.uint64)
             pp = np.ascontiguousarray(zp["pcs_proof"], dtype=np.uint8)
-        _check(lib().zinc_verifier_verify_checked(x.ctypes.data if x is not None and x.size else None, x.size if x is not None else 0,
+        _check(lib().zinc_verifier_verify_checked_spec(_spec_ptr(self.spec), x.ctypes.data if x is not None and x.size else None, x.size if x is not None else 0,
                                                   0 if x is None else 1, arr, t, s, d, len(S), masks.ctypes.data, cv.ctypes.data, transcript._h,
                                           field._m.ctypes.data, fl, self.device,
                                           prepared._h if prepared is not None else None, m1.ctypes.data, m2.ctypes.data,
