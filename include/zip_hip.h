@@ -44,7 +44,8 @@ extern "C" {
  * up to 8 tables instead of 4: a widening, every call that was valid means what it meant.  The batch entry points,
  * zip_batch_commit and the five beside it, are additive in the same way, and so are zip_batch_verify and
  * zip_batch_verify_calls.  So are zip_prime_test_base2, zip_get_prime and zip_prime_launch_counts, and
- * zip_ctx_set_proximity_tests / zip_ctx_proximity_tests: a ctx that never calls the setter behaves as before.) */
+ * zip_ctx_set_proximity_tests / zip_ctx_proximity_tests: a ctx that never calls the setter behaves as before.  So is
+ * zip_sumcheck_init_products.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -464,6 +465,30 @@ int32_t zip_sumcheck_prove(zip_sumcheck *s, zip_keccak_state *transcript, uint64
  * point) and launches of the tail kernel.  Every path gives the same bytes; tests and tools read the path taken here.
  * Either pointer may be NULL. */
 void zip_sumcheck_launch_counts(uint64_t *round_kernel_rounds, uint64_t *tail_kernel_launches);
+
+/* A sum of products in ONE handle: the polynomial of rand_poly / rand_poly_comb_fn (src/sumcheck/utils.rs:27-78, what
+ * benches/sumcheck_benches.rs and src/sumcheck/tests.rs prove),
+ *   comb_fn(vals) = sum_t coeff[t] * prod_{j in term_mask[t]} vals[j]
+ * with NO trailing factor; `products` is a zip_sumcheck_comb whose n_terms is the number of products.  One kernel per
+ * round reads every table once and folds it once, whatever the number of products that share it.
+ *   n_mles    1..32 tables; products->n_terms 1..8; every term_mask has 1..4 bits set, none at or above n_mles.
+ *             Masks may overlap and may repeat.  A table that belongs to no product is neither read nor folded (its
+ *             pointer must still not be NULL).
+ *   degree    1..4; it may exceed the largest product (rand_poly hands over the maximum it could have drawn)
+ *   num_vars  1..30
+ * Usage errors are those of zip_sumcheck_init, with the same codes and in the same order, before the device is touched:
+ * ZIP_ERR_NULL for mles, out, field or products; then ZIP_ERR_INVALID_PARAM for n_terms, for n_mles / degree /
+ * num_vars, for a mask.  HOST tables are copied, DEVICE tables are read in place and never written.
+ * The handle is an ordinary zip_sumcheck: zip_sumcheck_round, zip_sumcheck_round_begin / _end, zip_sumcheck_prove,
+ * zip_sumcheck_last_error and zip_sumcheck_free work on it as documented above.  zip_sumcheck_prove plays EVERY round
+ * of such a handle through the round kernel and steps the sponge on the host (what ZIP_HIP_SUMCHECK_TAIL=0 does for the
+ * other handles): the tail kernel does not know this combination function, so tail_kernel_launches does not move and
+ * round_kernel_rounds grows by num_vars.  Not built: the tail kernel for this form, more than 8 products or 32 tables
+ * in one handle (the host mirror keeps its loop of one handle per product for those).
+ * Additive: the ABI version stays 3. */
+int32_t zip_sumcheck_init_products(int32_t device, const uint64_t *const *mles, zip_mem_kind kind, uint32_t n_mles,
+                                   uint32_t num_vars, uint32_t degree, const zip_sumcheck_comb *products,
+                                   const zip_field *field, zip_sumcheck **out);
 
 /* ---- the random field: prime_gen::get_prime (src/prime_gen.rs:15-28) ---------------------------------------------
  * draw_random_field (src/zinc/utils.rs:161-171) absorbs the public inputs and calls get_prime: hash a candidate of

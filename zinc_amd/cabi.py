@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = (
     "zip_mctx_create", "zip_mctx_destroy", "zip_mctx_last_error", "zip_mctx_shards", "zip_mctx_shard_ctx", "zip_mctx_set_witness",
     "zip_mctx_commit_open", "zip_mctx_shard_openings", "zip_mctx_ends", "zip_mctx_roots", "zip_mctx_roots_path", "zip_verify", "zip_mle_eval", "zip_commitment_mle_eval", "zip_field_map_int256",
     "zip_open_stream", "zip_sumcheck_init", "zip_sumcheck_round", "zip_sumcheck_round_begin", "zip_sumcheck_round_end", "zip_sumcheck_last_error", "zip_sumcheck_free",
-    "zip_sumcheck_prove", "zip_sumcheck_launch_counts",
+    "zip_sumcheck_prove", "zip_sumcheck_launch_counts", "zip_sumcheck_init_products",
     "zip_ccs_create", "zip_ccs_free", "zip_ccs_last_error", "zip_ccs_set_z", "zip_ccs_eq_table",
     "zip_ccs_second_table", "zip_ccs_table", "zip_ccs_download", "zip_ccs_eval_matrices",
     "zip_batch_commit", "zip_batch_size", "zip_batch_free", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open",
@@ -224,6 +224,7 @@ def lib():
                                   vp, C.c_size_t]
     L.zip_sumcheck_init.argtypes = [C.c_int32, vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SumcheckComb),
                                     C.POINTER(ZipField), C.POINTER(vp)]
+    L.zip_sumcheck_init_products.argtypes = L.zip_sumcheck_init.argtypes
     L.zip_sumcheck_round.argtypes = [vp, u64p, u64p]
     L.zip_sumcheck_round_begin.argtypes = [vp, u64p]
     L.zip_sumcheck_round_end.argtypes = [vp, u64p]
@@ -946,9 +947,10 @@ def prime_launch_counts():
 
 class Sumcheck:
     """Device prover state of one sumcheck (zip_sumcheck_*): product of the MLEs, or the CCS form `comb`.  mles: list of CUDA int64/uint64 tensors
-    (read in place) or one numpy array [K, 2^nv, limbs] (copied)."""
+    (read in place) or one numpy array [K, 2^nv, limbs] (copied).  products=True (zip_sumcheck_init_products): `comb`
+    is a sum of products with no trailing factor, sum_t coeff[t] * prod_{j in term_mask[t]} vals[j], over up to 32 MLEs."""
 
-    def __init__(self, mles, num_vars, degree, field: ZipField, device=0, comb: "SumcheckComb" = None):
+    def __init__(self, mles, num_vars, degree, field: ZipField, device=0, comb: "SumcheckComb" = None, products=False):
         self.field, self.degree, self.num_vars = field, degree, num_vars
         if isinstance(mles, np.ndarray):
             self._keep = np.ascontiguousarray(mles, dtype=np.uint64)
@@ -960,10 +962,11 @@ class Sumcheck:
             kind = MEM_DEVICE
         arr = (C.c_void_p * len(ptrs))(*ptrs)
         h = C.c_void_p()
-        rc = lib().zip_sumcheck_init(device, arr, kind, len(ptrs), num_vars, degree,
-                                     C.byref(comb) if comb is not None else None, C.byref(field), C.byref(h))
+        init = lib().zip_sumcheck_init_products if products else lib().zip_sumcheck_init
+        rc = init(device, arr, kind, len(ptrs), num_vars, degree, C.byref(comb) if comb is not None else None, C.byref(field),
+                  C.byref(h))
         if rc != ZIP_OK:
-            raise ZipError(rc, "zip_sumcheck_init", strerror(rc))
+            raise ZipError(rc, "zip_sumcheck_init_products" if products else "zip_sumcheck_init", strerror(rc))
         self._h = h
 
     def round(self, r_prev=None):

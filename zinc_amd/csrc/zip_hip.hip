@@ -33,6 +33,7 @@
 #include "kernels_sumcheck.cuh"
 #include "kernels_sumcheck_tail.cuh"
 #include "kernels_sumcheck_wide.cuh"
+#include "kernels_sumcheck_products.cuh"
 #include "kernels_spartan.cuh"
 #include "kernels_prime.cuh"
 #include "rccl_dyn.h"
@@ -268,9 +269,9 @@ struct zip_sumcheck {
     bool pending = false;  // a round has been enqueued (zip_sumcheck_round_begin) and not yet collected
     bool proved = false;   // zip_sumcheck_prove has run: the handle is finished
     uint64_t *tail_out_d = nullptr;  // what sumcheck_tail_kernel writes out (kTailOutBytes)
-    const uint64_t *input[kSumcheckMaxMles] = {};  // the tables of round 1 (device; owned when `owned`)
+    const uint64_t *input[kSumcheckProductsMaxMles] = {};  // the tables of round 1 (device; owned when `owned`)
     bool owned = false;
-    uint64_t *buf[2][kSumcheckMaxMles] = {};  // ping-pong fold targets: 2^(nv-1) and 2^(nv-2) entries
+    uint64_t *buf[2][kSumcheckProductsMaxMles] = {};  // ping-pong fold targets: 2^(nv-1) and 2^(nv-2) entries
     uint64_t *partials = nullptr, *evals_d = nullptr;
     uint32_t *done_d = nullptr;          // arrival counter of the round kernel
     unsigned char *evals_pinned = nullptr;  // host-mapped slot the round message is written to (or null: evals_d + a copy)
@@ -279,6 +280,10 @@ struct zip_sumcheck {
     uint64_t mont_r[8] = {}, mont_r2[8] = {}, mont_inv = 0;  // Montgomery constants, computed once (512 modular doublings)
     uint32_t n_terms = 0, term_mask[8] = {};  // zip_sumcheck_comb, or n_terms == 0 for the plain product
     uint64_t coeff[8][8] = {};
+    // zip_sumcheck_init_products: comb_fn = sum_t coeff[t] * prod_{j in term_mask[t]} vals[j], no trailing factor
+    // (sumcheck_round_products_kernel).  n_factors / factors / own: SumcheckProductsArgs.
+    bool products = false;
+    uint32_t n_factors[8] = {}, factors[8] = {}, own[8] = {};
 };
 
 // CCS matrices and the per-proof tables of SpartanProver::prove (src/zinc/prover.rs:130-161) in HBM.
@@ -2098,6 +2103,69 @@ int32_t sumcheck_round_fl(zip_sumcheck *s, const uint64_t *r_prev, const HostFie
     }
 }
 
+// A zip_sumcheck_init_products handle: one sumcheck_round_products_kernel per round over all tables, eight lanes per
+// hypercube point, 32 points per workgroup.  Grid and reduction as launch_sumcheck_wide.
+template <int FL>
+int32_t sumcheck_round_products_fl(zip_sumcheck *s, const uint64_t *r_prev, const HostField &hf) {
+    zip_ctx *ctx = s->ctx;
+    SumcheckProductsArgs<FL> a{};
+    const uint32_t round = s->round + 1;  // 1-based
+    a.degree = s->degree;
+    a.half = (uint64_t)1 << (s->num_vars - round);
+    a.fold = round > 1;
+    a.partials = s->partials;
+    a.evals_out = s->evals_pinned ? reinterpret_cast<uint64_t *>(s->evals_pinned) : s->evals_d;
+    a.host_flag = s->evals_pinned ? reinterpret_cast<uint32_t *>(s->evals_pinned + 192) : nullptr;
+    a.seq = round;
+    a.n_products = s->n_terms;
+    uint64_t minus_one[8] = {0};
+    for (int i = 0; i < FL; i++) minus_one[i] = hf.modulus[i];
+    sub_limbs(minus_one, hf.r, FL);  // q - R
+    for (uint32_t t = 0; t < s->n_terms; t++) {
+        a.n_factors[t] = s->n_factors[t];
+        a.factors[t] = s->factors[t];
+        a.own[t] = s->own[t];
+        for (int i = 0; i < FL; i++) a.coeff[t][i] = s->coeff[t][i];
+        // (a single factor has no running term to negate or to start from: its coefficient is a multiplicand)
+        a.coeff_kind[t] = s->n_factors[t] < 2 ? 0u : !cmp_limbs(s->coeff[t], hf.r, FL) ? 1u : !cmp_limbs(s->coeff[t], minus_one, FL) ? 2u : 0u;
+    }
+    for (uint32_t k = 0; k < s->n_mles; k++) {  // the ping-pong of sumcheck_round_fl; an unused MLE has no tables at all
+        if (round == 1) a.src[k] = s->input[k];
+        else if (round == 2) { a.src[k] = s->input[k]; a.dst[k] = s->buf[0][k]; }
+        else { a.src[k] = s->buf[(round - 3) & 1][k]; a.dst[k] = s->buf[(round - 2) & 1][k]; }
+    }
+    if (a.fold)
+        for (int i = 0; i < FL; i++) a.r[i] = r_prev[i];
+    const FieldDev<FL> fd = to_dev<FL>(hf);
+    const size_t lds = (size_t)256 * FL * 8;
+    const uint64_t want = (a.half * kSumcheckWideLanes + 255) / 256;
+    uint32_t blocks = (uint32_t)std::min<uint64_t>(want ? want : 1, s->max_blocks);
+    if (blocks > ctx->num_cus) {  // exactly the workgroups that are resident together (grid-stride loop inside)
+        static std::mutex mu;
+        static std::map<std::pair<const void *, int>, int> occ;
+        const void *kern = reinterpret_cast<const void *>(sumcheck_round_products_kernel<FL>);
+        std::lock_guard<std::mutex> g(mu);
+        int &per_cu = occ[std::make_pair(kern, ctx->device)];
+        if (per_cu == 0 &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sumcheck_round_products_kernel<FL>, 256, lds) != hipSuccess)
+            per_cu = 0;
+        if (per_cu > 0) blocks = std::min<uint32_t>(blocks, ctx->num_cus * (uint32_t)per_cu);
+    }
+    a.done = blocks <= 64 ? s->done_d : nullptr;  // small rounds: one launch, the last workgroup folds the partials
+    {
+        LaunchTimer t(ctx, "sumcheck_round_products_kernel");
+        hipLaunchKernelGGL(sumcheck_round_products_kernel<FL>, dim3(blocks), dim3(256), lds, ctx->stream, a, fd);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (!a.done) {
+        LaunchTimer t(ctx, "sumcheck_reduce_kernel");
+        hipLaunchKernelGGL(sumcheck_reduce_kernel<FL>, dim3(1), dim3(256), 0, ctx->stream, a.partials, blocks, a.degree + 1, a.evals_out, fd,
+                           a.host_flag, a.seq);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return ZIP_OK;
+}
+
 // ---- zip_sumcheck_prove: the transcript of MLSumcheck::prove_as_subprotocol inside the library ---------------------------
 // Messages, challenges and the sponge of at most kTailMaxLog tail rounds
 constexpr size_t kTailOutBytes = ((size_t)kTailMaxLog * (kSumcheckMaxDegree + 2) * 4 + 25 + kKeccakRateWords + 1) * 8;
@@ -2136,7 +2204,9 @@ int32_t sumcheck_prove_fl(zip_sumcheck *s, zip_keccak_state *transcript, uint64_
     // kernel; more than fits the LDS for this shape: as much as fits.  (Per call: the tests flip it.)
     const uint32_t bound = tail_lds_bound(s->n_mles, FL);
     const uint32_t knob = (uint32_t)env_long("ZIP_HIP_SUMCHECK_TAIL", bound, 0, kTailMaxLog);
-    const uint32_t n_tail = std::min(std::min(knob, bound), nv);
+    // (a zip_sumcheck_init_products handle: sumcheck_tail_kernel does not know its combination function -- every round
+    // goes through the round kernel and the sponge stays on this thread)
+    const uint32_t n_tail = s->products ? 0u : std::min(std::min(knob, bound), nv);
     uint64_t r[FL] = {};
     for (uint32_t round = 0; round < nv - n_tail; round++) {  // the kernels and launch logic of zip_sumcheck_round
         uint64_t *msg = msgs_out + (size_t)round * ne * FL;
@@ -4719,6 +4789,10 @@ int32_t zip_open_stream(zip_commitment *c, const int64_t *evals, zip_mem_kind ev
     return check_timeout(ctx);
 }
 
+static int32_t sumcheck_create(int32_t device, const uint64_t *const *mles, zip_mem_kind kind, uint32_t n_mles, uint32_t num_vars,
+                               uint32_t degree, const zip_sumcheck_comb *comb, bool products, const zip_field *field,
+                               zip_sumcheck **out);
+
 int32_t zip_sumcheck_init(int32_t device, const uint64_t *const *mles, zip_mem_kind kind, uint32_t n_mles,
                           uint32_t num_vars, uint32_t degree, const zip_sumcheck_comb *comb, const zip_field *field,
                           zip_sumcheck **out) {
@@ -4731,6 +4805,31 @@ int32_t zip_sumcheck_init(int32_t device, const uint64_t *const *mles, zip_mem_k
     if (comb)  // a term that refers to an MLE that does not exist
         for (uint32_t t = 0; t < comb->n_terms; t++)
             if (comb->term_mask[t] >> n_mles) return ZIP_ERR_INVALID_PARAM;
+    return sumcheck_create(device, mles, kind, n_mles, num_vars, degree, comb, false, field, out);
+}
+
+int32_t zip_sumcheck_init_products(int32_t device, const uint64_t *const *mles, zip_mem_kind kind, uint32_t n_mles,
+                                   uint32_t num_vars, uint32_t degree, const zip_sumcheck_comb *products,
+                                   const zip_field *field, zip_sumcheck **out) {
+    if (!mles || !out || !field) return ZIP_ERR_NULL;
+    *out = nullptr;
+    if (!products) return ZIP_ERR_NULL;
+    if (products->n_terms < 1 || products->n_terms > 8) return ZIP_ERR_INVALID_PARAM;
+    if (n_mles < 1 || n_mles > (uint32_t)kSumcheckProductsMaxMles || degree < 1 || degree > (uint32_t)kSumcheckMaxDegree ||
+        num_vars < 1 || num_vars > 30)
+        return ZIP_ERR_INVALID_PARAM;
+    for (uint32_t t = 0; t < products->n_terms; t++) {  // 1..4 multiplicands, all of them among the tables
+        const uint32_t m = products->term_mask[t];
+        const int bits = __builtin_popcount(m);
+        if (bits < 1 || bits > kSumcheckProductsMaxFactors || ((uint64_t)m >> n_mles)) return ZIP_ERR_INVALID_PARAM;
+    }
+    return sumcheck_create(device, mles, kind, n_mles, num_vars, degree, products, true, field, out);
+}
+
+// what zip_sumcheck_init and zip_sumcheck_init_products share: the arguments have been checked
+static int32_t sumcheck_create(int32_t device, const uint64_t *const *mles, zip_mem_kind kind, uint32_t n_mles, uint32_t num_vars,
+                               uint32_t degree, const zip_sumcheck_comb *comb, bool products, const zip_field *field,
+                               zip_sumcheck **out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ZIP_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
@@ -4760,9 +4859,29 @@ int32_t zip_sumcheck_init(int32_t device, const uint64_t *const *mles, zip_mem_k
                 memcpy(s->coeff[t], comb->coeff[t], sizeof s->coeff[t]);
             }
         }
+        uint32_t used = n_mles >= 32 ? ~0u : (1u << n_mles) - 1u;  // the tables that are read at all
+        if (products) {
+            // factor lists, and who writes the folded table of an MLE that several products share: the lowest-numbered one
+            s->products = true;
+            used = 0;
+            for (uint32_t t = 0; t < comb->n_terms; t++) {
+                uint32_t nf = 0, first = 0;
+                for (uint32_t k = 0; k < n_mles; k++) {
+                    if (!((comb->term_mask[t] >> k) & 1u)) continue;
+                    if (nf == 0) first = k;
+                    s->factors[t] |= k << (8 * nf);
+                    if (!((used >> k) & 1u)) s->own[t] |= 1u << nf;
+                    used |= 1u << k;
+                    nf++;
+                }
+                s->n_factors[t] = nf;
+                for (uint32_t j = nf; j < (uint32_t)kSumcheckProductsMaxFactors; j++) s->factors[t] |= first << (8 * j);
+            }
+        }
         const size_t n = (size_t)1 << num_vars, elem = (size_t)hf.fl * 8;
         for (uint32_t k = 0; k < n_mles && rc == ZIP_OK; k++) {
             if (!mles[k]) { rc = ZIP_ERR_NULL; break; }
+            if (!((used >> k) & 1u)) continue;  // in no product: neither copied, read nor folded
             if (kind == ZIP_MEM_HOST) {
                 void *d = nullptr;
                 if ((rc = pool_alloc(ctx, n * elem, &d))) break;
@@ -4812,7 +4931,11 @@ int32_t zip_sumcheck_round_begin(zip_sumcheck *s, const uint64_t *r_prev) {
     memcpy(hf.r, s->mont_r, sizeof hf.r);
     memcpy(hf.r2, s->mont_r2, sizeof hf.r2);
     hf.inv = s->mont_inv;
-    if (int32_t rc = with_fl(s->fl, [&](auto FL) { return sumcheck_round_fl<decltype(FL)::value>(s, r_prev, hf); })) return rc;
+    if (int32_t rc = with_fl(s->fl, [&](auto FL) {
+            return s->products ? sumcheck_round_products_fl<decltype(FL)::value>(s, r_prev, hf)
+                               : sumcheck_round_fl<decltype(FL)::value>(s, r_prev, hf);
+        }))
+        return rc;
     g_sumcheck_round_launches++;
     s->round++;
     s->pending = true;

@@ -1222,7 +1222,7 @@ namespace {
 sumcheck::ProverOutput prove_as_subprotocol_impl(KeccakTranscript &transcript, const std::vector<const uint64_t *> &mles,
                                                  uint32_t nvars, uint32_t degree, const zip_sumcheck_comb *comb,
                                                  const FieldConfig &config, int device,
-                                                 zip_mem_kind kind = ZIP_MEM_HOST) {
+                                                 zip_mem_kind kind = ZIP_MEM_HOST, bool products = false) {
     sumcheck::ProverOutput out;
     // ZIP_HIP_SUMCHECK_ONECALL=1 (read per call: the tests flip it): the whole loop is ONE zip_sumcheck_prove call --
     // the library borrows the sponge, the tail of the rounds runs in one kernel (zip_hip.h).  Default (and =0): the
@@ -1236,9 +1236,11 @@ sumcheck::ProverOutput prove_as_subprotocol_impl(KeccakTranscript &transcript, c
     if (nvars == 0) return out;  // :77-92: empty proof
     const zip_field zf = config.to_abi();
     zip_sumcheck *raw = nullptr;
-    int32_t rc = zip_sumcheck_init(device, mles.data(), kind, (uint32_t)mles.size(), nvars, degree, comb, &zf, &raw);
+    // products: `comb` is a sum of products with no trailing factor, all of it in one handle (zip_hip.h)
+    int32_t rc = (products ? zip_sumcheck_init_products : zip_sumcheck_init)(device, mles.data(), kind, (uint32_t)mles.size(), nvars,
+                                                                             degree, comb, &zf, &raw);
     if (rc) throw ZipError(rc == ZIP_ERR_INVALID_PARAM ? ZipError::InvalidPcsParam : ZipError::Device,
-                           std::string("zip_sumcheck_init: ") + zip_strerror(rc));
+                           std::string(products ? "zip_sumcheck_init_products: " : "zip_sumcheck_init: ") + zip_strerror(rc));
     std::unique_ptr<zip_sumcheck, void (*)(zip_sumcheck *)> s(raw, zip_sumcheck_free);
     if (!per_round) {
         zip_keccak_state st;
@@ -1315,11 +1317,26 @@ sumcheck::ProverOutput sumcheck::prove_as_subprotocol_ccs(KeccakTranscript &tran
     return prove_as_subprotocol_impl(transcript, mles, nvars, degree, &comb, config, device);
 }
 
+namespace {
+// ZIP_HIP_SUMCHECK_FUSED (read per call: the tests flip it): 1 = a sum of products that one handle can hold goes through
+// zip_sumcheck_init_products, 0 = always the loop of one handle per product.  Unset: kSumcheckFusedDefault
+// (profiles/sumcheck_products.md).
+constexpr bool kSumcheckFusedDefault = true;
+bool env_flag(const char *e, bool def) {
+    if (e && (e[0] == '0' || e[0] == '1') && !e[1]) return e[0] == '1';
+    return def;
+}
+}  // namespace
+
 sumcheck::ProverOutput sumcheck::prove_as_subprotocol_products(
     KeccakTranscript &transcript, const std::vector<const uint64_t *> &mles, uint32_t nvars, uint32_t degree,
     const std::vector<std::pair<Limbs, std::vector<uint32_t>>> &products, const FieldConfig &config, int device) {
-    transcript.absorb_random_field(config, map_to_field_u128(config, nvars, 0));  // sumcheck.rs:64-76
-    transcript.absorb_random_field(config, map_to_field_u128(config, degree, 0));
+    const bool fused = env_flag(std::getenv("ZIP_HIP_SUMCHECK_FUSED"), kSumcheckFusedDefault);
+    auto absorb_header = [&] {  // sumcheck.rs:64-76 (the one-handle path leaves it to prove_as_subprotocol_impl)
+        transcript.absorb_random_field(config, map_to_field_u128(config, nvars, 0));
+        transcript.absorb_random_field(config, map_to_field_u128(config, degree, 0));
+    };
+    if (nvars == 0 || products.empty()) absorb_header();
     ProverOutput out;
     if (nvars == 0) return out;
     if (products.empty()) {  // comb_fn == 0 (sumcheck/tests.rs:525-557): every round polynomial is the zero constant
@@ -1333,19 +1350,44 @@ sumcheck::ProverOutput sumcheck::prove_as_subprotocol_products(
         }
         return out;
     }
+    // the shape is checked before a path is chosen: both paths refuse the same polynomials in the same way.  One handle
+    // holds <= 32 MLEs and <= 8 products of 1..4 DIFFERENT multiplicands (a mask cannot say "v0 * v0").
+    bool admissible = mles.size() <= 32 && products.size() <= 8;
+    for (const auto &[coeff, indices] : products) {
+        if (indices.empty() || indices.size() > 4) {
+            absorb_header();
+            throw ZipError(ZipError::InvalidPcsParam, "a product needs 1..4 multiplicands");
+        }
+        uint32_t mask = 0;
+        for (uint32_t j : indices) {
+            if (j >= mles.size()) {
+                absorb_header();
+                throw std::logic_error("index out of bounds: a product refers to a missing MLE");
+            }
+            if (j < 32) {
+                if ((mask >> j) & 1u) admissible = false;
+                mask |= 1u << j;
+            }
+        }
+    }
+    if (fused && admissible) {
+        zip_sumcheck_comb comb{};
+        comb.n_terms = (uint32_t)products.size();
+        for (size_t t = 0; t < products.size(); t++) {
+            for (uint32_t j : products[t].second) comb.term_mask[t] |= 1u << j;
+            for (uint32_t i = 0; i < config.limbs; i++) comb.coeff[t][i] = products[t].first[i];
+        }
+        return prove_as_subprotocol_impl(transcript, mles, nvars, degree, &comb, config, device, ZIP_MEM_HOST, true);
+    }
     const zip_field zf = config.to_abi();
+    absorb_header();  // the loop: one handle per product, each on its own stream; the round messages add up here
     struct Free {
         void operator()(zip_sumcheck *p) const { zip_sumcheck_free(p); }
     };
     std::vector<std::unique_ptr<zip_sumcheck, Free>> provers;
     for (const auto &[coeff, indices] : products) {
-        if (indices.empty() || indices.size() > 4)
-            throw ZipError(ZipError::InvalidPcsParam, "a product needs 1..4 multiplicands");
-        std::vector<const uint64_t *> tables;
-        for (uint32_t j : indices) {
-            if (j >= mles.size()) throw std::logic_error("index out of bounds: a product refers to a missing MLE");
-            tables.push_back(mles[j]);
-        }
+        std::vector<const uint64_t *> tables;  // (1..4 of them, all present: checked above)
+        for (uint32_t j : indices) tables.push_back(mles[j]);
         zip_sumcheck_comb comb{};  // coeff * prod_{j < K-1} vals[j] * vals[K-1]
         comb.n_terms = 1;
         comb.term_mask[0] = (1u << (tables.size() - 1)) - 1u;

@@ -374,9 +374,12 @@ ProverOutput prove_as_subprotocol_ccs(KeccakTranscript &transcript, const std::v
                                       const std::vector<std::vector<uint32_t>> &S, const FieldConfig &config,
                                       int device = 0);
 // The same for a sum of products, comb(vals) = sum_p coeff_p * prod_{j in indices_p} vals[j] (rand_poly_comb_fn,
-// src/sumcheck/utils.rs:67-78; the workload of benches/sumcheck_benches.rs: 7 products of 2-4 fresh MLEs).  Each
-// product runs as its own device prover (at most 4 multiplicands each), all of them enqueued before any is
-// collected; the round message is the field sum of theirs.
+// src/sumcheck/utils.rs:67-78; the workload of benches/sumcheck_benches.rs: 7 products of 2-4 fresh MLEs), at most
+// 4 multiplicands per product.  Up to 32 MLEs and 8 products with no multiplicand twice in a product: ONE device
+// prover for the whole sum (zip_sumcheck_init_products; ZIP_HIP_SUMCHECK_FUSED=0 turns it off, and with
+// ZIP_HIP_SUMCHECK_ONECALL=1 it is one zip_sumcheck_prove call).  Otherwise each product runs as its own device
+// prover, all of them enqueued before any is collected, and the round message is the field sum of theirs.  Same
+// bytes and transcript either way.
 ProverOutput prove_as_subprotocol_products(KeccakTranscript &transcript, const std::vector<const uint64_t *> &mles,
                                            uint32_t nvars, uint32_t degree,
                                            const std::vector<std::pair<Limbs, std::vector<uint32_t>>> &products,
