@@ -45,7 +45,7 @@ extern "C" {
  * zip_batch_commit and the five beside it, are additive in the same way, and so are zip_batch_verify and
  * zip_batch_verify_calls.  So are zip_prime_test_base2, zip_get_prime and zip_prime_launch_counts, and
  * zip_ctx_set_proximity_tests / zip_ctx_proximity_tests: a ctx that never calls the setter behaves as before.  So is
- * zip_sumcheck_init_products.) */
+ * zip_sumcheck_init_products, and so is zip_sumcheck_grid_counts.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -465,6 +465,13 @@ int32_t zip_sumcheck_prove(zip_sumcheck *s, zip_keccak_state *transcript, uint64
  * point) and launches of the tail kernel.  Every path gives the same bytes; tests and tools read the path taken here.
  * Either pointer may be NULL. */
 void zip_sumcheck_launch_counts(uint64_t *round_kernel_rounds, uint64_t *tail_kernel_launches);
+/* Process-wide, monotonic, kept like zip_sumcheck_launch_counts -- of the round-kernel launches so far: those whose
+ * grid-stride loop ran more than one pass (points of the round > workgroups launched * points per workgroup), those
+ * among them whose last pass was not taken by every workgroup, and those that left their partials to
+ * sumcheck_reduce_kernel (grid above 64).  Computed on the host at launch.  ZIP_HIP_SUMCHECK_GRID=n (test hook,
+ * 1 .. 8 * CUs, read per round) caps the workgroups of a round-kernel launch, after every other cap: with it the tests
+ * reach these regimes at small sizes.  Any pointer may be NULL. */
+void zip_sumcheck_grid_counts(uint64_t *multi_pass, uint64_t *uneven_last_pass, uint64_t *reduce_kernel);
 
 /* A sum of products in ONE handle: the polynomial of rand_poly / rand_poly_comb_fn (src/sumcheck/utils.rs:27-78, what
  * benches/sumcheck_benches.rs and src/sumcheck/tests.rs prove),

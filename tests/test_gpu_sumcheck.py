@@ -57,7 +57,9 @@ def test_sumcheck_rounds_equal_the_oracle(mods, modulus, fl, K, degree, nv):
 
 
 def test_sumcheck_device_resident_tables_2pow20(mods):
-    """ZincProver's second sumcheck shape at 2^20 (CCS s = 20): two tables in HBM, read in place."""
+    """ZincProver's second sumcheck shape at 2^20 (CCS s = 20): two tables in HBM, read in place.  Rounds 1 and 2 have
+    2048 and 1024 workgroups' worth of points and sumcheck_round_kernel<4, 2, 2> is resident three workgroups to a CU (768
+    on the 256 CUs of the MI355X): both run their grid-stride loop more than once, with an uneven last pass."""
     torch = pytest.importorskip("torch")
     cabi, pcs = mods
     nv, fl, K, degree = 20, 4, 2, 2
@@ -72,11 +74,13 @@ def test_sumcheck_device_resident_tables_2pow20(mods):
     dev = [torch.from_numpy(mles[k].view(np.int64)).cuda() for k in range(K)]
     before = [d.clone() for d in dev]
     sc = cabi.Sumcheck(dev, nv, degree, cabi.make_field(BENCH_MODULUS, fl))
+    multi_pass0 = cabi.sumcheck_grid_counts()[0]
     r = None
     for i in range(nv):
         ev = sc.round(r)
         assert np.array_equal(ev, msgs_o[i]), i
         r = rand_o[i]
+    assert cabi.sumcheck_grid_counts()[0] > multi_pass0
     with pytest.raises(cabi.ZipError):  # "Prover is not active" (prover.rs:91-93)
         sc.round(r)
     sc.free()

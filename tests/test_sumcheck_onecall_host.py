@@ -62,3 +62,4 @@ def test_cabi_keccak_state_layout():
     k = cabi.KeccakState.make(st=range(25), buf=b"abc")
     assert k.buflen == 3 and k.pending() == b"abc" and [int(w) for w in k.st] == list(range(25))
     assert "zip_sumcheck_prove" in cabi.EXPORTED_SYMBOLS and "zip_sumcheck_launch_counts" in cabi.EXPORTED_SYMBOLS
+    assert "zip_sumcheck_grid_counts" in cabi.EXPORTED_SYMBOLS

@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = (
     "zip_mctx_create", "zip_mctx_destroy", "zip_mctx_last_error", "zip_mctx_shards", "zip_mctx_shard_ctx", "zip_mctx_set_witness",
     "zip_mctx_commit_open", "zip_mctx_shard_openings", "zip_mctx_ends", "zip_mctx_roots", "zip_mctx_roots_path", "zip_verify", "zip_mle_eval", "zip_commitment_mle_eval", "zip_field_map_int256",
     "zip_open_stream", "zip_sumcheck_init", "zip_sumcheck_round", "zip_sumcheck_round_begin", "zip_sumcheck_round_end", "zip_sumcheck_last_error", "zip_sumcheck_free",
-    "zip_sumcheck_prove", "zip_sumcheck_launch_counts", "zip_sumcheck_init_products",
+    "zip_sumcheck_prove", "zip_sumcheck_launch_counts", "zip_sumcheck_grid_counts", "zip_sumcheck_init_products",
     "zip_ccs_create", "zip_ccs_free", "zip_ccs_last_error", "zip_ccs_set_z", "zip_ccs_eq_table",
     "zip_ccs_second_table", "zip_ccs_table", "zip_ccs_download", "zip_ccs_eval_matrices",
     "zip_batch_commit", "zip_batch_size", "zip_batch_free", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open",
@@ -231,6 +231,8 @@ def lib():
     L.zip_sumcheck_prove.argtypes = [vp, C.POINTER(KeccakState), u64p, u64p]
     L.zip_sumcheck_launch_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.zip_sumcheck_launch_counts.restype = None
+    L.zip_sumcheck_grid_counts.argtypes = [C.POINTER(C.c_uint64)] * 3
+    L.zip_sumcheck_grid_counts.restype = None
     L.zip_prime_test_base2.argtypes = [C.c_int32, u64p, C.c_uint32, C.c_uint32, u8p]
     L.zip_prime_test_base2.restype = C.c_int32
     L.zip_get_prime.argtypes = [C.c_int32, C.POINTER(KeccakState), C.c_uint32, u64p, C.POINTER(C.c_uint32)]
@@ -909,6 +911,15 @@ def sumcheck_launch_counts():
     a, b = C.c_uint64(0), C.c_uint64(0)
     lib().zip_sumcheck_launch_counts(C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+def sumcheck_grid_counts():
+    """(multi_pass, uneven_last_pass, reduce_kernel): of the round-kernel launches of this process so far, those whose
+    grid-stride loop ran more than one pass, those among them whose last pass not every workgroup took, and those that
+    left their partials to sumcheck_reduce_kernel (more than 64 workgroups)"""
+    a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    lib().zip_sumcheck_grid_counts(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
 
 
 def prime_test_base2(candidates, limbs: int, device: int = 0) -> np.ndarray:

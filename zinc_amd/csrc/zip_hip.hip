@@ -1934,6 +1934,24 @@ int32_t run_batch_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &h
 
 // ---- sumcheck prover -----------------------------------------
 namespace {
+// Process-wide counts of the regime the round-kernel launches ran in (zip_sumcheck_grid_counts): computed here, on
+// the host, from the points of the round, the final grid and the kernel's points per workgroup
+std::atomic<uint64_t> g_sumcheck_multi_pass{0}, g_sumcheck_uneven_last_pass{0}, g_sumcheck_reduce_launches{0};
+
+// The grid of a round-kernel launch after its last cap, and the regime it runs in.  ZIP_HIP_SUMCHECK_GRID=n (test hook,
+// 1 .. 8 per CU; per call: the tests flip it) caps the workgroups after the occupancy cap, so that the tests reach several
+// passes of the grid-stride loop, an uneven last pass and both reductions at small sizes; unset: `blocks` as it came.
+uint32_t sumcheck_final_grid(const zip_sumcheck *s, uint32_t blocks, uint64_t half, uint32_t points_per_wg) {
+    blocks = std::min<uint32_t>(blocks, (uint32_t)env_long("ZIP_HIP_SUMCHECK_GRID", (long)s->max_blocks, 1, (long)s->max_blocks));
+    const uint64_t worth = (half + points_per_wg - 1) / points_per_wg;  // workgroups' worth of points
+    if (worth > blocks) {
+        g_sumcheck_multi_pass++;
+        if (worth % blocks) g_sumcheck_uneven_last_pass++;
+    }
+    if (blocks > 64) g_sumcheck_reduce_launches++;
+    return blocks;
+}
+
 // degree 3: four lanes per hypercube point (sumcheck_round_quad_kernel, <= 128 VGPRs); ZIP_HIP_SUMCHECK_QUAD=0: the
 // one-thread-per-point kernel for every degree
 template <int FL, int K, int DEG>
@@ -1953,6 +1971,7 @@ int32_t launch_sumcheck_quad(zip_sumcheck *s, SumcheckRoundArgs<FL> a, const Fie
             per_cu = 0;
         if (per_cu > 0) blocks = std::min<uint32_t>(blocks, ctx->num_cus * (uint32_t)per_cu);
     }
+    blocks = sumcheck_final_grid(s, blocks, a.half, 64);
     a.done = blocks <= 64 ? s->done_d : nullptr;
     {
         LaunchTimer t(ctx, "sumcheck_round_kernel");
@@ -1969,7 +1988,7 @@ int32_t launch_sumcheck_quad(zip_sumcheck *s, SumcheckRoundArgs<FL> a, const Fie
 }
 
 template <int FL, int K, int DEG>
-int32_t launch_sumcheck_round(zip_sumcheck *s, const SumcheckRoundArgs<FL> &a, uint32_t blocks, const FieldDev<FL> &fd) {
+int32_t launch_sumcheck_round(zip_sumcheck *s, SumcheckRoundArgs<FL> a, uint32_t blocks, const FieldDev<FL> &fd) {
     zip_ctx *ctx = s->ctx;
     if constexpr (DEG == 3 || DEG == 2) {
         // Degree 3, the FOLDING rounds (all but the first): there the quad kernel is as fast in the big rounds and up to
@@ -1997,6 +2016,8 @@ int32_t launch_sumcheck_round(zip_sumcheck *s, const SumcheckRoundArgs<FL> &a, u
             per_cu = 0;
         if (per_cu > 0) blocks = std::min<uint32_t>(blocks, ctx->num_cus * (uint32_t)per_cu);
     }
+    blocks = sumcheck_final_grid(s, blocks, a.half, 256);
+    a.done = blocks <= 64 ? s->done_d : nullptr;  // small rounds: one launch, the last workgroup folds the partials
     {
         LaunchTimer t(ctx, "sumcheck_round_kernel");
         hipLaunchKernelGGL((sumcheck_round_kernel<FL, K, DEG>), dim3(blocks), dim3(256), lds, ctx->stream, a, fd);
@@ -2031,6 +2052,7 @@ int32_t launch_sumcheck_wide(zip_sumcheck *s, SumcheckRoundArgs<FL> a, const Fie
             per_cu = 0;
         if (per_cu > 0) blocks = std::min<uint32_t>(blocks, ctx->num_cus * (uint32_t)per_cu);
     }
+    blocks = sumcheck_final_grid(s, blocks, a.half, 256 / kSumcheckWideLanes);
     a.done = blocks <= 64 ? s->done_d : nullptr;
     {
         LaunchTimer t(ctx, "sumcheck_round_wide_kernel");
@@ -2088,8 +2110,8 @@ int32_t sumcheck_round_fl(zip_sumcheck *s, const uint64_t *r_prev, const HostFie
     if (a.fold)
         for (int i = 0; i < FL; i++) a.r[i] = r_prev[i];
     uint64_t want = (a.half + 255) / 256;
+    // (a.done -- the last workgroup folds the partials, or sumcheck_reduce_kernel does -- is the launcher's: it knows the final grid)
     uint32_t blocks = (uint32_t)std::min<uint64_t>(want ? want : 1, s->max_blocks);
-    a.done = blocks <= 64 ? s->done_d : nullptr;  // small rounds: one launch, the last workgroup folds the partials
     const FieldDev<FL> fd = to_dev<FL>(hf);
     switch (s->n_mles) {
         case 1: return sumcheck_round_k<FL, 1>(s, a, blocks, fd);
@@ -2151,6 +2173,7 @@ int32_t sumcheck_round_products_fl(zip_sumcheck *s, const uint64_t *r_prev, cons
             per_cu = 0;
         if (per_cu > 0) blocks = std::min<uint32_t>(blocks, ctx->num_cus * (uint32_t)per_cu);
     }
+    blocks = sumcheck_final_grid(s, blocks, a.half, 256 / kSumcheckWideLanes);
     a.done = blocks <= 64 ? s->done_d : nullptr;  // small rounds: one launch, the last workgroup folds the partials
     {
         LaunchTimer t(ctx, "sumcheck_round_products_kernel");
@@ -4999,6 +5022,12 @@ int32_t zip_sumcheck_prove(zip_sumcheck *s, zip_keccak_state *transcript, uint64
 void zip_sumcheck_launch_counts(uint64_t *rounds, uint64_t *tails) {
     if (rounds) *rounds = g_sumcheck_round_launches.load();
     if (tails) *tails = g_sumcheck_tail_launches.load();
+}
+
+void zip_sumcheck_grid_counts(uint64_t *multi_pass, uint64_t *uneven_last_pass, uint64_t *reduce_kernel) {
+    if (multi_pass) *multi_pass = g_sumcheck_multi_pass.load();
+    if (uneven_last_pass) *uneven_last_pass = g_sumcheck_uneven_last_pass.load();
+    if (reduce_kernel) *reduce_kernel = g_sumcheck_reduce_launches.load();
 }
 
 int32_t zip_prime_test_base2(int32_t device, const uint64_t *candidates, uint32_t n, uint32_t limbs, uint8_t *verdicts_out) {
