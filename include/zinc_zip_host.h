@@ -231,6 +231,21 @@ int32_t zinc_sumcheck_prove_ccs(zinc_transcript *transcript, const uint64_t *con
                                 const uint32_t *s_masks, const uint64_t *modulus, uint32_t limbs, int32_t device,
                                 uint64_t *msgs_out, uint64_t *randomness_out);
 
+/* n_instances sumchecks of one shape, each with its own transcript, tables and field: on instance i what
+ * zinc_sumcheck_prove_product (n_terms == NULL or n_terms[i] == 0) or zinc_sumcheck_prove_ccs (n_terms[i] = 1..8) does, with
+ * the same transcript, messages and challenges afterwards.  With nvars 1..16, the same number of limbs in every instance
+ * and from 2 / 3 / 6 instances on for nvars up to 12 / 14 / 16, it is ONE device call (zip_sumcheck_prove_batch: one
+ * workgroup per instance); with ZIP_HIP_BATCH=0, fewer instances or any other shape it is the loop over those two
+ * functions.
+ *   mles     n_instances * n_mles host tables, instance-major
+ *   c        instance i's coefficients at c + (i * 8 + t) * 4, limbs[i] limbs each; s_masks[i * 8 + t] as in zinc_sumcheck_prove_ccs
+ *   moduli   instance i's modulus at moduli + i * 4; limbs[i] its limbs
+ *   msgs_out / randomness_out   instance-major, instance i with nvars * (degree + 1) * limbs[i] / nvars * limbs[i] limbs */
+int32_t zinc_sumcheck_prove_batch(zinc_transcript *const *transcripts, uint32_t n_instances, const uint64_t *const *mles,
+                                  uint32_t n_mles, uint32_t nvars, uint32_t degree, const uint32_t *n_terms, const uint64_t *c,
+                                  const uint32_t *s_masks, const uint64_t *moduli, const uint32_t *limbs, int32_t device,
+                                  uint64_t *msgs_out, uint64_t *randomness_out);
+
 /* MLSumcheck::prove_as_subprotocol with rand_poly_comb_fn (src/sumcheck/utils.rs:67-78), the workload of
  * benches/sumcheck_benches.rs: sum_p coeffs[p] * prod_{j in masks[p]} vals[j] (bit j of masks[p]: MLE j is a factor;
  * 1..4 factors per product, up to 32 MLEs).  coeffs: n_products field elements (Montgomery). */

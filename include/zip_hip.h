@@ -45,7 +45,8 @@ extern "C" {
  * zip_batch_commit and the five beside it, are additive in the same way, and so are zip_batch_verify and
  * zip_batch_verify_calls.  So are zip_prime_test_base2, zip_get_prime and zip_prime_launch_counts, and
  * zip_ctx_set_proximity_tests / zip_ctx_proximity_tests: a ctx that never calls the setter behaves as before.  So is
- * zip_sumcheck_init_products, and so is zip_sumcheck_grid_counts.) */
+ * zip_sumcheck_init_products, and so is zip_sumcheck_grid_counts.  So are zip_sumcheck_prove_batch and
+ * zip_sumcheck_batch_counts: many small sumchecks in one launch, beside the one-at-a-time form that is unchanged.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -496,6 +497,43 @@ void zip_sumcheck_grid_counts(uint64_t *multi_pass, uint64_t *uneven_last_pass, 
 int32_t zip_sumcheck_init_products(int32_t device, const uint64_t *const *mles, zip_mem_kind kind, uint32_t n_mles,
                                    uint32_t num_vars, uint32_t degree, const zip_sumcheck_comb *products,
                                    const zip_field *field, zip_sumcheck **out);
+
+/* MANY small sumchecks of one shape in ONE launch: for instance i exactly what
+ *   zip_sumcheck_init(device, inst[i].mles, tables_kind, n_mles, num_vars, degree, inst[i].comb, inst[i].field, &h)
+ * followed by zip_sumcheck_prove on h and inst[i].transcript does, bit for bit (MLSumcheck::prove_as_subprotocol with the
+ * absorption of nvars and degree) -- but workgroup i of one kernel plays every round of instance i with the sponge on
+ * the device: one launch, one upload of the arguments, one device-to-host copy of the results and one synchronisation,
+ * whatever n_instances is.  For callers of the batch family (zip_batch_commit ...) that hold many small proofs.
+ *   inst            HOST, n_instances (1..65535) entries; every instance has its own tables, transcript, combination
+ *                   (NULL: the product; the forms may differ between instances) and field (the same `limbs` for all)
+ *   n_mles 1..8, degree 1..4, num_vars 1..16 (above: ZIP_ERR_UNSUPPORTED -- one sumcheck of that size fills the device
+ *                   through the round kernels; loop over zip_sumcheck_prove)
+ *   msgs_out        HOST, instance-major: n_instances * num_vars * (degree + 1) * limbs limbs
+ *   randomness_out  HOST, n_instances * num_vars * limbs limbs
+ * HOST tables are copied, DEVICE tables are read in place and never written.  The last n rounds are played from LDS, n =
+ * ZIP_HIP_SUMCHECK_TAIL cut to what fits one workgroup (the bound of zip_sumcheck_prove's tail kernel) and to num_vars;
+ * the rounds before stream the tables from HBM (round 1: the caller's; later: a per-instance scratch block).  Here
+ * ZIP_HIP_SUMCHECK_TAIL=0 means that every round is streamed.
+ * Errors, before anything reaches the device and in this order: ZIP_ERR_NULL (inst, msgs_out, randomness_out, any
+ * instance's mles / field / transcript / a table pointer); ZIP_ERR_INVALID_PARAM (n_instances; n_mles, degree, num_vars;
+ * limbs not in {2, 3, 4} or differing between instances; a comb with n_terms outside 1..8 or a mask bit at or above
+ * n_mles; buflen >= 136; a modulus that is even or 1); ZIP_ERR_UNSUPPORTED (num_vars above 16).  ZIP_ERR_ALLOC when scratch
+ * or staging cannot be had.  On ANY non-zero return no transcript has been modified and the outputs are unspecified.
+ * Not part of this: the sum-of-products form of zip_sumcheck_init_products.  The caller's current device is restored.
+ * Additive: the ABI version stays 3. */
+typedef struct {
+    const uint64_t *const *mles;   /* n_mles tables of 2^num_vars elements, Montgomery limbs */
+    const zip_sumcheck_comb *comb; /* NULL: the product of all tables; else as in zip_sumcheck_init */
+    const zip_field *field;        /* each instance its own (each proof draws its own field); same `limbs` for all */
+    zip_keccak_state *transcript;  /* in/out, as in zip_sumcheck_prove */
+} zip_sumcheck_instance;
+int32_t zip_sumcheck_prove_batch(int32_t device, const zip_sumcheck_instance *inst, uint32_t n_instances,
+                                 zip_mem_kind tables_kind, uint32_t n_mles, uint32_t num_vars, uint32_t degree,
+                                 uint64_t *msgs_out, uint64_t *randomness_out);
+/* Process-wide, monotonic, kept like zip_sumcheck_launch_counts: launches of the batch kernel, the instances they played,
+ * and the rounds played from HBM (max(0, num_vars - n) per instance, computed on the host at launch).  A batch call
+ * moves neither zip_sumcheck_launch_counts nor zip_sumcheck_grid_counts.  Any pointer may be NULL. */
+void zip_sumcheck_batch_counts(uint64_t *launches, uint64_t *instances, uint64_t *streamed_rounds);
 
 /* ---- the random field: prime_gen::get_prime (src/prime_gen.rs:15-28) ---------------------------------------------
  * draw_random_field (src/zinc/utils.rs:161-171) absorbs the public inputs and calls get_prime: hash a candidate of

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "zip_mctx_commit_open", "zip_mctx_shard_openings", "zip_mctx_ends", "zip_mctx_roots", "zip_mctx_roots_path", "zip_verify", "zip_mle_eval", "zip_commitment_mle_eval", "zip_field_map_int256",
     "zip_open_stream", "zip_sumcheck_init", "zip_sumcheck_round", "zip_sumcheck_round_begin", "zip_sumcheck_round_end", "zip_sumcheck_last_error", "zip_sumcheck_free",
     "zip_sumcheck_prove", "zip_sumcheck_launch_counts", "zip_sumcheck_grid_counts", "zip_sumcheck_init_products",
+    "zip_sumcheck_prove_batch", "zip_sumcheck_batch_counts",
     "zip_ccs_create", "zip_ccs_free", "zip_ccs_last_error", "zip_ccs_set_z", "zip_ccs_eq_table",
     "zip_ccs_second_table", "zip_ccs_table", "zip_ccs_download", "zip_ccs_eval_matrices",
     "zip_batch_commit", "zip_batch_size", "zip_batch_free", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open",
@@ -146,6 +147,12 @@ def make_comb(term_masks, coeffs_limbs):
     return c
 
 
+class SumcheckInstance(C.Structure):
+    """zip_sumcheck_instance: one sumcheck of a zip_sumcheck_prove_batch call"""
+    _fields_ = [("mles", C.c_void_p), ("comb", C.POINTER(SumcheckComb)), ("field", C.POINTER(ZipField)),
+                ("transcript", C.POINTER(KeccakState))]
+
+
 class SparseMatrix(C.Structure):
     """zip_sparse_matrix: SparseMatrix<Int<1>> as CSR"""
     _fields_ = [("n_rows", C.c_uint32), ("n_cols", C.c_uint32), ("row_ptr", C.c_void_p), ("col_idx", C.c_void_p),
@@ -233,6 +240,10 @@ def lib():
     L.zip_sumcheck_launch_counts.restype = None
     L.zip_sumcheck_grid_counts.argtypes = [C.POINTER(C.c_uint64)] * 3
     L.zip_sumcheck_grid_counts.restype = None
+    L.zip_sumcheck_prove_batch.argtypes = [C.c_int32, C.POINTER(SumcheckInstance), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, u64p, u64p]
+    L.zip_sumcheck_batch_counts.argtypes = [C.POINTER(C.c_uint64)] * 3
+    L.zip_sumcheck_batch_counts.restype = None
     L.zip_prime_test_base2.argtypes = [C.c_int32, u64p, C.c_uint32, C.c_uint32, u8p]
     L.zip_prime_test_base2.restype = C.c_int32
     L.zip_get_prime.argtypes = [C.c_int32, C.POINTER(KeccakState), C.c_uint32, u64p, C.POINTER(C.c_uint32)]
@@ -920,6 +931,48 @@ def sumcheck_grid_counts():
     a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     lib().zip_sumcheck_grid_counts(C.byref(a), C.byref(b), C.byref(c))
     return a.value, b.value, c.value
+
+
+def sumcheck_batch_counts():
+    """(launches of the batch sumcheck kernel, instances they played, rounds they played from HBM) in this process so far"""
+    a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    lib().zip_sumcheck_batch_counts(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def sumcheck_prove_batch(instances, n_mles: int, num_vars: int, degree: int, device: int = 0):
+    """zip_sumcheck_prove_batch: every instance's whole MLSumcheck::prove_as_subprotocol, one workgroup each, in ONE
+    launch.  instances: a sequence of (mles, field, state) or (mles, field, state, comb) -- mles one numpy array
+    [n_mles, 2^num_vars, limbs] (copied; all instances alike) or a list of n_mles CUDA tensors / raw device addresses
+    (read in place, never written); field a ZipField (the same limbs for all); state the instance's KeccakState before
+    the sumcheck, updated in place; comb a SumcheckComb or None (the product).
+    -> (msgs [B, num_vars, degree + 1, limbs], randomness [B, num_vars, limbs])."""
+    insts = [tuple(i) + (None,) * (4 - len(i)) for i in instances]
+    B = len(insts)
+    host = B > 0 and isinstance(insts[0][0], np.ndarray)
+    arr = (SumcheckInstance * max(B, 1))()
+    keep = []
+    for i, (mles, field, state, comb) in enumerate(insts):
+        if host:
+            t = np.ascontiguousarray(mles, dtype=np.uint64)
+            ptrs = [t[k].ctypes.data for k in range(t.shape[0])]
+        else:
+            t = list(mles)
+            ptrs = [x if isinstance(x, int) else x.data_ptr() for x in t]
+        pa = (C.c_void_p * len(ptrs))(*ptrs)
+        keep.append((t, pa))
+        arr[i].mles = C.cast(pa, C.c_void_p)
+        arr[i].comb = C.pointer(comb) if comb is not None else None
+        arr[i].field = C.pointer(field)
+        arr[i].transcript = C.pointer(state)
+    fl = insts[0][1].limbs if B else 0
+    msgs = np.zeros((B, num_vars, degree + 1, fl), dtype=np.uint64)
+    rand = np.zeros((B, num_vars, fl), dtype=np.uint64)
+    rc = lib().zip_sumcheck_prove_batch(device, arr, B, MEM_HOST if host else MEM_DEVICE, n_mles, num_vars, degree,
+                                        msgs.ctypes.data, rand.ctypes.data)
+    if rc != ZIP_OK:
+        raise ZipError(rc, "zip_sumcheck_prove_batch")
+    return msgs, rand
 
 
 def prime_test_base2(candidates, limbs: int, device: int = 0) -> np.ndarray:

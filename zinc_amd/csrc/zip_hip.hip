@@ -32,6 +32,7 @@
 #include "kernels_batch_verify.cuh"
 #include "kernels_sumcheck.cuh"
 #include "kernels_sumcheck_tail.cuh"
+#include "kernels_sumcheck_batch.cuh"
 #include "kernels_sumcheck_wide.cuh"
 #include "kernels_sumcheck_products.cuh"
 #include "kernels_spartan.cuh"
@@ -2282,6 +2283,113 @@ int32_t sumcheck_prove_fl(zip_sumcheck *s, zip_keccak_state *transcript, uint64_
     memcpy(transcript->st, sp.st, sizeof sp.st);
     memcpy(transcript->buf, sp.blk, sizeof transcript->buf);  // zero beyond buflen
     transcript->buflen = sp.buflen;
+    return ZIP_OK;
+}
+
+// ---- zip_sumcheck_prove_batch: n_instances sumchecks of one shape, one workgroup each, in ONE launch ---------------------
+// Process-wide (zip_sumcheck_batch_counts): launches of sumcheck_batch_kernel, the instances they played and the rounds
+// they played from HBM (max(0, num_vars - n) per instance, computed here at launch)
+std::atomic<uint64_t> g_sumcheck_batch_launches{0}, g_sumcheck_batch_instances{0}, g_sumcheck_batch_streamed{0};
+// HOST tables up to this size are gathered into the pinned bounce pair instead of being copied one by one (a copy
+// call costs ~10 us: as much as 256 KiB take through a memcpy)
+constexpr size_t kBatchPackBytes = (size_t)256 << 10;
+
+// The arguments have been checked and fields[i] made; `ctx` is the call's own plumbing context (its blocks come from
+// the recycle bin and go back there).  Transcripts are written only after everything has succeeded.
+template <int FL>
+int32_t sumcheck_prove_batch_fl(zip_ctx *ctx, const zip_sumcheck_instance *inst, uint32_t B, zip_mem_kind kind, uint32_t n_mles,
+                                uint32_t nv, uint32_t degree, const std::vector<HostField> &fields, uint64_t *msgs_out,
+                                uint64_t *randomness_out) {
+    const uint32_t ne = degree + 1;
+    // The last n rounds are played from LDS.  ZIP_HIP_SUMCHECK_TAIL=n as for zip_sumcheck_prove (per call: the tests flip
+    // it); here 0 means that every round is streamed.  The kernel's static LDS is the tail kernel's: the same bound.
+    const uint32_t bound = tail_lds_bound(n_mles, FL);
+    const uint32_t knob = (uint32_t)env_long("ZIP_HIP_SUMCHECK_TAIL", bound, 0, kTailMaxLog);
+    const uint32_t n_lds = std::min(std::min(knob, bound), nv), n_streamed = nv - n_lds;
+    const size_t elem = (size_t)FL * 8, tab_bytes = elem << nv, scr_bytes = n_streamed >= 2 ? (size_t)n_mles * (tab_bytes / 2) : 0;
+    const size_t out_words = sumcheck_batch_out_words(nv, degree, FL);
+    SumcheckBatchInst<FL> *args_d = nullptr;
+    uint64_t *out_d = nullptr, *tables_d = nullptr, *scratch_d = nullptr;
+    int32_t rc;
+    if ((rc = pool_alloc(ctx, (size_t)B * sizeof(SumcheckBatchInst<FL>), (void **)&args_d))) return rc;
+    if ((rc = pool_alloc(ctx, (size_t)B * out_words * 8, (void **)&out_d))) return rc;
+    if (scr_bytes && (rc = pool_alloc(ctx, (size_t)B * scr_bytes, (void **)&scratch_d))) return rc;
+    if (kind == ZIP_MEM_HOST) {
+        const size_t n_tabs = (size_t)B * n_mles;
+        if ((rc = pool_alloc(ctx, n_tabs * tab_bytes, (void **)&tables_d))) return rc;
+        unsigned char *dst = reinterpret_cast<unsigned char *>(tables_d);
+        if (tab_bytes <= kBatchPackBytes && n_tabs > 1) {
+            // small tables: a copy call apiece costs more than the bytes do -- gathered into the pinned bounce pair, one
+            // copy per buffer-full, the gather of the next beside the copy of this one
+            if ((rc = ensure_bounce(ctx, kBounceBytes))) return rc;
+            const size_t per = ctx->bounce_cap / tab_bytes;  // tables per buffer-full
+            hipEvent_t ev[2] = {take_dep_event(ctx), take_dep_event(ctx)};
+            size_t chunk = 0;
+            for (size_t at = 0; at < n_tabs && rc == ZIP_OK; at += per, chunk++) {
+                const size_t n = std::min(per, n_tabs - at);
+                unsigned char *b = ctx->bounce[chunk & 1];
+                if (chunk >= 2 && event_wait(ev[chunk & 1]) != hipSuccess) { rc = fail(ctx, ZIP_ERR_HIP, "host-to-device copy failed"); break; }
+                for (size_t t = 0; t < n; t++) memcpy(b + t * tab_bytes, inst[(at + t) / n_mles].mles[(at + t) % n_mles], tab_bytes);
+                hipError_t e = hipMemcpyAsync(dst + at * tab_bytes, b, n * tab_bytes, hipMemcpyHostToDevice, ctx->stream);
+                if (e == hipSuccess) e = hipEventRecord(ev[chunk & 1], ctx->stream);
+                if (e != hipSuccess) rc = fail(ctx, ZIP_ERR_HIP, "host-to-device copy failed: %s", hipGetErrorString(e));
+            }
+            ctx->dep_event_pool.push_back(ev[0]);
+            ctx->dep_event_pool.push_back(ev[1]);
+            if (rc) return rc;  // (the context's destruction waits for the stream before the pair is handed on)
+        } else {
+            for (size_t t = 0; t < n_tabs; t++)
+                if ((rc = copy_h2d_bounced(ctx, dst + t * tab_bytes, inst[t / n_mles].mles[t % n_mles], tab_bytes, ctx->stream))) return rc;
+        }
+    }
+    std::vector<SumcheckBatchInst<FL>> args(B);
+    for (uint32_t i = 0; i < B; i++) {
+        SumcheckBatchInst<FL> &a = args[i];
+        memset(&a, 0, sizeof a);
+        const HostField &hf = fields[i];
+        for (uint32_t k = 0; k < n_mles; k++)
+            a.src[k] = kind == ZIP_MEM_HOST ? tables_d + (((size_t)i * n_mles + k) << nv) * FL : inst[i].mles[k];
+        a.scratch = scr_bytes ? scratch_d + (size_t)i * (scr_bytes / 8) : nullptr;
+        a.f = to_dev<FL>(hf);
+        a.tf = tr_make_field<FL>(hf.modulus, hf.r2, hf.inv);
+        if (const zip_sumcheck_comb *c = inst[i].comb) {
+            a.n_terms = c->n_terms;
+            for (uint32_t t = 0; t < c->n_terms; t++) {
+                a.term_mask[t] = c->term_mask[t];
+                for (int l = 0; l < FL; l++) a.coeff[t][l] = c->coeff[t][l];
+            }
+        }
+        const zip_keccak_state *tr = inst[i].transcript;
+        memcpy(a.st, tr->st, sizeof a.st);
+        memcpy(a.blk, tr->buf, tr->buflen);  // little-endian host; zero beyond buflen
+        a.buflen = tr->buflen;
+        a.out = out_d + (size_t)i * out_words;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(args_d, args.data(), (size_t)B * sizeof(SumcheckBatchInst<FL>), hipMemcpyHostToDevice, ctx->stream));
+    const size_t lds = n_lds ? ((size_t)n_mles << n_lds) * elem : 0;
+    auto kern = sumcheck_batch_kernel<FL>;
+    if ((rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds))) return rc;
+    {
+        LaunchTimer t(ctx, "sumcheck_batch_kernel");
+        hipLaunchKernelGGL(kern, dim3(B), dim3(kTailThreads), lds, ctx->stream, (const SumcheckBatchInst<FL> *)args_d, n_mles, degree, nv, n_lds);
+        HIP_TRY(ctx, hipGetLastError());
+        g_sumcheck_batch_launches++;
+        g_sumcheck_batch_instances += B;
+        g_sumcheck_batch_streamed += (uint64_t)B * n_streamed;
+    }
+    std::vector<uint64_t> host((size_t)B * out_words);
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), out_d, host.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, stream_wait(ctx->stream));
+    const size_t n_msg = (size_t)nv * ne * FL, n_ch = (size_t)nv * FL;
+    for (uint32_t i = 0; i < B; i++) {
+        const uint64_t *o = host.data() + (size_t)i * out_words, *so = o + n_msg + n_ch;
+        memcpy(msgs_out + (size_t)i * n_msg, o, n_msg * 8);
+        memcpy(randomness_out + (size_t)i * n_ch, o + n_msg, n_ch * 8);
+        zip_keccak_state *tr = inst[i].transcript;
+        memcpy(tr->st, so, sizeof tr->st);
+        memcpy(tr->buf, so + 25, sizeof tr->buf);  // zero beyond buflen
+        tr->buflen = (uint32_t)so[25 + kKeccakRateWords];
+    }
     return ZIP_OK;
 }
 
@@ -5028,6 +5136,72 @@ void zip_sumcheck_grid_counts(uint64_t *multi_pass, uint64_t *uneven_last_pass, 
     if (multi_pass) *multi_pass = g_sumcheck_multi_pass.load();
     if (uneven_last_pass) *uneven_last_pass = g_sumcheck_uneven_last_pass.load();
     if (reduce_kernel) *reduce_kernel = g_sumcheck_reduce_launches.load();
+}
+
+int32_t zip_sumcheck_prove_batch(int32_t device, const zip_sumcheck_instance *inst, uint32_t n_instances, zip_mem_kind tables_kind,
+                                 uint32_t n_mles, uint32_t num_vars, uint32_t degree, uint64_t *msgs_out, uint64_t *randomness_out) {
+    // usage errors, before anything reaches the device: every NULL first, then the parameters, then the size limit
+    if (!inst || !msgs_out || !randomness_out) return ZIP_ERR_NULL;
+    const uint32_t scan = std::min<uint32_t>(n_instances, 65535), scan_k = std::min<uint32_t>(n_mles, kSumcheckMaxMles);
+    for (uint32_t i = 0; i < scan; i++) {
+        if (!inst[i].mles || !inst[i].field || !inst[i].transcript) return ZIP_ERR_NULL;
+        for (uint32_t k = 0; k < scan_k; k++)
+            if (!inst[i].mles[k]) return ZIP_ERR_NULL;
+    }
+    if (n_instances < 1 || n_instances > 65535) return ZIP_ERR_INVALID_PARAM;
+    if (n_mles < 1 || n_mles > (uint32_t)kSumcheckMaxMles || degree < 1 || degree > (uint32_t)kSumcheckMaxDegree || num_vars < 1 ||
+        num_vars > 30)
+        return ZIP_ERR_INVALID_PARAM;  // (zip_sumcheck_init's ranges; what lies above this entry point's own is refused below)
+    const uint32_t fl = inst[0].field->limbs;
+    if (fl < 2 || fl > 4) return ZIP_ERR_INVALID_PARAM;
+    for (uint32_t i = 0; i < n_instances; i++)
+        if (inst[i].field->limbs != fl) return ZIP_ERR_INVALID_PARAM;
+    for (uint32_t i = 0; i < n_instances; i++) {
+        const zip_sumcheck_comb *c = inst[i].comb;
+        if (!c) continue;
+        if (c->n_terms < 1 || c->n_terms > 8) return ZIP_ERR_INVALID_PARAM;
+        for (uint32_t t = 0; t < c->n_terms; t++)
+            if (c->term_mask[t] >> n_mles) return ZIP_ERR_INVALID_PARAM;
+    }
+    for (uint32_t i = 0; i < n_instances; i++)
+        if (inst[i].transcript->buflen >= kKeccakRate) return ZIP_ERR_INVALID_PARAM;
+    if (num_vars > kBatchSumcheckMaxVars) return ZIP_ERR_UNSUPPORTED;
+    // FieldConfig::new per instance (an even modulus or 1: ZIP_ERR_INVALID_PARAM, as from zip_sumcheck_init); neighbours
+    // with the same modulus share the work
+    std::vector<HostField> fields(n_instances);
+    for (uint32_t i = 0; i < n_instances; i++) {
+        if (i && !memcmp(inst[i].field->modulus, inst[i - 1].field->modulus, 8 * (size_t)fl)) {
+            fields[i] = fields[i - 1];
+            continue;
+        }
+        if (int32_t rc = make_field_uncached(nullptr, inst[i].field, &fields[i])) return rc;
+    }
+    CurrentDeviceGuard restore;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ZIP_ERR_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
+    zip_ctx *ctx = new (std::nothrow) zip_ctx();  // the call's plumbing, as a zip_sumcheck handle has one
+    if (!ctx) return ZIP_ERR_ALLOC;
+    ctx->device = device;
+    ctx->recycle = true;
+    int32_t rc = ZIP_OK;
+    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
+        ctx->stream = nullptr;
+        rc = ZIP_ERR_HIP;
+    }
+    if (!rc)
+        rc = with_fl(fl, [&](auto FL) {
+            return sumcheck_prove_batch_fl<decltype(FL)::value>(ctx, inst, n_instances, tables_kind, n_mles, num_vars, degree, fields,
+                                                                msgs_out, randomness_out);
+        });
+    zip_ctx_destroy(ctx);  // waits for the stream; every block goes back to the device's recycle bin
+    return rc;
+}
+
+void zip_sumcheck_batch_counts(uint64_t *launches, uint64_t *instances, uint64_t *streamed_rounds) {
+    if (launches) *launches = g_sumcheck_batch_launches.load();
+    if (instances) *instances = g_sumcheck_batch_instances.load();
+    if (streamed_rounds) *streamed_rounds = g_sumcheck_batch_streamed.load();
 }
 
 int32_t zip_prime_test_base2(int32_t device, const uint64_t *candidates, uint32_t n, uint32_t limbs, uint8_t *verdicts_out) {

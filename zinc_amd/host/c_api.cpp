@@ -495,6 +495,41 @@ int32_t zinc_sumcheck_prove_ccs(zinc_transcript *transcript, const uint64_t *con
     });
 }
 
+int32_t zinc_sumcheck_prove_batch(zinc_transcript *const *transcripts, uint32_t n_instances, const uint64_t *const *mles,
+                                  uint32_t n_mles, uint32_t nvars, uint32_t degree, const uint32_t *n_terms, const uint64_t *c,
+                                  const uint32_t *s_masks, const uint64_t *moduli, const uint32_t *limbs, int32_t device,
+                                  uint64_t *msgs_out, uint64_t *randomness_out) {
+    if (!transcripts || !mles || !moduli || !limbs || !msgs_out || !randomness_out) return ZINC_ERR_NULL;
+    for (uint32_t i = 0; i < n_instances; i++)
+        if (!transcripts[i] || (n_terms && n_terms[i] && (!c || !s_masks))) return ZINC_ERR_NULL;
+    return guarded([&] {
+        std::vector<zinc::sumcheck::BatchInstance> inst(n_instances);
+        for (uint32_t i = 0; i < n_instances; i++) {
+            zinc::sumcheck::BatchInstance &b = inst[i];
+            b.transcript = &transcripts[i]->t;
+            b.mles.assign(mles + (size_t)i * n_mles, mles + (size_t)(i + 1) * n_mles);
+            b.config = FieldConfig::make(moduli + (size_t)i * 4, limbs[i]);
+            const uint32_t nt = n_terms ? n_terms[i] : 0;
+            if (nt > 8) throw ZipError(ZipError::InvalidPcsParam, "more than 8 CCS terms in an instance of the batch");
+            b.ccs = nt != 0;
+            for (uint32_t t = 0; t < nt; t++) {
+                b.c.push_back(load(c + ((size_t)i * 8 + t) * 4, limbs[i]));
+                b.S.emplace_back();
+                for (uint32_t j = 0; j < 32; j++)
+                    if ((s_masks[(size_t)i * 8 + t] >> j) & 1u) b.S.back().push_back(j);
+            }
+        }
+        const auto res = zinc::sumcheck::prove_as_subprotocol_batch(inst, nvars, degree, device);
+        size_t m_at = 0, r_at = 0;  // instance-major, each instance with its own number of limbs
+        for (uint32_t i = 0; i < n_instances; i++)
+            for (size_t r = 0; r < res[i].proof.msgs.size(); r++) {
+                for (uint32_t e = 0; e <= degree; e++)
+                    for (uint32_t l = 0; l < limbs[i]; l++) msgs_out[m_at++] = res[i].proof.msgs[r][e][l];
+                for (uint32_t l = 0; l < limbs[i]; l++) randomness_out[r_at++] = res[i].randomness[r][l];
+            }
+    });
+}
+
 int32_t zinc_sumcheck_prove_products(zinc_transcript *transcript, const uint64_t *const *mles, uint32_t n_mles,
                                      uint32_t nvars, uint32_t degree, uint32_t n_products, const uint64_t *coeffs,
                                      const uint32_t *masks, const uint64_t *modulus, uint32_t limbs, int32_t device,

@@ -1423,6 +1423,66 @@ sumcheck::ProverOutput sumcheck::prove_as_subprotocol_products(
     return out;
 }
 
+std::vector<sumcheck::ProverOutput> sumcheck::prove_as_subprotocol_batch(std::vector<BatchInstance> &instances, uint32_t nvars,
+                                                                         uint32_t degree, int device) {
+    std::vector<ProverOutput> out;
+    auto one = [&](BatchInstance &b) {
+        return b.ccs ? prove_as_subprotocol_ccs(*b.transcript, b.mles, nvars, degree, b.c, b.S, b.config, device)
+                     : prove_as_subprotocol_product(*b.transcript, b.mles, nvars, degree, b.config, device);
+    };
+    // What zip_sumcheck_prove_batch serves: up to 65535 instances of one shape (the same number of tables and of limbs),
+    // 1..16 variables.  Everything else, and ZIP_HIP_BATCH=0, is the loop.  So is a batch too small to beat the loop by
+    // more than the loop's own spread (profiles/sumcheck_batch.md, host tables): one workgroup plays the streamed rounds
+    // of an instance more slowly than the whole device plays them for the loop, so the line moves with num_vars -- from
+    // 2 instances on up to 2^12, from 3 up to 2^14, from 6 up to 2^16 (the sizes between the measured ones take the
+    // rule of the next larger one).
+    const size_t B = instances.size();
+    const size_t min_batch = nvars <= 12 ? 2 : nvars <= 14 ? 3 : 6;
+    bool batched = zip::batch_path_enabled() && B >= min_batch && B <= 65535 && nvars >= 1 && nvars <= 16;
+    for (size_t i = 0; i < B && batched; i++)
+        batched = instances[i].mles.size() == instances[0].mles.size() && !instances[i].mles.empty() && instances[i].mles.size() <= 8 &&
+                  instances[i].config.limbs == instances[0].config.limbs;
+    if (batched) {
+        const size_t ne = degree + 1, fl = instances[0].config.limbs;
+        std::vector<zip_sumcheck_comb> combs(B);
+        std::vector<zip_field> fields(B);
+        std::vector<zip_keccak_state> states(B);
+        std::vector<zip_sumcheck_instance> abi(B);
+        for (size_t i = 0; i < B; i++) {
+            BatchInstance &b = instances[i];
+            if (b.ccs) combs[i] = make_comb(b.mles.size(), b.c, b.S, b.config);
+            fields[i] = b.config.to_abi();
+            b.transcript->export_state(&states[i]);
+            abi[i] = {b.mles.data(), b.ccs ? &combs[i] : nullptr, &fields[i], &states[i]};
+        }
+        std::vector<uint64_t> msgs(B * nvars * ne * fl), rand(B * nvars * fl);
+        const int32_t rc = zip_sumcheck_prove_batch(device, abi.data(), (uint32_t)B, ZIP_MEM_HOST, (uint32_t)instances[0].mles.size(), nvars,
+                                                    degree, msgs.data(), rand.data());
+        if (rc == ZIP_OK) {
+            for (size_t i = 0; i < B; i++) {
+                instances[i].transcript->import_state(states[i]);
+                ProverOutput o;
+                for (uint32_t round = 0; round < nvars; round++) {
+                    std::vector<Limbs> msg(ne);
+                    for (size_t e = 0; e < ne; e++)
+                        for (size_t l = 0; l < fl; l++) msg[e][l] = msgs[((i * nvars + round) * ne + e) * fl + l];
+                    o.proof.msgs.push_back(std::move(msg));
+                    Limbs r{};
+                    for (size_t l = 0; l < fl; l++) r[l] = rand[(i * nvars + round) * fl + l];
+                    o.randomness.push_back(r);
+                }
+                out.push_back(std::move(o));
+            }
+            return out;
+        }
+        // a refusal leaves every transcript as it was: the loop then reports what is wrong the way it always did
+        if (rc != ZIP_ERR_INVALID_PARAM && rc != ZIP_ERR_UNSUPPORTED)
+            throw ZipError(ZipError::Device, std::string("zip_sumcheck_prove_batch: ") + zip_strerror(rc));
+    }
+    for (BatchInstance &b : instances) out.push_back(one(b));
+    return out;
+}
+
 // ---------------------------------------------------------------------------- CCS
 ccs::SparseMatrix ccs::SparseMatrix::from_coeffs(uint32_t n_rows, uint32_t n_cols,
                                                  const std::vector<std::vector<std::pair<int64_t, uint32_t>>> &coeffs) {

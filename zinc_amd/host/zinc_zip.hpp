@@ -384,6 +384,22 @@ ProverOutput prove_as_subprotocol_products(KeccakTranscript &transcript, const s
                                            uint32_t nvars, uint32_t degree,
                                            const std::vector<std::pair<Limbs, std::vector<uint32_t>>> &products,
                                            const FieldConfig &config, int device = 0);
+// MANY small sumchecks of one shape, each with its own transcript, tables and field: prove_as_subprotocol_product (ccs
+// false) or prove_as_subprotocol_ccs (ccs true: c and S as there) on every instance.  Up to 16 variables, with the same
+// number of tables and limbs in every instance and from 2 / 3 / 6 instances on up to 2^12 / 2^14 / 2^16 points
+// (profiles/sumcheck_batch.md), it is ONE zip_sumcheck_prove_batch call (one workgroup per instance, the sponges on the
+// device); ZIP_HIP_BATCH=0, fewer instances and every shape the batch does not serve take the loop.  Transcripts,
+// messages and challenges are the same either way.
+struct BatchInstance {
+    KeccakTranscript *transcript = nullptr;
+    std::vector<const uint64_t *> mles;  // host tables, as above
+    FieldConfig config;
+    bool ccs = false;
+    std::vector<Limbs> c;
+    std::vector<std::vector<uint32_t>> S;
+};
+std::vector<ProverOutput> prove_as_subprotocol_batch(std::vector<BatchInstance> &instances, uint32_t nvars, uint32_t degree,
+                                                     int device = 0);
 // SumCheckError / SpartanError (src/sumcheck.rs:28-38, src/zinc/errors.rs): what the verifier returns as Err
 struct SpartanError : std::runtime_error {
     enum Kind { SumCheckFailed, InvalidProofLength, MaxDegreeExceeded, PcsVerification } kind;

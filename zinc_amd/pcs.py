@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = (
     "zinc_zip_verify", "zinc_zip_evaluate", "zinc_commit_z_mle_and_prove_evaluation", "zinc_zip_proof_len",
     "zinc_zip_proof_num_roots", "zinc_zip_proof_read", "zinc_zip_proof_free", "zinc_zip_release_cached_contexts", "zinc_sumcheck_prove_product", "zinc_sumcheck_prove_ccs", "zinc_zip_data_download", "zinc_zip_data_upload", "zinc_merkle_tree_new",
     "zinc_prover_prove", "zinc_prover_prepare", "zinc_prepared_ccs_free", "zinc_verifier_verify",
-    "zinc_sumcheck_prove_products", "zinc_sumcheck_verify",
+    "zinc_sumcheck_prove_products", "zinc_sumcheck_verify", "zinc_sumcheck_prove_batch",
     "zinc_zip_batch_commit", "zinc_zip_batch_open", "zinc_zip_batch_open_challenges",
     "zinc_zip_batch_verify", "zinc_zip_batch_verify_challenges",
     "zinc_get_prime", "zinc_draw_random_field", "zinc_verifier_verify_checked",
@@ -149,6 +149,8 @@ def lib():
         L.zinc_zip_data_download.argtypes = [vp, vp, vp, vp]
         L.zinc_zip_data_upload.argtypes = [vp, vp, vp, vp, C.POINTER(vp)]
         L.zinc_merkle_tree_new.argtypes = [C.c_uint32, vp, C.c_size_t, C.c_uint32, C.c_int32, vp]
+        L.zinc_sumcheck_prove_batch.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_int32,
+                                                vp, vp]
         L.zinc_sumcheck_prove_product.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_int32, vp, vp]
         L.zinc_prover_prove.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_size_t, vp,
                                         C.c_size_t, vp, vp, C.c_uint32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp,
@@ -603,6 +605,44 @@ def sumcheck_prove_ccs(transcript: KeccakTranscript, mles, degree: int, c, S, fi
     _check(lib().zinc_sumcheck_prove_ccs(transcript._h, ptrs, K, nv, degree, len(S), cv.ctypes.data, masks.ctypes.data,
                                          field._m.ctypes.data, fl, device, msgs.ctypes.data, rand.ctypes.data))
     return msgs, rand
+
+
+def sumcheck_prove_batch(transcripts, mles, degree: int, fields, combs=None, device: int = 0):
+    """Many small sumchecks of one shape: on instance i what sumcheck_prove_product (combs is None or combs[i] is None)
+    or sumcheck_prove_ccs (combs[i] = (c, S) as there) does with transcripts[i], mles[i] ([K, 2^nv, limbs]) and fields[i].
+    From 2 / 3 / 6 instances on (up to 12 / 14 / 16 variables) it is one zip_sumcheck_prove_batch call (ZIP_HIP_BATCH=0,
+    more than 16 variables or fields of different limb counts: the loop).  Returns the lists ([msgs [nv, degree+1, limbs] ...], [randomness [nv, limbs] ...])."""
+    B = len(transcripts)
+    tabs = [np.ascontiguousarray(m, dtype=np.uint64) for m in mles]
+    K, n, _ = tabs[0].shape
+    nv = n.bit_length() - 1
+    assert all(t.shape[:2] == (K, n) for t in tabs) and len(tabs) == B and len(fields) == B
+    ptrs = (C.c_void_p * (B * K))(*[t[k].ctypes.data for t in tabs for k in range(K)])
+    trs = (C.c_void_p * B)(*[t._h for t in transcripts])
+    limbs = np.array([f.limbs for f in fields], dtype=np.uint32)
+    moduli = np.zeros((B, 4), dtype=np.uint64)
+    n_terms = np.zeros(B, dtype=np.uint32)
+    cv = np.zeros((B, 8, 4), dtype=np.uint64)
+    masks = np.zeros((B, 8), dtype=np.uint32)
+    for i, f in enumerate(fields):
+        moduli[i, :f.limbs] = np.asarray(f._m, dtype=np.uint64)[:f.limbs]
+        if combs is not None and combs[i] is not None:
+            c, S = combs[i]
+            n_terms[i] = len(S)
+            cv[i, :len(S), :f.limbs] = np.asarray(c, dtype=np.uint64).reshape(len(S), f.limbs)
+            masks[i, :len(S)] = [sum(1 << j for j in s) for s in S]
+    total = int(limbs.sum())
+    msgs = np.zeros(nv * (degree + 1) * total, np.uint64)
+    rand = np.zeros(nv * total, np.uint64)
+    _check(lib().zinc_sumcheck_prove_batch(trs, B, ptrs, K, nv, degree, n_terms.ctypes.data, cv.ctypes.data, masks.ctypes.data,
+                                           moduli.ctypes.data, limbs.ctypes.data, device, msgs.ctypes.data, rand.ctypes.data))
+    out_m, out_r, m_at, r_at = [], [], 0, 0
+    for fl in (int(x) for x in limbs):
+        out_m.append(msgs[m_at:m_at + nv * (degree + 1) * fl].reshape(nv, degree + 1, fl))
+        out_r.append(rand[r_at:r_at + nv * fl].reshape(nv, fl))
+        m_at += nv * (degree + 1) * fl
+        r_at += nv * fl
+    return out_m, out_r
 
 
 def sumcheck_prove_products(transcript: KeccakTranscript, mles, degree: int, masks, coeffs, field: FieldConfig,
