@@ -1079,4 +1079,107 @@ __global__ void __launch_bounds__(256) open_columns_ilv_kernel(OpenColsArgs a) {
     }
 }
 
+// The same openings where EVERY block of the launch is P whole passes (the `whole` path above) and the launch has its
+// table (wg_tab), with no vector instruction spent on an address.  What belongs to the lane -- its group, row and half,
+// where its 16 bytes go in the image, what it copies out -- is a handful of 32-bit offsets from the block's first group
+// of four rows; what belongs to the opening (the node per level, the four ranks, where its stream begins) is the same
+// for the whole wave and stays on the scalar unit.  Every load and store is a raw buffer operation: a resource over the
+// block's span (below 4 GiB where `layers` is not), a scalar offset for the level and the opening, the lane's offset.
+// (From pointer arithmetic the compiler folds the two shares into a 64-bit per-lane pointer and pays VALU adds per
+// load.)  D, the depth, is a template argument: the record length, every LDS offset and the copy-out's trip count are
+// immediates.  These waves run beside the hashing waves of the commit kernel at a higher priority, so a VALU instruction
+// saved here is one issued there (the counters of a step's gathers, before and after: profiles/gather_walk.md).
+// A workgroup that WALKED several openings of its row block with this set-up done once (2, 4, 5, 8; the next one's loads
+// in flight while an image streams out) was built and measured: fewer instructions still, and slower -- EXPERIMENTS.md.
+template <int P, int D>
+__global__ void __launch_bounds__(256) open_columns_ilv_scalar_kernel(OpenColsArgs a) {
+    extern __shared__ __align__(16) unsigned char img[];
+    static_assert(P >= 1 && D >= 12 && D <= 15, "whole passes; every wave has its first three levels");
+    constexpr uint32_t K = 4;  // Int<4> column values (checked by zip_ctx_create)
+    constexpr uint32_t REC = 8 + 32 * D, ROWS = 32 * P, N16 = ROWS * REC / 16;
+    if (a.prio) __builtin_amdgcn_s_setprio(2);  // memory-bound: do not queue behind older hashing waves
+    // (nothing writes the table while the kernel runs: through the constant address space its entry is a scalar load)
+    const oc_u32x4 t = ((const __attribute__((address_space(4))) oc_u32x4 *)(uintptr_t)a.wg_tab)[blockIdx.x];
+    const uint32_t ci = t.x & 0xFFFFu, col = t.x >> 16;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t sub = lane & 7u, gi = lane >> 3, half = lane & 1u;
+    const uint32_t cw2 = 2u * a.cw;
+    const uint32_t r0 = a.row_lo + blockIdx.y * ROWS;
+    const size_t g0 = r0 >> 2;                                  // the block's first group of four rows
+    const uint32_t pk_gs = 4u * a.pk_stride, tr_gs = cw2 * 128u;  // bytes per group: packed block, trees
+    // ---- the lane's share ----
+    const uint32_t toff = gi * tr_gs + sub * 16u;                // its 16 bytes of a level's line, pass 0
+    const uint32_t off0 = wave < 3u ? gi * pk_gs + sub * 16u : toff;  // (level `wave`: packed below level 3)
+    const uint32_t voff = gi * pk_gs + ((lane >> 1) & 3u) * 16u;  // wave 3: row lane / 2 of the pass, its 16-byte entry
+    const uint32_t dst0 = (4u * gi + (sub >> 1)) * REC + 8u + wave * 32u + half * 16u;  // level `wave` in the image
+    const uint32_t cpy = threadIdx.x * 16u;
+    const bool has3 = wave + 12u < (uint32_t)D;
+    // ---- the wave's share: resources from wave-uniform values only, scalar offsets per level (k = wave + 4 j) ----
+    constexpr int kRsrcFlags = 0x00020000;  // gfx9 raw buffer, 32-bit data format
+    const uint8_t *pk0 = a.pk + g0 * pk_gs, *tr0 = reinterpret_cast<const uint8_t *>(a.layers) + g0 * tr_gs;
+    const auto rs_pk = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(pk0), 0, (int)((8u * P + 1u) * pk_gs), kRsrcFlags);
+    const auto rs_tr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(tr0), 0, (int)((8u * P + 1u) * tr_gs), kRsrcFlags);
+    const auto rs_0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(wave < 3u ? pk0 : tr0), 0,
+                                                        (int)((8u * P + 1u) * (wave < 3u ? pk_gs : tr_gs)), kRsrcFlags);
+    const uint32_t pstep0 = 8u * (wave < 3u ? pk_gs : tr_gs);  // bytes from a pass to the next
+    const uint32_t rank = wave == 0u ? t.y >> 16 : wave == 1u ? t.z & 0xFFFFu : t.z >> 16;
+    uint32_t s[4];
+    s[0] = wave < 3u ? 4u * (wave == 0u ? a.pk_off0 : wave == 1u ? a.pk_off1 : a.pk_off2) + rank * 128u
+                     : (cw2 - (cw2 >> 3) + ((col >> 3) ^ 1u)) * 128u;
+#pragma unroll
+    for (int j = 1; j < 4; j++) {
+        const uint32_t k = wave + 4u * j;
+        s[j] = (cw2 - (cw2 >> k) + ((col >> k) ^ 1u)) * 128u;
+    }
+    oc_u32x4 v[P][4], e[P];
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        v[p][0] = __builtin_amdgcn_raw_buffer_load_b128(rs_0, off0, s[0] + p * pstep0, 0);
+        v[p][1] = __builtin_amdgcn_raw_buffer_load_b128(rs_tr, toff, s[1] + p * 8u * tr_gs, 0);
+        v[p][2] = __builtin_amdgcn_raw_buffer_load_b128(rs_tr, toff, s[2] + p * 8u * tr_gs, 0);
+    }
+    if (has3) {
+#pragma unroll
+        for (int p = 0; p < P; p++) v[p][3] = __builtin_amdgcn_raw_buffer_load_b128(rs_tr, toff, s[3] + p * 8u * tr_gs, 0);
+    }
+    const size_t col_bytes = (size_t)a.num_rows * (8 * K + REC);
+    uint8_t *base = a.out + (size_t)ci * col_bytes;
+    if (wave == 3u) {
+        // column values (open_z.rs:130-137), from the 16-byte entries (w0, w1, w2, sign) at the value's rank: the upper
+        // half of the Int<4> is the sign word four times
+#pragma unroll
+        for (int p = 0; p < P; p++)
+            e[p] = __builtin_amdgcn_raw_buffer_load_b128(rs_pk, voff, (t.y & 0xFFFFu) * 64u + p * 8u * pk_gs, 0);
+        const auto rs_val = __builtin_amdgcn_make_buffer_rsrc(base + (size_t)r0 * 8 * K, 0, (int)(ROWS * 8 * K), kRsrcFlags);
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+            const oc_u32x4 o = half ? oc_u32x4{e[p].w, e[p].w, e[p].w, e[p].w} : e[p];
+            __builtin_amdgcn_raw_buffer_store_b128(o, rs_val, lane * 16u, p * 32u * 8 * K, 0);
+        }
+    }
+    if (wave == 2u && lane < 32u) {  // be64(depth), pcs_transcript.rs:200-203
+#pragma unroll
+        for (int p = 0; p < P; p++)
+            *reinterpret_cast<uint64_t *>(img + (32u * p + lane) * REC) = __builtin_bswap64((uint64_t)D);
+    }
+#pragma unroll
+    for (int p = 0; p < P; p++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (j == 3 && !has3) continue;
+            uint64_t *dst = reinterpret_cast<uint64_t *>(img + dst0 + (uint32_t)p * 32u * REC + (uint32_t)j * 128u);
+            dst[0] = ((uint64_t)v[p][j].y << 32) | v[p][j].x;
+            dst[1] = ((uint64_t)v[p][j].w << 32) | v[p][j].z;
+        }
+    __syncthreads();
+    // ---- stream the image out: aligned 16-byte stores (the launcher has checked the stream's alignment) ----
+    const auto rs_rec = __builtin_amdgcn_make_buffer_rsrc(base + (size_t)a.num_rows * 8 * K + (size_t)r0 * REC, 0,
+                                                          (int)(ROWS * REC), kRsrcFlags);
+#pragma unroll
+    for (uint32_t i = 0; i < N16; i += 256) {
+        if (i + 256 <= N16 || threadIdx.x < N16 - i)
+            __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const oc_u32x4 *>(img + i * 16u + cpy), rs_rec, cpy, i * 16u, 0);
+    }
+}
+
 }  // namespace zipk

@@ -1480,6 +1480,25 @@ int32_t run_open_columns(zip_commitment *c, const uint32_t *cols_dv, uint32_t n_
         a.rows_per_block = (rpb + 3u) & ~3u;
         const size_t lds = (size_t)a.rows_per_block * rec;
         const dim3 grid(n_cols, (row_hi - row_lo + a.rows_per_block - 1) / a.rows_per_block), block(256);
+        // Every block 32 / 64 whole rows and the launch has its table: the kernel whose addressing stays on the scalar
+        // unit (open_columns_ilv_scalar_kernel).  Its lane offsets are 32-bit (a block's span of the packed block must
+        // fit), its copy-out is 16-byte stores only, and the depth is a template argument.
+        if (a.wg_tab && (a.rows_per_block == 32 || a.rows_per_block == 64) && ctx->depth >= 12 && ctx->depth <= 14 &&
+            row_lo % 4 == 0 && (row_hi - row_lo) % a.rows_per_block == 0 && a.num_rows % 2 == 0 &&
+            (reinterpret_cast<uintptr_t>(out_d) & 15) == 0 && (uint64_t)a.rows_per_block * a.pk_stride < (1ull << 31)) {
+            void (*kern)(OpenColsArgs) = nullptr;
+            const bool two = a.rows_per_block == 64;
+            switch (ctx->depth) {
+                case 12: kern = two ? open_columns_ilv_scalar_kernel<2, 12> : open_columns_ilv_scalar_kernel<1, 12>; break;
+                case 13: kern = two ? open_columns_ilv_scalar_kernel<2, 13> : open_columns_ilv_scalar_kernel<1, 13>; break;
+                default: kern = two ? open_columns_ilv_scalar_kernel<2, 14> : open_columns_ilv_scalar_kernel<1, 14>; break;
+            }
+            if (int32_t rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
+            LaunchTimer t(ctx, "open_columns_kernel", st);
+            hipLaunchKernelGGL(kern, grid, block, lds, st, a);
+            HIP_TRY(ctx, hipGetLastError());
+            return ZIP_OK;
+        }
         // (blocks of 32 / 64 whole rows take the kernel's branch-free path: P passes of 32 rows with all loads in flight)
         const void *fn = a.rows_per_block == 64 ? reinterpret_cast<const void *>(open_columns_ilv_kernel<true, 2>)
                                                 : reinterpret_cast<const void *>(open_columns_ilv_kernel<true, 1>);
