@@ -293,6 +293,25 @@ int32_t zinc_prover_prove_spec(const zinc_linear_code_spec *spec, const zip_spar
                                int32_t with_pcs, uint64_t *msgs1_out, uint64_t *msgs2_out, uint64_t *v_s_out,
                                uint64_t *r_y_out, zinc_zip_proof **zip_proof_out);
 
+/* zinc_prover_prove for n_instances proofs of ONE circuit, each with its own statement (public_inputs[i] of l[i] entries),
+ * witness (w_ccs[i] of w_len[i]), transcript and field (moduli: n_instances * 4 limbs, limbs[i] each): for every instance
+ * the same proof, r_y and transcript afterwards as zinc_prover_prove gives.  From 2 instances on (6 above 2^14 rows, 3
+ * above 2^12), with s <= 16 and one limb count in all fields, the circuit goes to the device once, as integers
+ * (zip_ccs_batch), the tables of all proofs are built with a launch count that does not depend on n_instances, and each of
+ * the two sumchecks is one zip_sumcheck_prove_batch; ZIP_HIP_BATCH=0, one instance and every other shape take the loop.
+ * Every shape check runs on every instance before any transcript is touched.  with_pcs != 0 adds the PCS step of every
+ * proof, one after the other: each proof draws its code's permutations from its own transcript (prover.rs:313), a batch
+ * commit has one code for all members.
+ *   spec          NULL: the default LinearCodeSpec
+ *   outputs       instance-major, each instance with its own number of limbs, per instance as zinc_prover_prove;
+ *                 zip_proofs_out: n_instances handles when with_pcs != 0 (each freed with zinc_zip_proof_free) */
+int32_t zinc_prover_prove_batch(const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                                uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c, uint32_t n_instances,
+                                const int64_t *const *public_inputs, const size_t *l, const int64_t *const *w_ccs,
+                                const size_t *w_len, zinc_transcript *const *transcripts, const uint64_t *moduli,
+                                const uint32_t *limbs, int32_t device, int32_t with_pcs, uint64_t *msgs1_out, uint64_t *msgs2_out,
+                                uint64_t *v_s_out, uint64_t *r_y_out, zinc_zip_proof **zip_proofs_out);
+
 /* ZincVerifier (src/zinc/verifier.rs): SpartanVerifier::verify (:105-139), and with with_pcs != 0 also
  * verify_pcs_proof (:221-273: RaaCode::new from the transcript, MultilinearZip::verify, the matrix MLEs at
  * (r_x, r_y) on the device, the final equation) -- Verifier::verify without its draw_random_field check (with it:

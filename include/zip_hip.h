@@ -46,7 +46,8 @@ extern "C" {
  * zip_batch_verify_calls.  So are zip_prime_test_base2, zip_get_prime and zip_prime_launch_counts, and
  * zip_ctx_set_proximity_tests / zip_ctx_proximity_tests: a ctx that never calls the setter behaves as before.  So is
  * zip_sumcheck_init_products, and so is zip_sumcheck_grid_counts.  So are zip_sumcheck_prove_batch and
- * zip_sumcheck_batch_counts: many small sumchecks in one launch, beside the one-at-a-time form that is unchanged.) */
+ * zip_sumcheck_batch_counts: many small sumchecks in one launch, beside the one-at-a-time form that is unchanged.  So are the
+ * zip_ccs_batch_* entry points: the Spartan tables of many proofs of one circuit, beside zip_ccs.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -609,6 +610,61 @@ int32_t zip_ccs_second_table(zip_ccs *c, const uint64_t *r_x, const uint64_t *ga
 int32_t zip_ccs_eval_matrices(zip_ccs *c, const uint64_t *r_x, const uint64_t *r_y, uint64_t *v_xy_out);
 int32_t zip_ccs_table(zip_ccs *c, zip_ccs_table_kind which, uint32_t index, const uint64_t **table_dev);
 int32_t zip_ccs_download(zip_ccs *c, zip_ccs_table_kind which, uint32_t index, uint64_t *out);
+
+/* ---- the same tables for MANY small proofs of ONE circuit, each proof in its own field ----------------------------
+ * A zip_ccs is one circuit mapped into one field.  In the protocol every proof draws its own field from its public input
+ * (draw_random_field), so a caller of the batch family that holds n proofs of one circuit cannot share a zip_ccs between
+ * them.  A zip_ccs_batch holds the matrices ONCE, as the integers they are -- CSR as given and the CSC form, built at
+ * creation, both with int64 values; no Montgomery copy of them exists, a kernel maps a value into the instance's field
+ * where it uses it -- and the tables of up to `capacity` proofs.  Every call below launches a number of kernels that does
+ * not depend on n (the instance is a grid dimension): set_z 2, eq_tables 1, second_tables 3.
+ *   zip_ccs_batch_create   t 1..7, s 1..16 (the bound of zip_sumcheck_prove_batch, which these tables feed), limbs 2..4,
+ *                          capacity 1..65535.  Device memory: capacity * (t + 4) tables of 2^s * limbs * 8 bytes, and
+ *                          capacity * 2^s * 8 bytes for the z of a HOST set_z; ZIP_ERR_ALLOC when that cannot be had.
+ *                          Errors before a device is looked for, in this order: ZIP_ERR_NULL (matrices, out);
+ *                          ZIP_ERR_INVALID_PARAM (t; s outside 1..28; limbs; capacity); the matrices one after the other
+ *                          with the rules and codes of zip_ccs_create (ZIP_ERR_NULL an array, ZIP_ERR_SHAPE n_cols != 2^s
+ *                          or n_rows > 2^s, ZIP_ERR_INVALID_PARAM a row_ptr that does not start at 0 or decreases,
+ *                          ZIP_ERR_SHAPE a column index >= 2^s); ZIP_ERR_UNSUPPORTED (s above 16).
+ *   zip_ccs_batch_set_z    n <= capacity proofs: fields[i] (all of the handle's `limbs`, each its own modulus) and z[i]
+ *                          of z_len[i] <= 2^s entries, zero-extended (HOST: gathered into one copy; DEVICE: read in place,
+ *                          and must stay until the call's work is done -- the next call that waits).  Builds z_i in
+ *                          F_{q_i} and the t tables M_k z_i of every instance.  Replaces everything a previous set_z and
+ *                          the calls after it left: the handle is reusable with another n and other fields.
+ *                          Errors before anything reaches the device, in this order: ZIP_ERR_NULL (b, fields, z, z_len, a
+ *                          fields[i], a z[i] with z_len[i] > 0); ZIP_ERR_INVALID_PARAM (n outside 1..capacity; a field
+ *                          whose limbs differ from the handle's; a modulus that is even or 1); ZIP_ERR_SHAPE (a z_len[i]
+ *                          above 2^s).  A refused call leaves the handle as it was.
+ *   zip_ccs_batch_eq_tables      build_eq_x_r(r_i) of every instance into `slot`; r: HOST, n * s * limbs limbs, instance-major
+ *   zip_ccs_batch_second_tables  per instance what zip_ccs_second_table does: eq(r_x_i) into slot 1, the second
+ *                          sumcheck's table with gamma_i, and V_s (v_s_out: HOST, n * t * limbs limbs, instance-major);
+ *                          r_x: n * s * limbs, gamma: n * limbs, both HOST.  One upload, three launches, one copy back,
+ *                          one synchronisation.
+ *                          Both: ZIP_ERR_NULL for a NULL argument, then ZIP_ERR_INVALID_PARAM for slot > 1 and for a
+ *                          handle on which set_z has not run.
+ *   zip_ccs_batch_table    device pointer of a table of 2^s elements of `instance` (< n), which / index as for
+ *                          zip_ccs_table; valid until the next call that rebuilds it or zip_ccs_batch_free.  set_z and
+ *                          eq_tables only enqueue their work; this call (and download, and second_tables) waits for what
+ *                          is still enqueued, so a pointer it returns may be handed to any stream.
+ *                          ZIP_ERR_INVALID_PARAM: set_z has not run, instance >= n, a table that has not been built.
+ *   zip_ccs_batch_download the same table copied to the HOST (tests)
+ *   zip_ccs_batch_counts   process-wide, monotonic, kept like zip_sumcheck_batch_counts: kernel launches of set_z /
+ *                          eq_tables / second_tables so far, and the instances handed to set_z.  Any pointer may be NULL.
+ * Calls on one handle are serialised inside the library.  Not part of this: the verifier's V_xy (zip_ccs_eval_matrices)
+ * in a batch, a circuit per instance, s above 16.  Additive: the ABI version stays 3. */
+typedef struct zip_ccs_batch zip_ccs_batch;
+int32_t zip_ccs_batch_create(int32_t device, const zip_sparse_matrix *matrices, uint32_t t, uint32_t s, uint32_t limbs,
+                             uint32_t capacity, zip_ccs_batch **out);
+void zip_ccs_batch_free(zip_ccs_batch *b); /* NULL is a no-op */
+const char *zip_ccs_batch_last_error(const zip_ccs_batch *b);
+int32_t zip_ccs_batch_set_z(zip_ccs_batch *b, const zip_field *const *fields, const int64_t *const *z, const size_t *z_len,
+                            uint32_t n, zip_mem_kind kind);
+int32_t zip_ccs_batch_eq_tables(zip_ccs_batch *b, const uint64_t *r, uint32_t slot);
+int32_t zip_ccs_batch_second_tables(zip_ccs_batch *b, const uint64_t *r_x, const uint64_t *gamma, uint64_t *v_s_out);
+int32_t zip_ccs_batch_table(zip_ccs_batch *b, uint32_t instance, zip_ccs_table_kind which, uint32_t index,
+                            const uint64_t **table_dev);
+int32_t zip_ccs_batch_download(zip_ccs_batch *b, uint32_t instance, zip_ccs_table_kind which, uint32_t index, uint64_t *out);
+void zip_ccs_batch_counts(uint64_t *kernel_launches, uint64_t *instances);
 
 /* Diagnostic: FieldMap for Int<4> (src/conversion.rs:86-100) of n arbitrary 256-bit values, as the
  * verifier applies it to column entries.  values: HOST n*4 limbs; out: HOST n*limbs Montgomery limbs. */

@@ -36,6 +36,8 @@ EXPORTED_SYMBOLS = (
     "zip_sumcheck_prove_batch", "zip_sumcheck_batch_counts",
     "zip_ccs_create", "zip_ccs_free", "zip_ccs_last_error", "zip_ccs_set_z", "zip_ccs_eq_table",
     "zip_ccs_second_table", "zip_ccs_table", "zip_ccs_download", "zip_ccs_eval_matrices",
+    "zip_ccs_batch_create", "zip_ccs_batch_free", "zip_ccs_batch_last_error", "zip_ccs_batch_set_z", "zip_ccs_batch_eq_tables",
+    "zip_ccs_batch_second_tables", "zip_ccs_batch_table", "zip_ccs_batch_download", "zip_ccs_batch_counts",
     "zip_batch_commit", "zip_batch_size", "zip_batch_free", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open",
     "zip_batch_verify", "zip_batch_verify_calls",
     "zip_prime_test_base2", "zip_get_prime", "zip_prime_launch_counts",
@@ -266,6 +268,22 @@ def lib():
     L.zip_ccs_table.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(vp)]
     L.zip_ccs_eval_matrices.argtypes = [vp, u64p, u64p, u64p]
     L.zip_ccs_download.argtypes = [vp, C.c_int, C.c_uint32, u64p]
+    L.zip_ccs_batch_create.argtypes = [C.c_int32, C.POINTER(SparseMatrix), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.POINTER(vp)]
+    L.zip_ccs_batch_free.argtypes = [vp]
+    L.zip_ccs_batch_free.restype = None
+    L.zip_ccs_batch_last_error.argtypes = [vp]
+    L.zip_ccs_batch_last_error.restype = C.c_char_p
+    L.zip_ccs_batch_set_z.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_int]
+    L.zip_ccs_batch_eq_tables.argtypes = [vp, u64p, C.c_uint32]
+    L.zip_ccs_batch_second_tables.argtypes = [vp, u64p, u64p, u64p]
+    L.zip_ccs_batch_table.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(vp)]
+    L.zip_ccs_batch_download.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32, u64p]
+    L.zip_ccs_batch_counts.argtypes = [C.POINTER(C.c_uint64)] * 2
+    L.zip_ccs_batch_counts.restype = None
+    for fn in ("zip_ccs_batch_create", "zip_ccs_batch_set_z", "zip_ccs_batch_eq_tables", "zip_ccs_batch_second_tables",
+               "zip_ccs_batch_table", "zip_ccs_batch_download"):
+        getattr(L, fn).restype = C.c_int32
     L.zip_commitment_free.argtypes = [vp]
     L.zip_commitment_free.restype = None
     L.zip_batch_commit.argtypes = [vp, i64p, C.c_size_t, C.c_uint32, C.c_int, u8p, C.POINTER(vp)]
@@ -1132,6 +1150,94 @@ class Ccs:
     def free(self):
         if getattr(self, "_h", None):
             lib().zip_ccs_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def ccs_batch_counts():
+    """(kernel launches of the zip_ccs_batch_* calls, instances handed to set_z) in this process so far"""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    lib().zip_ccs_batch_counts(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+class CcsBatch:
+    """zip_ccs_batch: the CCS matrices once, as integers, and the tables of SpartanProver::prove for up to `capacity`
+    proofs of that circuit, each proof in its own field.  matrices: as for Ccs.  Every method's launch count is
+    independent of the number of proofs."""
+
+    def __init__(self, matrices, s, limbs, capacity, device=0):
+        self.s, self.t, self.m, self.limbs, self.capacity, self.n = s, len(matrices), 1 << s, limbs, capacity, 0
+        self._h = None
+        keep = [(np.ascontiguousarray(M.row_ptr, dtype=np.uint32), np.ascontiguousarray(M.col_idx, dtype=np.uint32),
+                 np.ascontiguousarray(M.values, dtype=np.int64)) for M in matrices]
+        arr = (SparseMatrix * max(self.t, 1))()
+        for k, (M, (rp, ci, va)) in enumerate(zip(matrices, keep)):
+            arr[k] = SparseMatrix(M.n_rows, M.n_cols, rp.ctypes.data, ci.ctypes.data, va.ctypes.data)
+        h = C.c_void_p()
+        rc = lib().zip_ccs_batch_create(device, arr, self.t, s, limbs, capacity, C.byref(h))
+        if rc != ZIP_OK:
+            raise ZipError(rc, "zip_ccs_batch_create", strerror(rc))
+        self._h = h
+
+    def _check(self, rc, what):
+        if rc != ZIP_OK:
+            raise ZipError(rc, what, lib().zip_ccs_batch_last_error(self._h).decode())
+
+    def set_z(self, fields, zs):
+        """fields: one ZipField per proof; zs: one z per proof, all numpy int64 (host, gathered into one copy) or all CUDA
+        int64 tensors (read in place: keep them until the next call that waits)"""
+        n = len(zs)
+        assert len(fields) == n
+        host = n == 0 or isinstance(zs[0], np.ndarray)
+        if host:
+            keep = [np.ascontiguousarray(z, dtype=np.int64) for z in zs]
+            ptrs, lens = [z.ctypes.data for z in keep], [z.size for z in keep]
+        else:
+            keep = list(zs)
+            ptrs, lens = [z.data_ptr() for z in keep], [z.numel() for z in keep]
+        fa = (C.POINTER(ZipField) * max(n, 1))(*[C.pointer(f) for f in fields])
+        za = (C.c_void_p * max(n, 1))(*ptrs)
+        la = (C.c_size_t * max(n, 1))(*lens)
+        self._check(lib().zip_ccs_batch_set_z(self._h, C.cast(fa, C.c_void_p), C.cast(za, C.c_void_p), C.cast(la, C.c_void_p), n,
+                                              MEM_HOST if host else MEM_DEVICE), "zip_ccs_batch_set_z")
+        self._keep_z, self.n = keep, n
+
+    def eq_tables(self, r, slot):
+        """r: [n, s, limbs] Montgomery limbs"""
+        r = np.ascontiguousarray(r, dtype=np.uint64)
+        assert r.shape == (self.n, self.s, self.limbs)
+        self._check(lib().zip_ccs_batch_eq_tables(self._h, r.ctypes.data, slot), "zip_ccs_batch_eq_tables")
+
+    def second_tables(self, r_x, gamma):
+        """r_x: [n, s, limbs], gamma: [n, limbs].  Returns V_s [n, t, limbs]."""
+        r_x = np.ascontiguousarray(r_x, dtype=np.uint64)
+        gamma = np.ascontiguousarray(gamma, dtype=np.uint64)
+        assert r_x.shape == (self.n, self.s, self.limbs) and gamma.shape == (self.n, self.limbs)
+        vs = np.zeros((self.n, self.t, self.limbs), dtype=np.uint64)
+        self._check(lib().zip_ccs_batch_second_tables(self._h, r_x.ctypes.data, gamma.ctypes.data, vs.ctypes.data),
+                    "zip_ccs_batch_second_tables")
+        return vs
+
+    def table(self, instance, which, index=0) -> int:
+        """Device address of a table of 2^s field elements of one proof."""
+        p = C.c_void_p()
+        self._check(lib().zip_ccs_batch_table(self._h, instance, which, index, C.byref(p)), "zip_ccs_batch_table")
+        return int(p.value)
+
+    def download(self, instance, which, index=0):
+        out = np.zeros((self.m, self.limbs), dtype=np.uint64)
+        self._check(lib().zip_ccs_batch_download(self._h, instance, which, index, out.ctypes.data), "zip_ccs_batch_download")
+        return out
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib().zip_ccs_batch_free(self._h)
         self._h = None
 
     def __del__(self):

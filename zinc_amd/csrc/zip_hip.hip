@@ -36,6 +36,7 @@
 #include "kernels_sumcheck_wide.cuh"
 #include "kernels_sumcheck_products.cuh"
 #include "kernels_spartan.cuh"
+#include "kernels_spartan_batch.cuh"
 #include "kernels_prime.cuh"
 #include "rccl_dyn.h"
 
@@ -302,6 +303,26 @@ struct zip_ccs {
     uint64_t *eq_half = nullptr;                       // eq tables over the low / high half of the variables
     uint32_t dot_blocks = 0;
     bool have_z = false, have_eq[2] = {false, false}, have_second = false;
+};
+
+// The CCS matrices once, as integers, and the Spartan tables of up to `capacity` proofs of that circuit, each with its
+// own field (kernels_spartan_batch.cuh).
+struct zip_ccs_batch {
+    zip_ctx *ctx = nullptr;  // private plumbing context (stream, pool, error text)
+    uint32_t t = 0, s = 0, m = 0, fl = 0, capacity = 0;
+    CcsBatchMats mats{};     // device pointers: CSR as uploaded, CSC built once at creation; int64 values in both
+    uint64_t *tables = nullptr;  // capacity * (t + 4) tables of m elements: per instance z_f, mz[0..t), eq[0], eq[1], second
+    int64_t *z_d = nullptr;      // the z vectors of a HOST set_z, one after the other (capacity * m entries)
+    void *args_d = nullptr;      // n CcsBatchInst<fl>
+    uint64_t *chal_d = nullptr;  // capacity * (s + 1) elements: r of eq_tables, or r_x followed by every gamma
+    uint64_t *vs_d = nullptr;    // capacity * t elements
+    // what the asynchronous uploads read: kept until the stream has passed them (the next call that refills them waits)
+    std::vector<unsigned char> args_h;
+    std::vector<int64_t> z_h;
+    std::vector<uint64_t> chal_h;
+    uint32_t n = 0;  // instances of the last set_z; 0: none yet
+    bool have_eq[2] = {false, false}, have_second = false;
+    bool in_flight = false;  // work enqueued since the last wait: zip_ccs_batch_table waits before it hands a pointer out
 };
 
 namespace {
@@ -2655,6 +2676,92 @@ int32_t ccs_field(zip_ccs *c, HostField *hf) {
     zf.limbs = c->fl;
     memcpy(zf.modulus, c->modulus, sizeof zf.modulus);
     return make_field(c->ctx, &zf, hf);
+}
+
+// ---- zip_ccs_batch: the same tables for n proofs of one circuit, launches per call independent of n ----------------------
+// Process-wide (zip_ccs_batch_counts): kernel launches of the zip_ccs_batch_* calls and the instances handed to set_z
+std::atomic<uint64_t> g_ccs_batch_launches{0}, g_ccs_batch_instances{0};
+
+// table j of an instance: 0 z_f, 1 .. t M_k z, t + 1 / t + 2 eq slot 0 / 1, t + 3 the second sumcheck's table
+uint64_t *ccs_batch_table_at(const zip_ccs_batch *b, uint32_t instance, uint32_t j) {
+    return b->tables + ((((size_t)instance * (b->t + 4) + j) << b->s) * b->fl);
+}
+
+// waits for everything enqueued so far; the host staging vectors are free afterwards
+int32_t ccs_batch_wait(zip_ccs_batch *b) {
+    if (!b->in_flight) return ZIP_OK;
+    HIP_TRY(b->ctx, stream_wait(b->ctx->stream));
+    b->in_flight = false;
+    return ZIP_OK;
+}
+
+// the per-instance argument array into b->args_h; z_dev[i]: where instance i's z lies on the device
+template <int FL>
+void ccs_batch_fill_args(zip_ccs_batch *b, const std::vector<HostField> &fields, const std::vector<const int64_t *> &z_dev,
+                         const size_t *z_len, uint32_t n) {
+    b->args_h.assign((size_t)n * sizeof(CcsBatchInst<FL>), 0);
+    CcsBatchInst<FL> *args = reinterpret_cast<CcsBatchInst<FL> *>(b->args_h.data());
+    for (uint32_t i = 0; i < n; i++) {
+        CcsBatchInst<FL> &a = args[i];
+        a.f = to_dev<FL>(fields[i]);
+        a.quirk_mod = fields[i].quirk_mod;
+        a.z = z_dev[i];
+        a.z_len = z_len[i];
+        a.z_f = ccs_batch_table_at(b, i, 0);
+        for (uint32_t k = 0; k < b->t; k++) a.mz[k] = ccs_batch_table_at(b, i, 1 + k);
+        a.eq[0] = ccs_batch_table_at(b, i, b->t + 1);
+        a.eq[1] = ccs_batch_table_at(b, i, b->t + 2);
+        a.second = ccs_batch_table_at(b, i, b->t + 3);
+    }
+}
+
+template <int FL>
+int32_t ccs_batch_set_z_fl(zip_ccs_batch *b) {
+    zip_ctx *ctx = b->ctx;
+    const CcsBatchInst<FL> *args = static_cast<const CcsBatchInst<FL> *>(b->args_d);
+    const uint32_t bx = (b->m + 255) / 256;
+    {
+        LaunchTimer t(ctx, "ccs_batch_map_z_kernel");
+        hipLaunchKernelGGL(ccs_batch_map_z_kernel<FL>, dim3(bx, b->n), dim3(256), 0, ctx->stream, args, b->m);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    {
+        LaunchTimer t(ctx, "ccs_batch_spmv_kernel");
+        hipLaunchKernelGGL(ccs_batch_spmv_kernel<FL>, dim3(bx, b->t, b->n), dim3(256), 0, ctx->stream, b->mats, args);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    g_ccs_batch_launches += 2;
+    return ZIP_OK;
+}
+
+// eq(x, r_i) for every instance into `slot`; r_d: n * s elements on the device
+template <int FL>
+int32_t ccs_batch_eq_fl(zip_ccs_batch *b, const uint64_t *r_d, uint32_t slot) {
+    zip_ctx *ctx = b->ctx;
+    LaunchTimer t(ctx, "ccs_batch_eq_kernel");
+    hipLaunchKernelGGL(ccs_batch_eq_kernel<FL>, dim3((b->m + kCcsBatchEqPerBlock - 1) / kCcsBatchEqPerBlock, b->n), dim3(256), 0,
+                       ctx->stream, static_cast<const CcsBatchInst<FL> *>(b->args_d), r_d, b->s, slot);
+    HIP_TRY(ctx, hipGetLastError());
+    g_ccs_batch_launches++;
+    return ZIP_OK;
+}
+
+template <int FL>
+int32_t ccs_batch_second_fl(zip_ccs_batch *b, const uint64_t *gamma_d) {
+    zip_ctx *ctx = b->ctx;
+    const CcsBatchInst<FL> *args = static_cast<const CcsBatchInst<FL> *>(b->args_d);
+    {
+        LaunchTimer t(ctx, "ccs_batch_second_kernel");
+        hipLaunchKernelGGL(ccs_batch_second_kernel<FL>, dim3((b->m + 255) / 256, b->n), dim3(256), 0, ctx->stream, b->mats, args, gamma_d);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    {
+        LaunchTimer t(ctx, "ccs_batch_vs_kernel");  // calculate_V_s
+        hipLaunchKernelGGL(ccs_batch_vs_kernel<FL>, dim3(b->t, b->n), dim3(kCcsBatchVsThreads), 0, ctx->stream, args, b->m, b->vs_d);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    g_ccs_batch_launches += 2;
+    return ZIP_OK;
 }
 }  // namespace
 
@@ -5278,12 +5385,9 @@ void zip_sumcheck_free(zip_sumcheck *s) {
 }
 
 // ---------------------------------------------------------------------------- zip_ccs
-int32_t zip_ccs_create(int32_t device, const zip_sparse_matrix *mats, uint32_t t, uint32_t s, const zip_field *field,
-                       zip_ccs **out) {
-    if (!mats || !out || !field) return ZIP_ERR_NULL;
-    *out = nullptr;
-    if (t < 1 || t > (uint32_t)kCcsMaxMatrices || s < 1 || s > 28) return ZIP_ERR_INVALID_PARAM;
-    const uint32_t m = 1u << s;
+namespace {
+// the shape rules of the t matrices of a CCS with m = 2^s columns (zip_ccs_create, zip_ccs_batch_create)
+int32_t ccs_check_matrices(const zip_sparse_matrix *mats, uint32_t t, uint32_t m) {
     for (uint32_t k = 0; k < t; k++) {
         const zip_sparse_matrix &M = mats[k];
         if (!M.row_ptr || (M.row_ptr[M.n_rows] && (!M.col_idx || !M.values))) return ZIP_ERR_NULL;
@@ -5295,6 +5399,17 @@ int32_t zip_ccs_create(int32_t device, const zip_sparse_matrix *mats, uint32_t t
         for (uint32_t e = 0; e < M.row_ptr[M.n_rows]; e++)
             if (M.col_idx[e] >= m) return ZIP_ERR_SHAPE;  // the reference indexes out of bounds (panic)
     }
+    return ZIP_OK;
+}
+}  // namespace
+
+int32_t zip_ccs_create(int32_t device, const zip_sparse_matrix *mats, uint32_t t, uint32_t s, const zip_field *field,
+                       zip_ccs **out) {
+    if (!mats || !out || !field) return ZIP_ERR_NULL;
+    *out = nullptr;
+    if (t < 1 || t > (uint32_t)kCcsMaxMatrices || s < 1 || s > 28) return ZIP_ERR_INVALID_PARAM;
+    const uint32_t m = 1u << s;
+    if (int32_t rc = ccs_check_matrices(mats, t, m)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ZIP_ERR_NO_DEVICE;
     if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
@@ -5501,6 +5616,269 @@ int32_t zip_ccs_download(zip_ccs *c, zip_ccs_table_kind which, uint32_t index, u
     zip_ctx *ctx = c->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return copy_d2h_bounced(ctx, out, d, (size_t)c->m * c->fl * 8, ctx->stream);
+}
+
+// ---------------------------------------------------------------------------- zip_ccs_batch
+int32_t zip_ccs_batch_create(int32_t device, const zip_sparse_matrix *mats, uint32_t t, uint32_t s, uint32_t limbs,
+                             uint32_t capacity, zip_ccs_batch **out) {
+    // usage errors, before a device is looked for: NULLs, the ranges, the matrices, then this entry point's own size limit
+    if (!mats || !out) return ZIP_ERR_NULL;
+    *out = nullptr;
+    if (t < 1 || t > (uint32_t)kCcsMaxMatrices || s < 1 || s > 28) return ZIP_ERR_INVALID_PARAM;  // (zip_ccs_create's ranges)
+    if (limbs < 2 || limbs > 4 || capacity < 1 || capacity > 65535) return ZIP_ERR_INVALID_PARAM;
+    if (int32_t rc = ccs_check_matrices(mats, t, 1u << s)) return rc;
+    if (s > kCcsBatchMaxVars) return ZIP_ERR_UNSUPPORTED;
+    static_assert(kCcsBatchMaxVars == kBatchSumcheckMaxVars, "the tables feed zip_sumcheck_prove_batch");
+    const uint32_t m = 1u << s;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ZIP_ERR_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
+    const size_t elem = (size_t)limbs * 8, tab = (size_t)m * elem;
+    const size_t tables_bytes = (size_t)capacity * (t + 4) * tab, z_bytes = (size_t)capacity * m * 8;
+    {   // what cannot fit is refused without asking the allocator for it
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return ZIP_ERR_HIP;
+        if (tables_bytes + z_bytes > total_b) return ZIP_ERR_ALLOC;
+    }
+    zip_ctx *ctx = new (std::nothrow) zip_ctx();
+    zip_ccs_batch *b = new (std::nothrow) zip_ccs_batch();
+    if (!ctx || !b) { delete ctx; delete b; return ZIP_ERR_ALLOC; }
+    ctx->device = device;
+    ctx->recycle = true;
+    ctx->h2d_bounce_threshold = (size_t)256 << 10;  // (as zip_ccs_create)
+    b->ctx = ctx;
+    b->t = t;
+    b->s = s;
+    b->m = m;
+    b->fl = limbs;
+    b->capacity = capacity;
+    b->mats.t = t;
+    b->mats.m = m;
+    int32_t rc = ZIP_OK;
+    do {
+        if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { ctx->stream = nullptr; rc = ZIP_ERR_HIP; break; }
+        std::vector<void *> tmp;  // per-matrix cursors and tile sums: released once the stream has passed them
+        const uint32_t n_cnt = m + 1, tiles = (n_cnt + kScanTile - 1) / kScanTile;
+        for (uint32_t k = 0; k < t && rc == ZIP_OK; k++) {
+            const zip_sparse_matrix &M = mats[k];
+            const uint32_t nnz = M.row_ptr[M.n_rows];
+            uint32_t *row_ptr = nullptr, *col_idx = nullptr, *col_ptr = nullptr, *row_idx = nullptr, *cursor = nullptr, *sums = nullptr;
+            int64_t *vals = nullptr, *vals_t = nullptr;
+            if ((rc = pool_alloc(ctx, (size_t)(M.n_rows + 1) * 4, (void **)&row_ptr))) break;
+            if ((rc = pool_alloc(ctx, (size_t)nnz * 4, (void **)&col_idx))) break;
+            if ((rc = pool_alloc(ctx, (size_t)n_cnt * 4, (void **)&col_ptr))) break;
+            if ((rc = pool_alloc(ctx, (size_t)nnz * 4, (void **)&row_idx))) break;
+            if ((rc = pool_alloc(ctx, (size_t)nnz * 8, (void **)&vals))) break;
+            if ((rc = pool_alloc(ctx, (size_t)nnz * 8, (void **)&vals_t))) break;
+            if ((rc = pool_alloc(ctx, (size_t)n_cnt * 4, (void **)&cursor))) break;
+            tmp.push_back(cursor);
+            if ((rc = pool_alloc(ctx, (size_t)tiles * 4, (void **)&sums))) break;
+            tmp.push_back(sums);
+            b->mats.row_ptr[k] = row_ptr;
+            b->mats.col_idx[k] = col_idx;
+            b->mats.vals[k] = vals;
+            b->mats.col_ptr[k] = col_ptr;
+            b->mats.row_idx[k] = row_idx;
+            b->mats.vals_t[k] = vals_t;
+            b->mats.n_rows[k] = M.n_rows;
+            if ((rc = copy_h2d_bounced(ctx, row_ptr, M.row_ptr, (size_t)(M.n_rows + 1) * 4, ctx->stream))) break;
+            if (hipMemsetAsync(col_ptr, 0, (size_t)n_cnt * 4, ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
+            if (nnz) {
+                if ((rc = copy_h2d_bounced(ctx, col_idx, M.col_idx, (size_t)nnz * 4, ctx->stream))) break;
+                if ((rc = copy_h2d_bounced(ctx, vals, M.values, (size_t)nnz * 8, ctx->stream))) break;
+                const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)nnz + 255) / 256, 65535);
+                hipLaunchKernelGGL(csc_count_kernel, dim3(blocks), dim3(256), 0, ctx->stream, col_idx, nnz, col_ptr);
+            }
+            // col_ptr = inclusive scan of the counters (counts sit at [col + 1], so col_ptr[0] = 0)
+            hipLaunchKernelGGL(scan_tiles_kernel, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, col_ptr, n_cnt, sums,
+                               static_cast<const uint32_t *>(nullptr));
+            hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanBlock), 0, ctx->stream, sums, tiles);
+            hipLaunchKernelGGL(scan_tiles_kernel, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, col_ptr, n_cnt,
+                               static_cast<uint32_t *>(nullptr), static_cast<const uint32_t *>(sums));
+            if (hipMemcpyAsync(cursor, col_ptr, (size_t)n_cnt * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
+            if (nnz) {  // the int64 values travel as one-limb elements
+                const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)M.n_rows + 255) / 256, 65535);
+                hipLaunchKernelGGL(csc_fill_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, row_ptr, col_idx,
+                                   reinterpret_cast<const uint64_t *>(vals), M.n_rows, cursor, row_idx, reinterpret_cast<uint64_t *>(vals_t));
+            }
+            if (hipGetLastError() != hipSuccess) { rc = ZIP_ERR_HIP; break; }
+        }
+        if (rc) break;
+        if ((rc = pool_alloc(ctx, tables_bytes, (void **)&b->tables))) break;
+        if ((rc = pool_alloc(ctx, z_bytes, (void **)&b->z_d))) break;
+        const size_t inst_bytes = with_fl(limbs, [](auto FL) { return sizeof(CcsBatchInst<decltype(FL)::value>); });
+        if ((rc = pool_alloc(ctx, (size_t)capacity * inst_bytes, &b->args_d))) break;
+        if ((rc = pool_alloc(ctx, (size_t)capacity * (s + 1) * elem, (void **)&b->chal_d))) break;
+        if ((rc = pool_alloc(ctx, (size_t)capacity * t * elem, (void **)&b->vs_d))) break;
+        if (stream_wait(ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }  // ONE wait for all t transpositions
+        for (void *p : tmp) pool_release(ctx, p);
+    } while (0);
+    if (rc) {
+        zip_ccs_batch_free(b);
+        return rc;
+    }
+    *out = b;
+    return ZIP_OK;
+}
+
+void zip_ccs_batch_free(zip_ccs_batch *b) {
+    if (!b) return;
+    if (b->ctx) {
+        if (b->ctx->stream) (void)stream_wait(b->ctx->stream);  // the staging vectors die with the handle
+        zip_ctx_destroy(b->ctx);  // frees every pool block and the stream
+    }
+    delete b;
+}
+
+const char *zip_ccs_batch_last_error(const zip_ccs_batch *b) { return b && b->ctx ? b->ctx->last_error.c_str() : ""; }
+
+int32_t zip_ccs_batch_set_z(zip_ccs_batch *b, const zip_field *const *fields, const int64_t *const *z, const size_t *z_len,
+                            uint32_t n, zip_mem_kind kind) {
+    // usage errors, before anything reaches the device: every NULL, then n, the fields, then the lengths
+    if (!b || !fields || !z || !z_len) return ZIP_ERR_NULL;
+    zip_ctx *ctx = b->ctx;
+    const uint32_t scan = std::min(n, b->capacity);
+    for (uint32_t i = 0; i < scan; i++)
+        if (!fields[i] || (!z[i] && z_len[i])) return ZIP_ERR_NULL;
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (n < 1 || n > b->capacity) return fail(ctx, ZIP_ERR_INVALID_PARAM, "%u instances, the handle was made for 1..%u", n, b->capacity);
+    for (uint32_t i = 0; i < n; i++)
+        if (fields[i]->limbs != b->fl)
+            return fail(ctx, ZIP_ERR_INVALID_PARAM, "instance %u: a field of %u limbs, the handle was made for %u", i, fields[i]->limbs, b->fl);
+    // FieldConfig::new per instance (an even modulus or 1: ZIP_ERR_INVALID_PARAM); neighbours with the same modulus share the work
+    std::vector<HostField> hf(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (i && !memcmp(fields[i]->modulus, fields[i - 1]->modulus, 8 * (size_t)b->fl)) {
+            hf[i] = hf[i - 1];
+            continue;
+        }
+        if (int32_t rc = make_field_uncached(ctx, fields[i], &hf[i])) return rc;
+    }
+    for (uint32_t i = 0; i < n; i++)
+        if (z_len[i] > b->m) return fail(ctx, ZIP_ERR_SHAPE, "instance %u: z has %zu entries, the matrices %u columns", i, z_len[i], b->m);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int32_t rc;
+    if ((rc = ccs_batch_wait(b))) return rc;  // the staging vectors of the previous call
+    b->n = 0;  // (a call that fails from here on leaves no tables)
+    b->have_eq[0] = b->have_eq[1] = b->have_second = false;
+    std::vector<const int64_t *> z_dev(n);
+    if (kind == ZIP_MEM_HOST) {  // one gathered copy for all z
+        size_t total = 0;
+        for (uint32_t i = 0; i < n; i++) total += z_len[i];
+        b->z_h.resize(total);
+        for (size_t i = 0, at = 0; i < n; at += z_len[i], i++) {
+            if (z_len[i]) memcpy(b->z_h.data() + at, z[i], z_len[i] * 8);
+            z_dev[i] = b->z_d + at;
+        }
+        b->in_flight = true;
+        if (total && (rc = copy_h2d_bounced(ctx, b->z_d, b->z_h.data(), total * 8, ctx->stream))) return rc;
+    } else {
+        for (uint32_t i = 0; i < n; i++) z_dev[i] = z[i];
+    }
+    with_fl(b->fl, [&](auto FL) { ccs_batch_fill_args<decltype(FL)::value>(b, hf, z_dev, z_len, n); });
+    b->in_flight = true;
+    HIP_TRY(ctx, hipMemcpyAsync(b->args_d, b->args_h.data(), b->args_h.size(), hipMemcpyHostToDevice, ctx->stream));
+    b->n = n;
+    if ((rc = with_fl(b->fl, [&](auto FL) { return ccs_batch_set_z_fl<decltype(FL)::value>(b); }))) {
+        b->n = 0;
+        return rc;
+    }
+    g_ccs_batch_instances += n;
+    return ZIP_OK;
+}
+
+int32_t zip_ccs_batch_eq_tables(zip_ccs_batch *b, const uint64_t *r, uint32_t slot) {
+    if (!b || !r) return ZIP_ERR_NULL;
+    zip_ctx *ctx = b->ctx;
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (slot > 1) return fail(ctx, ZIP_ERR_INVALID_PARAM, "slot %u: 0 = eq(beta), 1 = eq(r_x)", slot);
+    if (!b->n) return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_ccs_batch_set_z has not run");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int32_t rc;
+    if ((rc = ccs_batch_wait(b))) return rc;  // (chal_h may still be on its way up)
+    const size_t words = (size_t)b->n * b->s * b->fl;
+    b->chal_h.assign(r, r + words);
+    b->in_flight = true;
+    HIP_TRY(ctx, hipMemcpyAsync(b->chal_d, b->chal_h.data(), words * 8, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = with_fl(b->fl, [&](auto FL) { return ccs_batch_eq_fl<decltype(FL)::value>(b, b->chal_d, slot); }))) return rc;
+    b->have_eq[slot] = true;
+    if (slot == 1) b->have_second = false;
+    return ZIP_OK;
+}
+
+int32_t zip_ccs_batch_second_tables(zip_ccs_batch *b, const uint64_t *r_x, const uint64_t *gamma, uint64_t *v_s_out) {
+    if (!b || !r_x || !gamma || !v_s_out) return ZIP_ERR_NULL;
+    zip_ctx *ctx = b->ctx;
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (!b->n) return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_ccs_batch_set_z has not run");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int32_t rc;
+    if ((rc = ccs_batch_wait(b))) return rc;
+    // one upload: every r_x, then every gamma
+    const size_t r_words = (size_t)b->n * b->s * b->fl, g_words = (size_t)b->n * b->fl;
+    b->chal_h.assign(r_x, r_x + r_words);
+    b->chal_h.insert(b->chal_h.end(), gamma, gamma + g_words);
+    b->in_flight = true;
+    b->have_second = false;
+    HIP_TRY(ctx, hipMemcpyAsync(b->chal_d, b->chal_h.data(), (r_words + g_words) * 8, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = with_fl(b->fl, [&](auto FL) { return ccs_batch_eq_fl<decltype(FL)::value>(b, b->chal_d, 1); }))) return rc;
+    if ((rc = with_fl(b->fl, [&](auto FL) { return ccs_batch_second_fl<decltype(FL)::value>(b, b->chal_d + r_words); }))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(v_s_out, b->vs_d, (size_t)b->n * b->t * b->fl * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = ccs_batch_wait(b))) return rc;
+    b->have_eq[1] = b->have_second = true;
+    return ZIP_OK;
+}
+
+int32_t zip_ccs_batch_table(zip_ccs_batch *b, uint32_t instance, zip_ccs_table_kind which, uint32_t index,
+                            const uint64_t **table_dev) {
+    if (!b || !table_dev) return ZIP_ERR_NULL;
+    zip_ctx *ctx = b->ctx;
+    *table_dev = nullptr;
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (!b->n) return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_ccs_batch_set_z has not run");
+    if (instance >= b->n) return fail(ctx, ZIP_ERR_INVALID_PARAM, "instance %u of %u", instance, b->n);
+    uint32_t j = 0;
+    switch (which) {
+        case ZIP_CCS_Z_FIELD:
+            break;
+        case ZIP_CCS_MZ:
+            if (index >= b->t) return fail(ctx, ZIP_ERR_INVALID_PARAM, "matrix %u of %u", index, b->t);
+            j = 1 + index;
+            break;
+        case ZIP_CCS_EQ:
+            if (index > 1 || !b->have_eq[index]) return fail(ctx, ZIP_ERR_INVALID_PARAM, "eq table %u has not been built", index);
+            j = b->t + 1 + index;
+            break;
+        case ZIP_CCS_SECOND:
+            if (!b->have_second) return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_ccs_batch_second_tables has not run");
+            j = b->t + 3;
+            break;
+        default:
+            return fail(ctx, ZIP_ERR_INVALID_PARAM, "unknown table kind %d", (int)which);
+    }
+    // the tables are read by other streams (zip_sumcheck_prove_batch has its own): complete before the pointer leaves
+    if (b->in_flight) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (int32_t rc = ccs_batch_wait(b)) return rc;
+    }
+    *table_dev = ccs_batch_table_at(b, instance, j);
+    return ZIP_OK;
+}
+
+int32_t zip_ccs_batch_download(zip_ccs_batch *b, uint32_t instance, zip_ccs_table_kind which, uint32_t index, uint64_t *out) {
+    if (!b || !out) return ZIP_ERR_NULL;
+    std::lock_guard<std::recursive_mutex> api_lock(b->ctx->api_mu);
+    const uint64_t *d = nullptr;
+    int32_t rc = zip_ccs_batch_table(b, instance, which, index, &d);
+    if (rc) return rc;
+    zip_ctx *ctx = b->ctx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return copy_d2h_bounced(ctx, out, d, (size_t)b->m * b->fl * 8, ctx->stream);
+}
+
+void zip_ccs_batch_counts(uint64_t *kernel_launches, uint64_t *instances) {
+    if (kernel_launches) *kernel_launches = g_ccs_batch_launches.load();
+    if (instances) *instances = g_ccs_batch_instances.load();
 }
 
 int32_t zip_sum_partials(zip_ctx *ctx, const uint64_t *uparts, const uint64_t *fparts, uint32_t n_parts,

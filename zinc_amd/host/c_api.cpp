@@ -664,6 +664,70 @@ int32_t zinc_prover_prove_spec(const zinc_linear_code_spec *spec, const zip_spar
     });
 }
 
+int32_t zinc_prover_prove_batch(const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                                uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c, uint32_t n_instances,
+                                const int64_t *const *public_inputs, const size_t *l, const int64_t *const *w_ccs,
+                                const size_t *w_len, zinc_transcript *const *transcripts, const uint64_t *moduli,
+                                const uint32_t *limbs, int32_t device, int32_t with_pcs, uint64_t *msgs1_out, uint64_t *msgs2_out,
+                                uint64_t *v_s_out, uint64_t *r_y_out, zinc_zip_proof **zip_proofs_out) {
+    if (!constraints || !s_masks || !c || !public_inputs || !l || !w_ccs || !w_len || !transcripts || !moduli || !limbs ||
+        !msgs1_out || !msgs2_out || !v_s_out || !r_y_out || (with_pcs && !zip_proofs_out))
+        return ZINC_ERR_NULL;
+    for (uint32_t i = 0; i < n_instances; i++) {
+        if (!transcripts[i] || (l[i] && !public_inputs[i]) || (w_len[i] && !w_ccs[i])) return ZINC_ERR_NULL;
+        if (zip_proofs_out) zip_proofs_out[i] = nullptr;
+    }
+    return guarded([&] {
+        zinc::ccs::CCS_Z ccs = square_ccs(t, s);
+        ccs.q = q;
+        ccs.d = d;
+        for (uint32_t i = 0; i < q; i++) {
+            ccs.c.push_back(c[i]);
+            ccs.S.emplace_back();
+            for (uint32_t j = 0; j < 32; j++)
+                if ((s_masks[i] >> j) & 1u) ccs.S.back().push_back(j);
+        }
+        std::vector<zinc::IntVec> z(n_instances);
+        std::vector<zinc::ZincProver::ZVector> zs(n_instances);
+        std::vector<zinc::KeccakTranscript *> tr(n_instances);
+        std::vector<FieldConfig> f;
+        for (uint32_t i = 0; i < n_instances; i++) {
+            z[i] = zinc::ZincProver::get_z_ccs(public_inputs[i], l[i], w_ccs[i], w_len[i], ccs.m);  // x || 1 || w
+            zs[i] = {z[i].data(), z[i].size()};
+            tr[i] = &transcripts[i]->t;
+            f.push_back(FieldConfig::make(moduli + (size_t)i * 4, limbs[i]));
+        }
+        const zinc::ZincProver prover(spec_of(spec), device);
+        std::vector<zinc::SpartanProof> sp(n_instances);
+        std::vector<std::vector<Limbs>> r_y(n_instances);
+        if (with_pcs) {
+            auto proofs = prover.prove_batch(constraints, ccs, zs, tr, f, &r_y);
+            for (uint32_t i = 0; i < n_instances; i++) {
+                sp[i] = std::move(proofs[i].spartan_proof);
+                zip_proofs_out[i] = new zinc_zip_proof{std::move(proofs[i].zip_proof), limbs[i]};
+            }
+        } else {
+            auto res = prover.spartan_prove_batch(constraints, ccs, zs, tr, f);
+            for (uint32_t i = 0; i < n_instances; i++) {
+                sp[i] = std::move(res[i].first);
+                r_y[i] = std::move(res[i].second);
+            }
+        }
+        size_t m1 = 0, m2 = 0, vs = 0, ry = 0;  // instance-major, each instance with its own number of limbs
+        for (uint32_t i = 0; i < n_instances; i++) {
+            auto put = [&](uint64_t *dst, size_t &at, const Limbs &v) {
+                for (uint32_t k = 0; k < limbs[i]; k++) dst[at++] = v[k];
+            };
+            for (const auto &round : sp[i].linearization_sumcheck.msgs)
+                for (uint32_t e = 0; e <= d + 1; e++) put(msgs1_out, m1, round[e]);
+            for (const auto &round : sp[i].second_sumcheck.msgs)
+                for (uint32_t e = 0; e < 3; e++) put(msgs2_out, m2, round[e]);
+            for (const Limbs &v : sp[i].V_s) put(v_s_out, vs, v);
+            for (const Limbs &v : r_y[i]) put(r_y_out, ry, v);
+        }
+    });
+}
+
 int32_t zinc_verifier_verify(const zip_sparse_matrix *constraints, uint32_t t, uint32_t s, uint32_t d, uint32_t q,
                              const uint32_t *s_masks, const int64_t *c, zinc_transcript *transcript, const uint64_t *modulus,
                              uint32_t limbs, int32_t device, zinc_prepared_ccs *prepared, const uint64_t *msgs1,

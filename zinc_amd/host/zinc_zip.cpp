@@ -1547,6 +1547,28 @@ const uint64_t *ccs_table(zip_ccs *h, zip_ccs_table_kind which, uint32_t index) 
 }
 }  // namespace
 
+namespace {
+// the shape the reference's prover supports (see the header), checked before anything else of a proof; -> ccs.S
+std::vector<std::vector<uint32_t>> spartan_shape(size_t n_matrices, const ccs::CCS_Z &ccs, size_t z_len) {
+    if (ccs.s == 0 || ccs.s > 28 || ccs.m != ((size_t)1 << ccs.s) || ccs.n != ccs.m || ccs.s_prime != ccs.s)
+        throw std::logic_error("assertion failed: rx.len() == num_rows (compute_eval_table_sparse): m == n == 2^s is required");
+    if (n_matrices != ccs.t || ccs.S.size() != ccs.q || ccs.c.size() != ccs.q)
+        throw std::logic_error("CCS sizes and the statement disagree");
+    if (z_len > ccs.m) throw std::logic_error("LengthsNotEqual: M.n_cols != z.len()");
+    std::vector<std::vector<uint32_t>> S(ccs.q);
+    size_t pos = 0;
+    for (size_t i = 0; i < ccs.q; i++) {
+        if (ccs.c[i] == 0) throw ZipError(ZipError::InvalidPcsParam, "a zero CCS coefficient shifts the MLE list the combination function indexes");
+        for (size_t j : ccs.S[i]) {
+            if (j != pos++) throw ZipError(ZipError::InvalidPcsParam, "ccs.S must list the matrices 0..t-1 in order");
+            S[i].push_back((uint32_t)j);
+        }
+    }
+    if (pos != ccs.t) throw ZipError(ZipError::InvalidPcsParam, "ccs.S must list the matrices 0..t-1 in order");
+    return S;
+}
+}  // namespace
+
 PreparedCcs::PreparedCcs(const ccs::Statement_Z &statement, const ccs::CCS_Z &ccs, const FieldConfig &config, int device)
     : t_((uint32_t)ccs.t), s_((uint32_t)ccs.s), limbs_(config.limbs), modulus_(config.modulus), device_(device) {
     if (ccs.s == 0 || ccs.s > 28 || ccs.m != ((size_t)1 << ccs.s) || ccs.n != ccs.m || ccs.s_prime != ccs.s)
@@ -1568,24 +1590,7 @@ std::pair<SpartanProof, std::vector<Limbs>> ZincProver::spartan_prove(const ccs:
                                                                       const int64_t *z_ccs, size_t z_len,
                                                                       KeccakTranscript &transcript, const ccs::CCS_Z &ccs,
                                                                       const FieldConfig &config, PreparedCcs *prepared) const {
-    // the shape the reference's prover supports (see the header)
-    if (ccs.s == 0 || ccs.s > 28 || ccs.m != ((size_t)1 << ccs.s) || ccs.n != ccs.m || ccs.s_prime != ccs.s)
-        throw std::logic_error("assertion failed: rx.len() == num_rows (compute_eval_table_sparse): m == n == 2^s is required");
-    if (statement.constraints.size() != ccs.t || ccs.S.size() != ccs.q || ccs.c.size() != ccs.q)
-        throw std::logic_error("CCS sizes and the statement disagree");
-    if (z_len > ccs.m) throw std::logic_error("LengthsNotEqual: M.n_cols != z.len()");
-    std::vector<std::vector<uint32_t>> S(ccs.q);
-    {
-        size_t pos = 0;
-        for (size_t i = 0; i < ccs.q; i++) {
-            if (ccs.c[i] == 0) throw ZipError(ZipError::InvalidPcsParam, "a zero CCS coefficient shifts the MLE list the combination function indexes");
-            for (size_t j : ccs.S[i]) {
-                if (j != pos++) throw ZipError(ZipError::InvalidPcsParam, "ccs.S must list the matrices 0..t-1 in order");
-                S[i].push_back((uint32_t)j);
-            }
-        }
-        if (pos != ccs.t) throw ZipError(ZipError::InvalidPcsParam, "ccs.S must list the matrices 0..t-1 in order");
-    }
+    const std::vector<std::vector<uint32_t>> S = spartan_shape(statement.constraints.size(), ccs, z_len);
     const uint32_t s = (uint32_t)ccs.s, t = (uint32_t)ccs.t;
     StageTimer timer;
     std::unique_ptr<PreparedCcs> own;
@@ -1655,6 +1660,17 @@ ZincProof ZincProver::prove_z(const ccs::Statement_Z &statement, const int64_t *
                               const ccs::CCS_Z &ccs, const FieldConfig &config, std::vector<Limbs> *r_y_out,
                               PreparedCcs *prepared) const {
     auto [spartan_proof, r_y] = spartan_prove(statement, z_ccs, z_len, transcript, ccs, config, prepared);
+    ZincProof out;
+    out.spartan_proof = std::move(spartan_proof);
+    StageTimer timer;
+    out.zip_proof = pcs_step(z_ccs, z_len, ccs, r_y, transcript, config);
+    timer.lap("commit_z_mle_and_prove_eval");
+    if (r_y_out) *r_y_out = std::move(r_y);
+    return out;
+}
+
+zip::ZipProof ZincProver::pcs_step(const int64_t *z_ccs, size_t z_len, const ccs::CCS_Z &ccs, const std::vector<Limbs> &r_y,
+                                   KeccakTranscript &transcript, const FieldConfig &config) const {
     // commit_z_mle_and_prove_evaluation (prover.rs:305-327); z_mle = from_evaluations_slice(s_prime, z_ccs)
     const size_t n_mle = (size_t)1 << ccs.s_prime;
     IntVec padded;
@@ -1665,13 +1681,195 @@ ZincProof ZincProver::prove_z(const ccs::Statement_Z &statement, const int64_t *
         if (z_len < n_mle) std::memset(padded.data() + z_len, 0, (n_mle - z_len) * 8);
         z_mle = padded.data();
     }
-    ZincProof out;
-    out.spartan_proof = std::move(spartan_proof);
+    return zip::commit_z_mle_and_prove_evaluation(lc_spec_, z_mle, ccs.m, r_y.data(), r_y.size(), transcript, config, device_);
+}
+
+// ---- B proofs of one circuit (zip_ccs_batch + zip_sumcheck_prove_batch) -------------------------------------------------
+namespace {
+void ccs_batch_check(zip_ccs_batch *h, int32_t rc, const char *what) {
+    if (rc == ZIP_OK) return;
+    const std::string detail = h ? zip_ccs_batch_last_error(h) : "";
+    const std::string msg = std::string(what) + ": " + (detail.empty() ? zip_strerror(rc) : detail);
+    if (rc == ZIP_ERR_SHAPE) throw std::logic_error(msg);  // the reference panics / LengthsNotEqual
+    throw ZipError(rc == ZIP_ERR_INVALID_PARAM ? ZipError::InvalidPcsParam : ZipError::Device, msg);
+}
+struct CcsBatchHandle {
+    zip_ccs_batch *h = nullptr;
+    ~CcsBatchHandle() { zip_ccs_batch_free(h); }
+};
+// From how many instances on the batch is taken: where it beat the loop over spartan_prove by more than the loop's own
+// spread (profiles/spartan_batch.md, t = 3, 4 limbs).  2 proofs win at 2^10 and 2^12 (1.31x, 1.12x) and lose at 2^14 and
+// 2^16 (0.84x, 0.47x); 3 win at 2^14 (1.34x); at 2^16 3 and 4 lose (0.76x, 0.98x) and 6 win (1.48x).  The batch costs what
+// its two batch sumchecks cost -- one workgroup plays an instance's streamed rounds more slowly than the whole device
+// plays them for the loop -- so the line is prove_as_subprotocol_batch's; a size between the measured ones takes the rule
+// of the next larger one.
+// ZIP_HIP_SPARTAN_MIN_BATCH=n (n >= 2, read per call) puts the line at n for every size: how tools/spartan_batch_times.py
+// measures the batch below the line.
+size_t min_spartan_batch(size_t s) {
+    if (const char *e = std::getenv("ZIP_HIP_SPARTAN_MIN_BATCH")) {
+        const long n = std::atol(e);
+        if (n >= 2) return (size_t)n;
+    }
+    return s <= 12 ? 2 : s <= 14 ? 3 : 6;
+}
+}  // namespace
+
+std::vector<ZincProver::SpartanOutput> ZincProver::spartan_prove_batch(const ccs::Statement_Z &statement, const ccs::CCS_Z &ccs,
+                                                                       const std::vector<ZVector> &zs,
+                                                                       const std::vector<KeccakTranscript *> &transcripts,
+                                                                       const std::vector<FieldConfig> &configs) const {
+    if (statement.constraints.size() != ccs.t) throw std::logic_error("CCS sizes and the statement disagree");
+    std::vector<zip_sparse_matrix> mats;
+    for (const auto &M : statement.constraints) mats.push_back(M.to_abi());
+    return spartan_prove_batch(mats.data(), ccs, zs, transcripts, configs);
+}
+
+std::vector<ZincProver::SpartanOutput> ZincProver::spartan_prove_batch(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs,
+                                                                       const std::vector<ZVector> &zs,
+                                                                       const std::vector<KeccakTranscript *> &transcripts,
+                                                                       const std::vector<FieldConfig> &configs) const {
+    const size_t B = zs.size();
+    if (transcripts.size() != B || configs.size() != B) throw std::logic_error("spartan_prove_batch: one transcript and one field per z");
+    if (!matrices && B) throw std::logic_error("spartan_prove_batch: no matrices");
+    // every shape check of spartan_prove on every instance, before any transcript is touched
+    std::vector<std::vector<uint32_t>> S;
+    for (size_t i = 0; i < B; i++) {
+        if (!transcripts[i] || (!zs[i].z && zs[i].len)) throw std::logic_error("spartan_prove_batch: a NULL transcript or z");
+        S = spartan_shape(ccs.t, ccs, zs[i].len);
+    }
+    const uint32_t s = (uint32_t)ccs.s, t = (uint32_t)ccs.t;
+    bool batched = zip::batch_path_enabled() && B >= 2 && B >= min_spartan_batch(s) && B <= 65535 && s <= 16;
+    for (size_t i = 1; i < B && batched; i++) batched = configs[i].limbs == configs[0].limbs;
+    std::vector<SpartanOutput> out;
+    if (!batched) {
+        ccs::Statement_Z st;
+        st.constraints.resize(t);  // the matrices go to the device straight from the caller's arrays
+        for (size_t i = 0; i < B; i++) {  // per proof, as the reference maps the matrices per proof
+            PreparedCcs prep(matrices, t, s, configs[i], device_);
+            out.push_back(spartan_prove(st, zs[i].z, zs[i].len, *transcripts[i], ccs, configs[i], &prep));
+        }
+        return out;
+    }
+    const uint32_t fl = configs[0].limbs;
     StageTimer timer;
-    out.zip_proof = zip::commit_z_mle_and_prove_evaluation(lc_spec_, z_mle, ccs.m, r_y.data(), r_y.size(), transcript,
-                                                           config, device_);
-    timer.lap("commit_z_mle_and_prove_eval");
-    if (r_y_out) *r_y_out = std::move(r_y);
+    CcsBatchHandle dev;
+    ccs_batch_check(nullptr, zip_ccs_batch_create(device_, matrices, t, s, fl, (uint32_t)B, &dev.h), "zip_ccs_batch_create");
+    timer.lap("zip_ccs_batch_create");
+    std::vector<zip_field> fields(B);
+    std::vector<const zip_field *> field_ptrs(B);
+    std::vector<const int64_t *> z_ptrs(B);
+    std::vector<size_t> z_lens(B);
+    for (size_t i = 0; i < B; i++) {
+        fields[i] = configs[i].to_abi();
+        field_ptrs[i] = &fields[i];
+        z_ptrs[i] = zs[i].z;
+        z_lens[i] = zs[i].len;
+    }
+    // z_ccs -> F_q (prover.rs:236); calculate_Mz_mles -- of every proof
+    ccs_batch_check(dev.h, zip_ccs_batch_set_z(dev.h, field_ptrs.data(), z_ptrs.data(), z_lens.data(), (uint32_t)B, ZIP_MEM_HOST),
+                    "zip_ccs_batch_set_z");
+    timer.lap("zip_ccs_batch_set_z");
+    auto table = [&](size_t i, zip_ccs_table_kind which, uint32_t index) {
+        const uint64_t *p = nullptr;
+        ccs_batch_check(dev.h, zip_ccs_batch_table(dev.h, (uint32_t)i, which, index, &p), "zip_ccs_batch_table");
+        return p;
+    };
+    // one zip_sumcheck_prove_batch over device tables; the transcripts travel as sponge states and come back
+    auto sumcheck = [&](const std::vector<std::vector<const uint64_t *>> &tables, uint32_t degree, const std::vector<zip_sumcheck_comb> *combs) {
+        const size_t ne = degree + 1;
+        std::vector<zip_keccak_state> states(B);
+        std::vector<zip_sumcheck_instance> abi(B);
+        for (size_t i = 0; i < B; i++) {
+            transcripts[i]->export_state(&states[i]);
+            abi[i] = {tables[i].data(), combs ? &(*combs)[i] : nullptr, &fields[i], &states[i]};
+        }
+        std::vector<uint64_t> msgs(B * s * ne * fl), rand(B * s * fl);
+        const int32_t rc = zip_sumcheck_prove_batch(device_, abi.data(), (uint32_t)B, ZIP_MEM_DEVICE, (uint32_t)tables[0].size(), s, degree,
+                                                    msgs.data(), rand.data());
+        if (rc != ZIP_OK) throw ZipError(rc == ZIP_ERR_INVALID_PARAM ? ZipError::InvalidPcsParam : ZipError::Device,
+                                         std::string("zip_sumcheck_prove_batch: ") + zip_strerror(rc));
+        std::vector<sumcheck::ProverOutput> res(B);
+        for (size_t i = 0; i < B; i++) {
+            transcripts[i]->import_state(states[i]);
+            for (uint32_t round = 0; round < s; round++) {
+                std::vector<Limbs> msg(ne);
+                for (size_t e = 0; e < ne; e++)
+                    for (size_t l = 0; l < fl; l++) msg[e][l] = msgs[((i * s + round) * ne + e) * fl + l];
+                res[i].proof.msgs.push_back(std::move(msg));
+                Limbs r{};
+                for (size_t l = 0; l < fl; l++) r[l] = rand[(i * s + round) * fl + l];
+                res[i].randomness.push_back(r);
+            }
+        }
+        return res;
+    };
+
+    // ---- sumcheck_1 (prover.rs:242-259)
+    std::vector<uint64_t> flat(B * s * fl);
+    for (size_t i = 0; i < B; i++) {
+        transcripts[i]->absorb(reinterpret_cast<const uint8_t *>("beta_s"), 6);  // squeeze_beta_challenges
+        for (uint32_t j = 0; j < s; j++) {
+            const Limbs b = transcripts[i]->get_challenge(configs[i]);
+            std::copy(b.begin(), b.begin() + fl, flat.begin() + (i * s + j) * fl);
+        }
+    }
+    ccs_batch_check(dev.h, zip_ccs_batch_eq_tables(dev.h, flat.data(), 0), "zip_ccs_batch_eq_tables");
+    std::vector<std::vector<const uint64_t *>> g(B);  // prepare_lin_sumcheck_polynomial: [Mz_0 .. Mz_{t-1}, eq(beta)], degree d + 1
+    std::vector<zip_sumcheck_comb> combs(B);
+    for (size_t i = 0; i < B; i++) {
+        for (uint32_t k = 0; k < t; k++) g[i].push_back(table(i, ZIP_CCS_MZ, k));
+        g[i].push_back(table(i, ZIP_CCS_EQ, 0));
+        std::vector<Limbs> c_f;
+        for (int64_t c : ccs.c) c_f.push_back(map_to_field(configs[i], c));  // CCS_Z::map_to_field, ccs_z.rs:147
+        combs[i] = make_comb(g[i].size(), c_f, S, configs[i]);
+    }
+    timer.lap("beta, zip_ccs_batch_eq_tables");
+    auto sc1 = sumcheck(g, (uint32_t)ccs.d + 1, &combs);
+    timer.lap("sumcheck_1 (batch)");
+
+    // ---- sumcheck_2 (prover.rs:261-303)
+    std::vector<uint64_t> gammas(B * fl), vs(B * t * fl);
+    for (size_t i = 0; i < B; i++) {
+        transcripts[i]->absorb(reinterpret_cast<const uint8_t *>("gamma"), 5);  // squeeze_gamma_challenge
+        const Limbs gamma = transcripts[i]->get_challenge(configs[i]);
+        std::copy(gamma.begin(), gamma.begin() + fl, gammas.begin() + i * fl);
+        for (uint32_t j = 0; j < s; j++)
+            std::copy(sc1[i].randomness[j].begin(), sc1[i].randomness[j].begin() + fl, flat.begin() + (i * s + j) * fl);
+    }
+    ccs_batch_check(dev.h, zip_ccs_batch_second_tables(dev.h, flat.data(), gammas.data(), vs.data()), "zip_ccs_batch_second_tables");
+    timer.lap("gamma, zip_ccs_batch_second_tables");
+    std::vector<std::vector<const uint64_t *>> two(B);
+    for (size_t i = 0; i < B; i++) two[i] = {table(i, ZIP_CCS_SECOND, 0), table(i, ZIP_CCS_Z_FIELD, 0)};
+    auto sc2 = sumcheck(two, 2, nullptr);
+    timer.lap("sumcheck_2 (batch)");
+
+    for (size_t i = 0; i < B; i++) {
+        SpartanProof proof;
+        proof.linearization_sumcheck = std::move(sc1[i].proof);
+        proof.second_sumcheck = std::move(sc2[i].proof);
+        for (uint32_t k = 0; k < t; k++) {  // calculate_V_s (prover.rs:330-347), computed with the second table
+            Limbs v{};
+            for (uint32_t l = 0; l < fl; l++) v[l] = vs[(i * t + k) * fl + l];
+            proof.V_s.push_back(v);
+        }
+        out.emplace_back(std::move(proof), std::move(sc2[i].randomness));
+    }
+    return out;
+}
+
+std::vector<ZincProof> ZincProver::prove_batch(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs, const std::vector<ZVector> &zs,
+                                               const std::vector<KeccakTranscript *> &transcripts,
+                                               const std::vector<FieldConfig> &configs, std::vector<std::vector<Limbs>> *r_y_out) const {
+    auto spartan = spartan_prove_batch(matrices, ccs, zs, transcripts, configs);
+    // The PCS step stays a loop: every proof draws the permutations of its RAA code from its own transcript
+    // (prover.rs:313), zip_batch_commit has one code for all its members.
+    std::vector<ZincProof> out(zs.size());
+    if (r_y_out) r_y_out->clear();
+    for (size_t i = 0; i < zs.size(); i++) {
+        out[i].spartan_proof = std::move(spartan[i].first);
+        out[i].zip_proof = pcs_step(zs[i].z, zs[i].len, ccs, spartan[i].second, *transcripts[i], configs[i]);
+        if (r_y_out) r_y_out->push_back(std::move(spartan[i].second));
+    }
     return out;
 }
 

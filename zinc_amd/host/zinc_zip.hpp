@@ -500,6 +500,31 @@ class ZincProver {
     std::pair<SpartanProof, std::vector<Limbs>> spartan_prove(const ccs::Statement_Z &statement, const int64_t *z_ccs, size_t z_len,
                                                               KeccakTranscript &transcript, const ccs::CCS_Z &ccs,
                                                               const FieldConfig &config, PreparedCcs *prepared = nullptr) const;
+    // B proofs of ONE circuit, each with its own z, transcript and field: for every instance exactly what spartan_prove
+    // does -- the same proof, r_y and transcript afterwards.  From 2 instances on, with s <= 16 and one limb count in all
+    // configs (and not below the line of min_spartan_batch, zinc_zip.cpp), the matrices go to the device ONCE, as integers
+    // (zip_ccs_batch), the tables of all proofs are built with a launch count that does not depend on B, and each of the
+    // two sumchecks is ONE zip_sumcheck_prove_batch call over the device tables.  ZIP_HIP_BATCH=0, one instance and every
+    // shape the batch does not serve take the loop over spartan_prove.  Every shape check of spartan_prove runs on every
+    // instance before any transcript is touched.
+    struct ZVector {
+        const int64_t *z = nullptr;
+        size_t len = 0;
+    };
+    using SpartanOutput = std::pair<SpartanProof, std::vector<Limbs>>;
+    std::vector<SpartanOutput> spartan_prove_batch(const ccs::Statement_Z &statement, const ccs::CCS_Z &ccs,
+                                                   const std::vector<ZVector> &zs, const std::vector<KeccakTranscript *> &transcripts,
+                                                   const std::vector<FieldConfig> &configs) const;
+    // the same from borrowed CSR arrays (ccs.t matrices of 2^s columns): nothing is copied on the host
+    std::vector<SpartanOutput> spartan_prove_batch(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs,
+                                                   const std::vector<ZVector> &zs, const std::vector<KeccakTranscript *> &transcripts,
+                                                   const std::vector<FieldConfig> &configs) const;
+    // spartan_prove_batch, then the PCS step of every proof as the loop of commit_z_mle_and_prove_evaluation: each proof
+    // draws the permutations of its RAA code from its own transcript (prover.rs:313), and zip_batch_commit has ONE code
+    // for all its members -- a PCS step with per-member codes is not built.
+    std::vector<ZincProof> prove_batch(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs, const std::vector<ZVector> &zs,
+                                       const std::vector<KeccakTranscript *> &transcripts, const std::vector<FieldConfig> &configs,
+                                       std::vector<std::vector<Limbs>> *r_y_out = nullptr) const;
     // get_z_ccs_and_z_mle (:222-239): x || 1 || w, zero-extended to ccs.m
     static IntVec get_z_ccs(const int64_t *x, size_t l, const int64_t *w, size_t w_len, size_t m);
     static IntVec get_z_ccs(const ccs::Statement_Z &statement, const ccs::Witness_Z &wit, const ccs::CCS_Z &ccs) {
@@ -507,6 +532,9 @@ class ZincProver {
     }
 
   private:
+    // commit_z_mle_and_prove_evaluation over z zero-extended to 2^s_prime (prover.rs:305-327)
+    zip::ZipProof pcs_step(const int64_t *z_ccs, size_t z_len, const ccs::CCS_Z &ccs, const std::vector<Limbs> &r_y,
+                           KeccakTranscript &transcript, const FieldConfig &config) const;
     zip::LinearCodeSpec lc_spec_;
     int device_;
 };

@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = (
     "zinc_zip_verify", "zinc_zip_evaluate", "zinc_commit_z_mle_and_prove_evaluation", "zinc_zip_proof_len",
     "zinc_zip_proof_num_roots", "zinc_zip_proof_read", "zinc_zip_proof_free", "zinc_zip_release_cached_contexts", "zinc_sumcheck_prove_product", "zinc_sumcheck_prove_ccs", "zinc_zip_data_download", "zinc_zip_data_upload", "zinc_merkle_tree_new",
     "zinc_prover_prove", "zinc_prover_prepare", "zinc_prepared_ccs_free", "zinc_verifier_verify",
-    "zinc_sumcheck_prove_products", "zinc_sumcheck_verify", "zinc_sumcheck_prove_batch",
+    "zinc_sumcheck_prove_products", "zinc_sumcheck_verify", "zinc_sumcheck_prove_batch", "zinc_prover_prove_batch",
     "zinc_zip_batch_commit", "zinc_zip_batch_open", "zinc_zip_batch_open_challenges",
     "zinc_zip_batch_verify", "zinc_zip_batch_verify_challenges",
     "zinc_get_prime", "zinc_draw_random_field", "zinc_verifier_verify_checked",
@@ -155,6 +155,8 @@ def lib():
         L.zinc_prover_prove.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_size_t, vp,
                                         C.c_size_t, vp, vp, C.c_uint32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp,
                                         C.POINTER(vp)]
+        L.zinc_prover_prove_batch.argtypes = [C.POINTER(LinearCodeSpec), vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
+                                              C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
         L.zinc_prover_prepare.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_int32, C.POINTER(vp)]
         L.zinc_prepared_ccs_free.argtypes = [vp]
         L.zinc_prepared_ccs_free.restype = None
@@ -742,6 +744,63 @@ class ZincProver:
               prepared=None):
         """Prover::prove (prover.rs:50-88) -> ZincProof {spartan_proof, zip_proof}."""
         return self._run(matrices, s, d, S, c, public_input, w_ccs, transcript, field, True, prepared)
+
+    def _run_batch(self, matrices, s, d, S, c, xs, ws, transcripts, fields, with_pcs):
+        B, t = len(xs), len(matrices)
+        assert len(ws) == B and len(transcripts) == B and len(fields) == B
+        arr, _keep = self._abi_matrices(matrices)
+        masks = np.array([sum(1 << j for j in Si) for Si in S], dtype=np.uint32)
+        cv = np.array(c, dtype=np.int64)
+        x = [np.ascontiguousarray(v, dtype=np.int64).reshape(-1) for v in xs]
+        w = [np.ascontiguousarray(v, dtype=np.int64).reshape(-1) for v in ws]
+        n = max(B, 1)
+        xp = (C.c_void_p * n)(*[v.ctypes.data for v in x])
+        wp = (C.c_void_p * n)(*[v.ctypes.data for v in w])
+        xl = (C.c_size_t * n)(*[v.size for v in x])
+        wl = (C.c_size_t * n)(*[v.size for v in w])
+        trs = (C.c_void_p * n)(*[tr._h for tr in transcripts])
+        limbs = np.array([f.limbs for f in fields], dtype=np.uint32)
+        moduli = np.zeros((n, 4), dtype=np.uint64)
+        for i, f in enumerate(fields):
+            moduli[i, :f.limbs] = np.asarray(f._m, dtype=np.uint64)[:f.limbs]
+        total = int(limbs.sum())
+        m1, m2 = np.zeros(s * (d + 2) * total, np.uint64), np.zeros(s * 3 * total, np.uint64)
+        vs, ry = np.zeros(t * total, np.uint64), np.zeros(s * total, np.uint64)
+        hs = (C.c_void_p * n)()
+        _check(lib().zinc_prover_prove_batch(_spec_ptr(self.spec), arr, t, s, d, len(S), masks.ctypes.data, cv.ctypes.data, B, xp, xl,
+                                             wp, wl, trs, moduli.ctypes.data, limbs.ctypes.data, self.device, 1 if with_pcs else 0,
+                                             m1.ctypes.data, m2.ctypes.data, vs.ctypes.data, ry.ctypes.data, hs))
+        out, at = [], 0
+        for i, fl in enumerate(int(v) for v in limbs):
+            o = dict(msgs1=m1[at * s * (d + 2):(at + fl) * s * (d + 2)].reshape(s, d + 2, fl),
+                     msgs2=m2[at * s * 3:(at + fl) * s * 3].reshape(s, 3, fl),
+                     V_s=vs[at * t:(at + fl) * t].reshape(t, fl), r_y=ry[at * s:(at + fl) * s].reshape(s, fl))
+            at += fl
+            if with_pcs:
+                h = C.c_void_p(hs[i])
+                try:
+                    roots = np.zeros((lib().zinc_zip_proof_num_roots(h), 32), np.uint8)
+                    v = np.zeros(fl, np.uint64)
+                    proof = np.zeros(lib().zinc_zip_proof_len(h), np.uint8)
+                    lib().zinc_zip_proof_read(h, roots.ctypes.data, v.ctypes.data, proof.ctypes.data)
+                finally:
+                    lib().zinc_zip_proof_free(h)
+                o["zip_proof"] = dict(z_comm=roots, v=v, pcs_proof=proof)
+            out.append(o)
+        return out
+
+    def spartan_prove_batch(self, matrices, s, d, S, c, xs, ws, transcripts, fields):
+        """spartan_prove for B proofs of ONE circuit: xs[i], ws[i], transcripts[i], fields[i] per proof -> a list of the
+        dicts spartan_prove returns; every transcript ends where spartan_prove leaves it.  From 2 proofs on (s <= 16, one
+        limb count) the circuit goes up once as integers (zip_ccs_batch), the tables of all proofs are built with a launch
+        count that does not depend on B and both sumchecks are one zip_sumcheck_prove_batch each; ZIP_HIP_BATCH=0, one
+        proof and every other shape take the loop."""
+        return self._run_batch(matrices, s, d, S, c, xs, ws, transcripts, fields, False)
+
+    def prove_batch(self, matrices, s, d, S, c, xs, ws, transcripts, fields):
+        """spartan_prove_batch, then the PCS step of every proof, one after the other (each proof draws its code from its
+        own transcript) -> a list of the dicts prove returns."""
+        return self._run_batch(matrices, s, d, S, c, xs, ws, transcripts, fields, True)
 
 
 class ZincVerifier:
