@@ -32,8 +32,15 @@ def _instances():
             ("dummy8k", _ccs.dummy_ccs_from_len(1 << 13, seed=13))]  # >= 12 variables: the split eq() tables
 
 
+def _empty_middle():
+    """t = 3, s = 3 with a middle matrix that has no entries at all (nnz == 0: nothing to upload, count or transpose)"""
+    base = _ccs.vitalik_ccs(3)
+    mats = [base.matrices[0], _ccs.CsrMatrix(8, 8, []), base.matrices[2]]
+    return _ccs.CcsInstance(8, 8, 3, 3, 2, mats, base.S, base.c, base.z)
+
+
 @pytest.mark.parametrize("q,fl", FIELDS)
-@pytest.mark.parametrize("name,inst", _instances())
+@pytest.mark.parametrize("name,inst", _instances() + [("empty_middle", _empty_middle())])
 def test_ccs_tables_equal_the_oracle(mods, q, fl, name, inst):
     """z_ccs in F_q, M_k z, eq(beta), eq(r_x), the second sumcheck's table and V_s, one by one."""
     cabi, _ = mods

@@ -68,6 +68,14 @@ struct PendingEvent {
     hipEvent_t start, stop;
 };
 
+// What FieldConfig::new makes of a modulus (make_field): the context's memo, and the field of a sumcheck / CCS handle
+struct HostField {
+    uint32_t fl = 0;
+    uint64_t modulus[8]{}, r[8]{}, r2[8]{};
+    uint64_t inv = 0;
+    uint64_t quirk_mod = 0;
+};
+
 }  // namespace
 
 // (documented with get_hint_plan below)
@@ -173,10 +181,9 @@ struct zip_ctx {
     // that another job ran cannot tell any more whether its own waits gave up too (the flag is cleared): it re-gathers.
     // Jobs enqueued after it are covered by the flag again.
     uint64_t recover_epoch = 0;
-    // make_field memo: the last zip_field seen and what FieldConfig::new made of it (a HostField, kept as bytes here
-    // because that type is defined further down)
+    // make_field memo: the last zip_field seen and what FieldConfig::new made of it
     zip_field field_cache_in{};
-    alignas(8) unsigned char field_cache_out[256] = {};
+    HostField field_cache_out;
     bool field_cache_valid = false;
     std::string last_error;
     // private plumbing context of a zip_sumcheck / zip_ccs: its blocks go to the process-wide recycle bin
@@ -278,8 +285,7 @@ struct zip_sumcheck {
     uint32_t *done_d = nullptr;          // arrival counter of the round kernel
     unsigned char *evals_pinned = nullptr;  // host-mapped slot the round message is written to (or null: evals_d + a copy)
     uint32_t max_blocks = 0;
-    uint64_t modulus[8] = {};
-    uint64_t mont_r[8] = {}, mont_r2[8] = {}, mont_inv = 0;  // Montgomery constants, computed once (512 modular doublings)
+    HostField field;  // modulus and Montgomery constants, computed once (512 modular doublings)
     uint32_t n_terms = 0, term_mask[8] = {};  // zip_sumcheck_comb, or n_terms == 0 for the plain product
     uint64_t coeff[8][8] = {};
     // zip_sumcheck_init_products: comb_fn = sum_t coeff[t] * prod_{j in term_mask[t]} vals[j], no trailing factor
@@ -292,7 +298,7 @@ struct zip_sumcheck {
 struct zip_ccs {
     zip_ctx *ctx = nullptr;  // private plumbing context (stream, pool, error text)
     uint32_t t = 0, s = 0, m = 0, fl = 0;
-    uint64_t modulus[8] = {};
+    HostField field;
     struct Mat {
         uint32_t n_rows = 0, nnz = 0;
         uint32_t *row_ptr = nullptr, *col_idx = nullptr, *col_ptr = nullptr, *row_idx = nullptr;
@@ -775,14 +781,6 @@ int32_t wait_ready(zip_commitment *c, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------------ field setup
-struct HostField {
-    uint32_t fl = 0;
-    uint64_t modulus[8]{}, r[8]{}, r2[8]{};
-    uint64_t inv = 0;
-    uint64_t quirk_mod = 0;
-};
-static_assert(sizeof(HostField) <= 256, "zip_ctx::field_cache_out holds a HostField");
-
 int cmp_limbs(const uint64_t *a, const uint64_t *b, uint32_t n) {
     for (uint32_t i = n; i-- > 0;)
         if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
@@ -811,13 +809,13 @@ int32_t make_field(zip_ctx *ctx, const zip_field *zf, HostField *f) {
     if (!zf) return fail(ctx, ZIP_ERR_NULL, "field is NULL");
     if (ctx && ctx->field_cache_valid && ctx->field_cache_in.limbs == zf->limbs &&
         !memcmp(ctx->field_cache_in.modulus, zf->modulus, 8 * (size_t)zf->limbs)) {
-        memcpy(f, ctx->field_cache_out, sizeof(HostField));
+        *f = ctx->field_cache_out;
         return ZIP_OK;
     }
     int32_t rc = make_field_uncached(ctx, zf, f);
     if (!rc && ctx) {
         ctx->field_cache_in = *zf;
-        memcpy(ctx->field_cache_out, f, sizeof(HostField));
+        ctx->field_cache_out = *f;
         ctx->field_cache_valid = true;
     }
     return rc;
@@ -1993,35 +1991,41 @@ uint32_t sumcheck_final_grid(const zip_sumcheck *s, uint32_t blocks, uint64_t ha
     return blocks;
 }
 
-// degree 3: four lanes per hypercube point (sumcheck_round_quad_kernel, <= 128 VGPRs); ZIP_HIP_SUMCHECK_QUAD=0: the
-// one-thread-per-point kernel for every degree
-template <int FL, int K, int DEG>
-int32_t launch_sumcheck_quad(zip_sumcheck *s, SumcheckRoundArgs<FL> a, const FieldDev<FL> &fd) {
+// Workgroups of a round kernel that one CU holds at a time, asked once per (kernel, device).  0: the query failed --
+// the caller caps nothing, and the next call asks again.
+int sumcheck_round_occupancy(zip_ctx *ctx, const void *kern, size_t lds) {
+    static std::mutex mu;
+    static std::map<std::pair<const void *, int>, int> occ;
+    std::lock_guard<std::mutex> g(mu);
+    int &per_cu = occ[std::make_pair(kern, ctx->device)];
+    if (per_cu == 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess) per_cu = 0;
+    return per_cu;
+}
+
+// One round: `kern` over a.half hypercube points, `points_per_wg` of them per workgroup and pass, timed as `name`.
+template <int FL, class Args>
+int32_t launch_sumcheck_kernel(zip_sumcheck *s, void (*kern)(Args, FieldDev<FL>), const char *name, size_t lds,
+                               uint32_t points_per_wg, Args a, const FieldDev<FL> &fd) {
     zip_ctx *ctx = s->ctx;
-    const size_t lds = (size_t)256 * FL * 8;
-    const uint64_t want = (a.half * 4 + 255) / 256;
+    const uint64_t want = (a.half + points_per_wg - 1) / points_per_wg;
     uint32_t blocks = (uint32_t)std::min<uint64_t>(want ? want : 1, s->max_blocks);
-    if (blocks > ctx->num_cus) {  // (as below: exactly the workgroups that are resident together)
-        static std::mutex mu;
-        static std::map<std::pair<const void *, int>, int> occ;
-        const void *kern = reinterpret_cast<const void *>(sumcheck_round_quad_kernel<FL, K, DEG>);
-        std::lock_guard<std::mutex> g(mu);
-        int &per_cu = occ[std::make_pair(kern, ctx->device)];
-        if (per_cu == 0 &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sumcheck_round_quad_kernel<FL, K, DEG>, 256, lds) != hipSuccess)
-            per_cu = 0;
+    // a big round runs as exactly the workgroups that are resident together (grid-stride loop inside): a grid of
+    // 8 per CU with 3 resident left a third wave of workgroups two thirds full
+    if (blocks > ctx->num_cus) {
+        const int per_cu = sumcheck_round_occupancy(ctx, reinterpret_cast<const void *>(kern), lds);
         if (per_cu > 0) blocks = std::min<uint32_t>(blocks, ctx->num_cus * (uint32_t)per_cu);
     }
-    blocks = sumcheck_final_grid(s, blocks, a.half, 64);
+    blocks = sumcheck_final_grid(s, blocks, a.half, points_per_wg);
+    // small rounds: one launch, the last workgroup folds the partials; otherwise sumcheck_reduce_kernel does
     a.done = blocks <= 64 ? s->done_d : nullptr;
     {
-        LaunchTimer t(ctx, "sumcheck_round_kernel");
-        hipLaunchKernelGGL((sumcheck_round_quad_kernel<FL, K, DEG>), dim3(blocks), dim3(256), lds, ctx->stream, a, fd);
+        LaunchTimer t(ctx, name);
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, ctx->stream, a, fd);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (!a.done) {
         LaunchTimer t(ctx, "sumcheck_reduce_kernel");
-        hipLaunchKernelGGL(sumcheck_reduce_kernel<FL>, dim3(1), dim3(256), 0, ctx->stream, a.partials, blocks, (uint32_t)(DEG + 1), a.evals_out, fd,
+        hipLaunchKernelGGL(sumcheck_reduce_kernel<FL>, dim3(1), dim3(256), 0, ctx->stream, a.partials, blocks, a.degree + 1, a.evals_out, fd,
                            a.host_flag, a.seq);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -2029,8 +2033,7 @@ int32_t launch_sumcheck_quad(zip_sumcheck *s, SumcheckRoundArgs<FL> a, const Fie
 }
 
 template <int FL, int K, int DEG>
-int32_t launch_sumcheck_round(zip_sumcheck *s, SumcheckRoundArgs<FL> a, uint32_t blocks, const FieldDev<FL> &fd) {
-    zip_ctx *ctx = s->ctx;
+int32_t launch_sumcheck_round(zip_sumcheck *s, const SumcheckRoundArgs<FL> &a, const FieldDev<FL> &fd) {
     if constexpr (DEG == 3 || DEG == 2) {
         // Degree 3, the FOLDING rounds (all but the first): there the quad kernel is as fast in the big rounds and up to
         // 1.4x as fast in the small ones (four times the threads for the same number of points, five waves per SIMD
@@ -2040,88 +2043,45 @@ int32_t launch_sumcheck_round(zip_sumcheck *s, SumcheckRoundArgs<FL> a, uint32_t
         // 2^16 points down (the last rounds: 32 against 49 us).  ZIP_HIP_SUMCHECK_QUAD=0 / 2: never / every round.
         const long mode = env_long("ZIP_HIP_SUMCHECK_QUAD", 1, 0, 2);  // (per call: the tests flip it)
         const bool pays = a.fold && (DEG == 3 || a.half <= 65536u);
-        if (mode == 2 || (mode == 1 && pays)) return launch_sumcheck_quad<FL, K, DEG>(s, a, fd);
+        // four lanes per hypercube point (sumcheck_round_quad_kernel, <= 128 VGPRs), 64 points per workgroup
+        if (mode == 2 || (mode == 1 && pays))
+            return launch_sumcheck_kernel<FL>(s, sumcheck_round_quad_kernel<FL, K, DEG>, "sumcheck_round_kernel", (size_t)256 * FL * 8, 64, a, fd);
     }
     // (extra dynamic LDS to lower the occupancy was an experiment, since removed: EXPERIMENTS.md)
-    const size_t lds = (size_t)256 * (DEG + 1) * FL * 8;
-    // a big round runs as exactly the workgroups that are resident together (grid-stride loop inside): a grid of
-    // 8 per CU with 3 resident left a third wave of workgroups two thirds full
-    if (blocks > ctx->num_cus) {
-        static std::mutex mu;
-        static std::map<std::pair<const void *, int>, int> occ;
-        const void *kern = reinterpret_cast<const void *>(sumcheck_round_kernel<FL, K, DEG>);
-        std::lock_guard<std::mutex> g(mu);
-        int &per_cu = occ[std::make_pair(kern, ctx->device)];
-        if (per_cu == 0 &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sumcheck_round_kernel<FL, K, DEG>, 256, lds) != hipSuccess)
-            per_cu = 0;
-        if (per_cu > 0) blocks = std::min<uint32_t>(blocks, ctx->num_cus * (uint32_t)per_cu);
-    }
-    blocks = sumcheck_final_grid(s, blocks, a.half, 256);
-    a.done = blocks <= 64 ? s->done_d : nullptr;  // small rounds: one launch, the last workgroup folds the partials
-    {
-        LaunchTimer t(ctx, "sumcheck_round_kernel");
-        hipLaunchKernelGGL((sumcheck_round_kernel<FL, K, DEG>), dim3(blocks), dim3(256), lds, ctx->stream, a, fd);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    if (!a.done) {
-        LaunchTimer t(ctx, "sumcheck_reduce_kernel");
-        hipLaunchKernelGGL(sumcheck_reduce_kernel<FL>, dim3(1), dim3(256), 0, ctx->stream, a.partials, blocks, (uint32_t)(DEG + 1),
-                           a.evals_out, fd, a.host_flag, a.seq);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return ZIP_OK;
+    return launch_sumcheck_kernel<FL>(s, sumcheck_round_kernel<FL, K, DEG>, "sumcheck_round_kernel", (size_t)256 * (DEG + 1) * FL * 8, 256, a, fd);
 }
 
 // 5..8 MLEs: eight lanes per hypercube point (sumcheck_round_wide_kernel), every degree and every round; 32 points per
-// workgroup.  The grid is capped like the others (exactly the workgroups that are resident together, grid-stride loop
-// inside) and a small grid folds its partials itself.  ZIP_HIP_SUMCHECK_QUAD does not apply here.
+// workgroup.  ZIP_HIP_SUMCHECK_QUAD does not apply here.
 template <int FL, int K>
-int32_t launch_sumcheck_wide(zip_sumcheck *s, SumcheckRoundArgs<FL> a, const FieldDev<FL> &fd) {
-    zip_ctx *ctx = s->ctx;
-    const size_t lds = (size_t)256 * FL * 8;
-    const uint64_t want = (a.half * kSumcheckWideLanes + 255) / 256;
-    uint32_t blocks = (uint32_t)std::min<uint64_t>(want ? want : 1, s->max_blocks);
-    if (blocks > ctx->num_cus) {
-        static std::mutex mu;
-        static std::map<std::pair<const void *, int>, int> occ;
-        const void *kern = reinterpret_cast<const void *>(sumcheck_round_wide_kernel<FL, K>);
-        std::lock_guard<std::mutex> g(mu);
-        int &per_cu = occ[std::make_pair(kern, ctx->device)];
-        if (per_cu == 0 &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sumcheck_round_wide_kernel<FL, K>, 256, lds) != hipSuccess)
-            per_cu = 0;
-        if (per_cu > 0) blocks = std::min<uint32_t>(blocks, ctx->num_cus * (uint32_t)per_cu);
-    }
-    blocks = sumcheck_final_grid(s, blocks, a.half, 256 / kSumcheckWideLanes);
-    a.done = blocks <= 64 ? s->done_d : nullptr;
-    {
-        LaunchTimer t(ctx, "sumcheck_round_wide_kernel");
-        hipLaunchKernelGGL((sumcheck_round_wide_kernel<FL, K>), dim3(blocks), dim3(256), lds, ctx->stream, a, fd);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    if (!a.done) {
-        LaunchTimer t(ctx, "sumcheck_reduce_kernel");
-        hipLaunchKernelGGL(sumcheck_reduce_kernel<FL>, dim3(1), dim3(256), 0, ctx->stream, a.partials, blocks, a.degree + 1, a.evals_out, fd,
-                           a.host_flag, a.seq);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return ZIP_OK;
+int32_t launch_sumcheck_wide(zip_sumcheck *s, const SumcheckRoundArgs<FL> &a, const FieldDev<FL> &fd) {
+    return launch_sumcheck_kernel<FL>(s, sumcheck_round_wide_kernel<FL, K>, "sumcheck_round_wide_kernel", (size_t)256 * FL * 8,
+                                      256 / kSumcheckWideLanes, a, fd);
 }
 
 template <int FL, int K>
-int32_t sumcheck_round_k(zip_sumcheck *s, const SumcheckRoundArgs<FL> &a, uint32_t blocks, const FieldDev<FL> &fd) {
+int32_t sumcheck_round_k(zip_sumcheck *s, const SumcheckRoundArgs<FL> &a, const FieldDev<FL> &fd) {
     switch (s->degree) {
-        case 1: return launch_sumcheck_round<FL, K, 1>(s, a, blocks, fd);
-        case 2: return launch_sumcheck_round<FL, K, 2>(s, a, blocks, fd);
-        case 3: return launch_sumcheck_round<FL, K, 3>(s, a, blocks, fd);
-        default: return launch_sumcheck_round<FL, K, 4>(s, a, blocks, fd);
+        case 1: return launch_sumcheck_round<FL, K, 1>(s, a, fd);
+        case 2: return launch_sumcheck_round<FL, K, 2>(s, a, fd);
+        case 3: return launch_sumcheck_round<FL, K, 3>(s, a, fd);
+        default: return launch_sumcheck_round<FL, K, 4>(s, a, fd);
     }
 }
 
-template <int FL>
-int32_t sumcheck_round_fl(zip_sumcheck *s, const uint64_t *r_prev, const HostField &hf) {
-    SumcheckRoundArgs<FL> a{};
+// 0 = general, 1 = one (R), 2 = minus one (q - R): SumcheckRoundArgs::coeff_kind
+uint32_t coeff_kind(const uint64_t *coeff, const HostField &hf) {
+    uint64_t minus_one[8] = {0};
+    memcpy(minus_one, hf.modulus, 8 * (size_t)hf.fl);
+    sub_limbs(minus_one, hf.r, hf.fl);  // q - R
+    return !cmp_limbs(coeff, hf.r, hf.fl) ? 1u : !cmp_limbs(coeff, minus_one, hf.fl) ? 2u : 0u;
+}
+
+// What SumcheckRoundArgs and SumcheckProductsArgs share, for round s->round + 1.  (a.done -- the last workgroup folds the
+// partials, or sumcheck_reduce_kernel does -- is the launcher's: it knows the final grid.)
+template <int FL, class Args>
+void sumcheck_fill_round(const zip_sumcheck *s, const uint64_t *r_prev, Args &a) {
+    const HostField &hf = s->field;
     const uint32_t round = s->round + 1;  // 1-based
     a.degree = s->degree;
     a.half = (uint64_t)1 << (s->num_vars - round);
@@ -2130,19 +2090,11 @@ int32_t sumcheck_round_fl(zip_sumcheck *s, const uint64_t *r_prev, const HostFie
     a.evals_out = s->evals_pinned ? reinterpret_cast<uint64_t *>(s->evals_pinned) : s->evals_d;
     a.host_flag = s->evals_pinned ? reinterpret_cast<uint32_t *>(s->evals_pinned + 192) : nullptr;
     a.seq = round;
-    a.n_terms = s->n_terms;
-    uint64_t minus_one[8] = {0};
-    for (int i = 0; i < FL; i++) {
-        a.one[i] = hf.r[i];
-        minus_one[i] = hf.modulus[i];
-    }
-    sub_limbs(minus_one, hf.r, FL);  // q - R
     for (uint32_t t = 0; t < s->n_terms; t++) {
-        a.term_mask[t] = s->term_mask[t];
         for (int i = 0; i < FL; i++) a.coeff[t][i] = s->coeff[t][i];
-        a.coeff_kind[t] = !cmp_limbs(s->coeff[t], hf.r, FL) ? 1u : !cmp_limbs(s->coeff[t], minus_one, FL) ? 2u : 0u;
+        a.coeff_kind[t] = coeff_kind(s->coeff[t], hf);
     }
-    for (uint32_t k = 0; k < s->n_mles; k++) {
+    for (uint32_t k = 0; k < s->n_mles; k++) {  // (a products handle: an unused MLE has no tables at all)
         // round 1 reads the input; round 2 folds input -> buf[0]; round j >= 3 folds buf[j & 1] ... alternating
         if (round == 1) a.src[k] = s->input[k];
         else if (round == 2) { a.src[k] = s->input[k]; a.dst[k] = s->buf[0][k]; }
@@ -2150,15 +2102,21 @@ int32_t sumcheck_round_fl(zip_sumcheck *s, const uint64_t *r_prev, const HostFie
     }
     if (a.fold)
         for (int i = 0; i < FL; i++) a.r[i] = r_prev[i];
-    uint64_t want = (a.half + 255) / 256;
-    // (a.done -- the last workgroup folds the partials, or sumcheck_reduce_kernel does -- is the launcher's: it knows the final grid)
-    uint32_t blocks = (uint32_t)std::min<uint64_t>(want ? want : 1, s->max_blocks);
-    const FieldDev<FL> fd = to_dev<FL>(hf);
+}
+
+template <int FL>
+int32_t sumcheck_round_fl(zip_sumcheck *s, const uint64_t *r_prev) {
+    SumcheckRoundArgs<FL> a{};
+    sumcheck_fill_round<FL>(s, r_prev, a);
+    a.n_terms = s->n_terms;
+    for (uint32_t t = 0; t < s->n_terms; t++) a.term_mask[t] = s->term_mask[t];
+    for (int i = 0; i < FL; i++) a.one[i] = s->field.r[i];
+    const FieldDev<FL> fd = to_dev<FL>(s->field);
     switch (s->n_mles) {
-        case 1: return sumcheck_round_k<FL, 1>(s, a, blocks, fd);
-        case 2: return sumcheck_round_k<FL, 2>(s, a, blocks, fd);
-        case 3: return sumcheck_round_k<FL, 3>(s, a, blocks, fd);
-        case 4: return sumcheck_round_k<FL, 4>(s, a, blocks, fd);
+        case 1: return sumcheck_round_k<FL, 1>(s, a, fd);
+        case 2: return sumcheck_round_k<FL, 2>(s, a, fd);
+        case 3: return sumcheck_round_k<FL, 3>(s, a, fd);
+        case 4: return sumcheck_round_k<FL, 4>(s, a, fd);
         case 5: return launch_sumcheck_wide<FL, 5>(s, a, fd);
         case 6: return launch_sumcheck_wide<FL, 6>(s, a, fd);
         case 7: return launch_sumcheck_wide<FL, 7>(s, a, fd);
@@ -2167,67 +2125,22 @@ int32_t sumcheck_round_fl(zip_sumcheck *s, const uint64_t *r_prev, const HostFie
 }
 
 // A zip_sumcheck_init_products handle: one sumcheck_round_products_kernel per round over all tables, eight lanes per
-// hypercube point, 32 points per workgroup.  Grid and reduction as launch_sumcheck_wide.
+// hypercube point, 32 points per workgroup.
 template <int FL>
-int32_t sumcheck_round_products_fl(zip_sumcheck *s, const uint64_t *r_prev, const HostField &hf) {
-    zip_ctx *ctx = s->ctx;
+int32_t sumcheck_round_products_fl(zip_sumcheck *s, const uint64_t *r_prev) {
     SumcheckProductsArgs<FL> a{};
-    const uint32_t round = s->round + 1;  // 1-based
-    a.degree = s->degree;
-    a.half = (uint64_t)1 << (s->num_vars - round);
-    a.fold = round > 1;
-    a.partials = s->partials;
-    a.evals_out = s->evals_pinned ? reinterpret_cast<uint64_t *>(s->evals_pinned) : s->evals_d;
-    a.host_flag = s->evals_pinned ? reinterpret_cast<uint32_t *>(s->evals_pinned + 192) : nullptr;
-    a.seq = round;
+    sumcheck_fill_round<FL>(s, r_prev, a);
     a.n_products = s->n_terms;
-    uint64_t minus_one[8] = {0};
-    for (int i = 0; i < FL; i++) minus_one[i] = hf.modulus[i];
-    sub_limbs(minus_one, hf.r, FL);  // q - R
     for (uint32_t t = 0; t < s->n_terms; t++) {
         a.n_factors[t] = s->n_factors[t];
         a.factors[t] = s->factors[t];
         a.own[t] = s->own[t];
-        for (int i = 0; i < FL; i++) a.coeff[t][i] = s->coeff[t][i];
         // (a single factor has no running term to negate or to start from: its coefficient is a multiplicand)
-        a.coeff_kind[t] = s->n_factors[t] < 2 ? 0u : !cmp_limbs(s->coeff[t], hf.r, FL) ? 1u : !cmp_limbs(s->coeff[t], minus_one, FL) ? 2u : 0u;
+        if (s->n_factors[t] < 2) a.coeff_kind[t] = 0u;
     }
-    for (uint32_t k = 0; k < s->n_mles; k++) {  // the ping-pong of sumcheck_round_fl; an unused MLE has no tables at all
-        if (round == 1) a.src[k] = s->input[k];
-        else if (round == 2) { a.src[k] = s->input[k]; a.dst[k] = s->buf[0][k]; }
-        else { a.src[k] = s->buf[(round - 3) & 1][k]; a.dst[k] = s->buf[(round - 2) & 1][k]; }
-    }
-    if (a.fold)
-        for (int i = 0; i < FL; i++) a.r[i] = r_prev[i];
-    const FieldDev<FL> fd = to_dev<FL>(hf);
-    const size_t lds = (size_t)256 * FL * 8;
-    const uint64_t want = (a.half * kSumcheckWideLanes + 255) / 256;
-    uint32_t blocks = (uint32_t)std::min<uint64_t>(want ? want : 1, s->max_blocks);
-    if (blocks > ctx->num_cus) {  // exactly the workgroups that are resident together (grid-stride loop inside)
-        static std::mutex mu;
-        static std::map<std::pair<const void *, int>, int> occ;
-        const void *kern = reinterpret_cast<const void *>(sumcheck_round_products_kernel<FL>);
-        std::lock_guard<std::mutex> g(mu);
-        int &per_cu = occ[std::make_pair(kern, ctx->device)];
-        if (per_cu == 0 &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sumcheck_round_products_kernel<FL>, 256, lds) != hipSuccess)
-            per_cu = 0;
-        if (per_cu > 0) blocks = std::min<uint32_t>(blocks, ctx->num_cus * (uint32_t)per_cu);
-    }
-    blocks = sumcheck_final_grid(s, blocks, a.half, 256 / kSumcheckWideLanes);
-    a.done = blocks <= 64 ? s->done_d : nullptr;  // small rounds: one launch, the last workgroup folds the partials
-    {
-        LaunchTimer t(ctx, "sumcheck_round_products_kernel");
-        hipLaunchKernelGGL(sumcheck_round_products_kernel<FL>, dim3(blocks), dim3(256), lds, ctx->stream, a, fd);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    if (!a.done) {
-        LaunchTimer t(ctx, "sumcheck_reduce_kernel");
-        hipLaunchKernelGGL(sumcheck_reduce_kernel<FL>, dim3(1), dim3(256), 0, ctx->stream, a.partials, blocks, a.degree + 1, a.evals_out, fd,
-                           a.host_flag, a.seq);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    return ZIP_OK;
+    auto kern = sumcheck_round_products_kernel<FL>;
+    return launch_sumcheck_kernel<FL>(s, kern, "sumcheck_round_products_kernel", (size_t)256 * FL * 8, 256 / kSumcheckWideLanes, a,
+                                      to_dev<FL>(s->field));
 }
 
 // ---- zip_sumcheck_prove: the transcript of MLSumcheck::prove_as_subprotocol inside the library ---------------------------
@@ -2246,9 +2159,9 @@ uint32_t tail_lds_bound(uint32_t n_mles, uint32_t fl) {
 }
 
 template <int FL>
-int32_t sumcheck_prove_fl(zip_sumcheck *s, zip_keccak_state *transcript, uint64_t *msgs_out, uint64_t *randomness_out,
-                          const HostField &hf) {
+int32_t sumcheck_prove_fl(zip_sumcheck *s, zip_keccak_state *transcript, uint64_t *msgs_out, uint64_t *randomness_out) {
     zip_ctx *ctx = s->ctx;
+    const HostField &hf = s->field;
     const uint32_t nv = s->num_vars, ne = s->degree + 1;
     // (the sponge on this thread: TrSponge, keccak_dev.cuh -- the serial form of what the tail kernel does)
     TrSponge sp;
@@ -2669,13 +2582,6 @@ int32_t ccs_eval_matrices_fl(zip_ccs *c, uint64_t *out_d, const HostField &hf) {
         HIP_TRY(ctx, hipGetLastError());
     }
     return ZIP_OK;
-}
-
-int32_t ccs_field(zip_ccs *c, HostField *hf) {
-    zip_field zf{};
-    zf.limbs = c->fl;
-    memcpy(zf.modulus, c->modulus, sizeof zf.modulus);
-    return make_field(c->ctx, &zf, hf);
 }
 
 // ---- zip_ccs_batch: the same tables for n proofs of one circuit, launches per call independent of n ----------------------
@@ -5046,6 +4952,31 @@ int32_t zip_open_stream(zip_commitment *c, const int64_t *evals, zip_mem_kind ev
     return check_timeout(ctx);
 }
 
+namespace {
+// The private plumbing context of a sumcheck or CCS handle, or of one call: `device` made current, its CU count, a
+// non-blocking stream; recycle: the blocks come from the device's recycle bin and go back there.  An error leaves no
+// context behind.
+int32_t private_ctx_create(int32_t device, bool recycle, zip_ctx **out) {
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ZIP_ERR_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
+    zip_ctx *ctx = new (std::nothrow) zip_ctx();
+    if (!ctx) return ZIP_ERR_ALLOC;
+    ctx->device = device;
+    ctx->recycle = recycle;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
+        ctx->num_cus = (uint32_t)cus;
+    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
+        delete ctx;  // (nothing but the object exists yet)
+        return ZIP_ERR_HIP;
+    }
+    *out = ctx;
+    return ZIP_OK;
+}
+}  // namespace
+
 static int32_t sumcheck_create(int32_t device, const uint64_t *const *mles, zip_mem_kind kind, uint32_t n_mles, uint32_t num_vars,
                                uint32_t degree, const zip_sumcheck_comb *comb, bool products, const zip_field *field,
                                zip_sumcheck **out);
@@ -5087,28 +5018,19 @@ int32_t zip_sumcheck_init_products(int32_t device, const uint64_t *const *mles, 
 static int32_t sumcheck_create(int32_t device, const uint64_t *const *mles, zip_mem_kind kind, uint32_t n_mles, uint32_t num_vars,
                                uint32_t degree, const zip_sumcheck_comb *comb, bool products, const zip_field *field,
                                zip_sumcheck **out) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ZIP_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
-    zip_ctx *ctx = new (std::nothrow) zip_ctx();
+    zip_ctx *ctx = nullptr;
+    int32_t rc = private_ctx_create(device, true, &ctx);
+    if (rc) return rc;
     zip_sumcheck *s = new (std::nothrow) zip_sumcheck();
-    if (!ctx || !s) { delete ctx; delete s; return ZIP_ERR_ALLOC; }
-    ctx->device = device;
-    ctx->recycle = true;
+    if (!s) { zip_ctx_destroy(ctx); return ZIP_ERR_ALLOC; }
     s->ctx = ctx;
-    int32_t rc = ZIP_OK;
     do {
-        if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
-        HostField hf;
+        HostField &hf = s->field;
         if ((rc = make_field(ctx, field, &hf))) break;
         s->n_mles = n_mles;
         s->num_vars = num_vars;
         s->degree = degree;
         s->fl = hf.fl;
-        memcpy(s->modulus, hf.modulus, sizeof s->modulus);
-        memcpy(s->mont_r, hf.r, sizeof s->mont_r);
-        memcpy(s->mont_r2, hf.r2, sizeof s->mont_r2);
-        s->mont_inv = hf.inv;
         if (comb) {
             s->n_terms = comb->n_terms;
             for (uint32_t t = 0; t < comb->n_terms; t++) {
@@ -5153,9 +5075,7 @@ static int32_t sumcheck_create(int32_t device, const uint64_t *const *mles, zip_
         }
         if (rc) break;
         s->owned = kind == ZIP_MEM_HOST;
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-        s->max_blocks = (uint32_t)cus * 8;
+        s->max_blocks = ctx->num_cus * 8;
         if ((rc = pool_alloc(ctx, (size_t)s->max_blocks * (degree + 1) * elem, (void **)&s->partials))) break;
         if ((rc = pool_alloc(ctx, (size_t)(degree + 1) * elem, (void **)&s->evals_d))) break;
         if ((rc = pool_alloc(ctx, 16, (void **)&s->done_d))) break;
@@ -5182,15 +5102,9 @@ int32_t zip_sumcheck_round_begin(zip_sumcheck *s, const uint64_t *r_prev) {
     if (s->round >= s->num_vars) return fail(ctx, ZIP_ERR_INVALID_PARAM, "Prover is not active");  // prover.rs:91-93
     if (s->round == 0 && r_prev) return fail(ctx, ZIP_ERR_INVALID_PARAM, "first round should be prover first.");
     if (s->round > 0 && !r_prev) return fail(ctx, ZIP_ERR_INVALID_PARAM, "verifier message is empty");
-    HostField hf;
-    hf.fl = s->fl;
-    memcpy(hf.modulus, s->modulus, sizeof hf.modulus);
-    memcpy(hf.r, s->mont_r, sizeof hf.r);
-    memcpy(hf.r2, s->mont_r2, sizeof hf.r2);
-    hf.inv = s->mont_inv;
     if (int32_t rc = with_fl(s->fl, [&](auto FL) {
-            return s->products ? sumcheck_round_products_fl<decltype(FL)::value>(s, r_prev, hf)
-                               : sumcheck_round_fl<decltype(FL)::value>(s, r_prev, hf);
+            return s->products ? sumcheck_round_products_fl<decltype(FL)::value>(s, r_prev)
+                               : sumcheck_round_fl<decltype(FL)::value>(s, r_prev);
         }))
         return rc;
     g_sumcheck_round_launches++;
@@ -5241,14 +5155,8 @@ int32_t zip_sumcheck_prove(zip_sumcheck *s, zip_keccak_state *transcript, uint64
     if (transcript->buflen >= kKeccakRate)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "transcript buflen %u is not below the Keccak-256 rate (136)", transcript->buflen);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HostField hf;
-    hf.fl = s->fl;
-    memcpy(hf.modulus, s->modulus, sizeof hf.modulus);
-    memcpy(hf.r, s->mont_r, sizeof hf.r);
-    memcpy(hf.r2, s->mont_r2, sizeof hf.r2);
-    hf.inv = s->mont_inv;
     s->proved = true;  // whatever happens from here on, the handle does not start over
-    const int32_t rc = with_fl(s->fl, [&](auto FL) { return sumcheck_prove_fl<decltype(FL)::value>(s, transcript, msgs_out, randomness_out, hf); });
+    const int32_t rc = with_fl(s->fl, [&](auto FL) { return sumcheck_prove_fl<decltype(FL)::value>(s, transcript, msgs_out, randomness_out); });
     if (rc) s->round = s->num_vars;
     return rc;
 }
@@ -5303,23 +5211,13 @@ int32_t zip_sumcheck_prove_batch(int32_t device, const zip_sumcheck_instance *in
         if (int32_t rc = make_field_uncached(nullptr, inst[i].field, &fields[i])) return rc;
     }
     CurrentDeviceGuard restore;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ZIP_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
-    zip_ctx *ctx = new (std::nothrow) zip_ctx();  // the call's plumbing, as a zip_sumcheck handle has one
-    if (!ctx) return ZIP_ERR_ALLOC;
-    ctx->device = device;
-    ctx->recycle = true;
-    int32_t rc = ZIP_OK;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
-        ctx->stream = nullptr;
-        rc = ZIP_ERR_HIP;
-    }
-    if (!rc)
-        rc = with_fl(fl, [&](auto FL) {
-            return sumcheck_prove_batch_fl<decltype(FL)::value>(ctx, inst, n_instances, tables_kind, n_mles, num_vars, degree, fields,
-                                                                msgs_out, randomness_out);
-        });
+    zip_ctx *ctx = nullptr;  // the call's plumbing, as a zip_sumcheck handle has one
+    int32_t rc = private_ctx_create(device, true, &ctx);
+    if (rc) return rc;
+    rc = with_fl(fl, [&](auto FL) {
+        return sumcheck_prove_batch_fl<decltype(FL)::value>(ctx, inst, n_instances, tables_kind, n_mles, num_vars, degree, fields,
+                                                            msgs_out, randomness_out);
+    });
     zip_ctx_destroy(ctx);  // waits for the stream; every block goes back to the device's recycle bin
     return rc;
 }
@@ -5386,8 +5284,11 @@ void zip_sumcheck_free(zip_sumcheck *s) {
 
 // ---------------------------------------------------------------------------- zip_ccs
 namespace {
-// the shape rules of the t matrices of a CCS with m = 2^s columns (zip_ccs_create, zip_ccs_batch_create)
-int32_t ccs_check_matrices(const zip_sparse_matrix *mats, uint32_t t, uint32_t m) {
+// the ranges of t and s, then the shape rules of the t matrices of a CCS with m = 2^s columns (zip_ccs_create,
+// zip_ccs_batch_create)
+int32_t ccs_check_matrices(const zip_sparse_matrix *mats, uint32_t t, uint32_t s) {
+    if (t < 1 || t > (uint32_t)kCcsMaxMatrices || s < 1 || s > 28) return ZIP_ERR_INVALID_PARAM;
+    const uint32_t m = 1u << s;
     for (uint32_t k = 0; k < t; k++) {
         const zip_sparse_matrix &M = mats[k];
         if (!M.row_ptr || (M.row_ptr[M.n_rows] && (!M.col_idx || !M.values))) return ZIP_ERR_NULL;
@@ -5401,75 +5302,79 @@ int32_t ccs_check_matrices(const zip_sparse_matrix *mats, uint32_t t, uint32_t m
     }
     return ZIP_OK;
 }
+
+// One matrix of m columns into the pool, up to its transposition: the arrays of D (values of `val_bytes` each, not
+// filled here), the CSR indices uploaded, col_ptr counted and scanned, and a copy of it in *cursor (the per-column write
+// positions of csc_fill_kernel).  The caller uploads D.vals, launches csc_fill_kernel, and releases *cursor and *sums
+// once the stream has passed them.
+int32_t ccs_upload_matrix(zip_ctx *ctx, const zip_sparse_matrix &M, uint32_t m, size_t val_bytes, zip_ccs::Mat &D, uint32_t **cursor,
+                          uint32_t **sums) {
+    const uint32_t nnz = M.row_ptr[M.n_rows], n_cnt = m + 1, tiles = (n_cnt + kScanTile - 1) / kScanTile;
+    D.n_rows = M.n_rows;
+    D.nnz = nnz;
+    int32_t rc;
+    if ((rc = pool_alloc(ctx, (size_t)(M.n_rows + 1) * 4, (void **)&D.row_ptr))) return rc;
+    if ((rc = pool_alloc(ctx, (size_t)nnz * 4, (void **)&D.col_idx))) return rc;
+    if ((rc = pool_alloc(ctx, (size_t)n_cnt * 4, (void **)&D.col_ptr))) return rc;
+    if ((rc = pool_alloc(ctx, (size_t)nnz * 4, (void **)&D.row_idx))) return rc;
+    if ((rc = pool_alloc(ctx, (size_t)nnz * val_bytes, (void **)&D.vals))) return rc;
+    if ((rc = pool_alloc(ctx, (size_t)nnz * val_bytes, (void **)&D.vals_t))) return rc;
+    if ((rc = pool_alloc(ctx, (size_t)n_cnt * 4, (void **)cursor))) return rc;
+    if ((rc = pool_alloc(ctx, (size_t)tiles * 4, (void **)sums))) return rc;
+    if ((rc = copy_h2d_bounced(ctx, D.row_ptr, M.row_ptr, (size_t)(M.n_rows + 1) * 4, ctx->stream))) return rc;
+    if (hipMemsetAsync(D.col_ptr, 0, (size_t)n_cnt * 4, ctx->stream) != hipSuccess) return ZIP_ERR_HIP;
+    if (nnz) {
+        if ((rc = copy_h2d_bounced(ctx, D.col_idx, M.col_idx, (size_t)nnz * 4, ctx->stream))) return rc;
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)nnz + 255) / 256, 65535);
+        hipLaunchKernelGGL(csc_count_kernel, dim3(blocks), dim3(256), 0, ctx->stream, D.col_idx, nnz, D.col_ptr);
+    }
+    // col_ptr = inclusive scan of the counters (counts sit at [col + 1], so col_ptr[0] = 0)
+    hipLaunchKernelGGL(scan_tiles_kernel, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, D.col_ptr, n_cnt, *sums,
+                       static_cast<const uint32_t *>(nullptr));
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanBlock), 0, ctx->stream, *sums, tiles);
+    hipLaunchKernelGGL(scan_tiles_kernel, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, D.col_ptr, n_cnt,
+                       static_cast<uint32_t *>(nullptr), static_cast<const uint32_t *>(*sums));
+    if (hipMemcpyAsync(*cursor, D.col_ptr, (size_t)n_cnt * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) return ZIP_ERR_HIP;
+    return ZIP_OK;
+}
 }  // namespace
 
 int32_t zip_ccs_create(int32_t device, const zip_sparse_matrix *mats, uint32_t t, uint32_t s, const zip_field *field,
                        zip_ccs **out) {
     if (!mats || !out || !field) return ZIP_ERR_NULL;
     *out = nullptr;
-    if (t < 1 || t > (uint32_t)kCcsMaxMatrices || s < 1 || s > 28) return ZIP_ERR_INVALID_PARAM;
+    if (int32_t rc = ccs_check_matrices(mats, t, s)) return rc;
     const uint32_t m = 1u << s;
-    if (int32_t rc = ccs_check_matrices(mats, t, m)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ZIP_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
-    zip_ctx *ctx = new (std::nothrow) zip_ctx();
+    zip_ctx *ctx = nullptr;
+    int32_t rc = private_ctx_create(device, true, &ctx);
+    if (rc) return rc;
     zip_ccs *c = new (std::nothrow) zip_ccs();
-    if (!ctx || !c) { delete ctx; delete c; return ZIP_ERR_ALLOC; }
-    ctx->device = device;
-    ctx->recycle = true;
+    if (!c) { zip_ctx_destroy(ctx); return ZIP_ERR_ALLOC; }
     ctx->h2d_bounce_threshold = (size_t)256 << 10;  // MiB-sized index arrays: staged pageable copies run at 3-4 GB/s
     c->ctx = ctx;
-    int32_t rc = ZIP_OK;
     do {
-        if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
-        HostField hf;
+        HostField &hf = c->field;
         if ((rc = make_field(ctx, field, &hf))) break;
         c->t = t;
         c->s = s;
         c->m = m;
         c->fl = hf.fl;
-        memcpy(c->modulus, hf.modulus, sizeof c->modulus);
         const size_t elem = (size_t)hf.fl * 8, tab = (size_t)m * elem;
         for (uint32_t k = 0; k < t && rc == ZIP_OK; k++) {
             const zip_sparse_matrix &M = mats[k];
             zip_ccs::Mat &D = c->mat[k];
-            const uint32_t nnz = M.row_ptr[M.n_rows];
-            D.n_rows = M.n_rows;
-            D.nnz = nnz;
-            void *tmp = nullptr, *cursor = nullptr, *sums = nullptr;
-            const uint32_t n_cnt = m + 1, tiles = (n_cnt + kScanTile - 1) / kScanTile;
-            if ((rc = pool_alloc(ctx, (size_t)(M.n_rows + 1) * 4, (void **)&D.row_ptr))) break;
-            if ((rc = pool_alloc(ctx, (size_t)nnz * 4, (void **)&D.col_idx))) break;
-            if ((rc = pool_alloc(ctx, (size_t)n_cnt * 4, (void **)&D.col_ptr))) break;
-            if ((rc = pool_alloc(ctx, (size_t)nnz * 4, (void **)&D.row_idx))) break;
-            if ((rc = pool_alloc(ctx, (size_t)nnz * elem, (void **)&D.vals))) break;
-            if ((rc = pool_alloc(ctx, (size_t)nnz * elem, (void **)&D.vals_t))) break;
-            if ((rc = pool_alloc(ctx, (size_t)nnz * 8, &tmp))) break;       // i64 values before the field map
-            if ((rc = pool_alloc(ctx, (size_t)n_cnt * 4, &cursor))) break;  // per-column write positions
-            if ((rc = pool_alloc(ctx, (size_t)tiles * 4, &sums))) break;
-            if ((rc = copy_h2d_bounced(ctx, D.row_ptr, M.row_ptr, (size_t)(M.n_rows + 1) * 4, ctx->stream))) break;
-            if (hipMemsetAsync(D.col_ptr, 0, (size_t)n_cnt * 4, ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
-            if (nnz) {
-                if ((rc = copy_h2d_bounced(ctx, D.col_idx, M.col_idx, (size_t)nnz * 4, ctx->stream))) break;
+            void *tmp = nullptr;
+            uint32_t *cursor = nullptr, *sums = nullptr;
+            if ((rc = ccs_upload_matrix(ctx, M, m, elem, D, &cursor, &sums))) break;
+            if (D.nnz) {
+                if ((rc = pool_alloc(ctx, (size_t)D.nnz * 8, &tmp))) break;  // i64 values before the field map
                 // SparseMatrix::map_to_field (sparse_matrix.rs:38-58)
-                if ((rc = copy_h2d_bounced(ctx, tmp, M.values, (size_t)nnz * 8, ctx->stream))) break;
-                rc = with_fl(hf.fl, [&](auto FL) { return ccs_map_i64<decltype(FL)::value>(ctx, static_cast<const int64_t *>(tmp), nnz, nnz, D.vals, hf); });
+                if ((rc = copy_h2d_bounced(ctx, tmp, M.values, (size_t)D.nnz * 8, ctx->stream))) break;
+                rc = with_fl(hf.fl, [&](auto FL) { return ccs_map_i64<decltype(FL)::value>(ctx, static_cast<const int64_t *>(tmp), D.nnz, D.nnz, D.vals, hf); });
                 if (rc) break;
-                const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)nnz + 255) / 256, 65535);
-                hipLaunchKernelGGL(csc_count_kernel, dim3(blocks), dim3(256), 0, ctx->stream, D.col_idx, nnz, D.col_ptr);
-            }
-            // col_ptr = inclusive scan of the counters (counts sit at [col + 1], so col_ptr[0] = 0)
-            hipLaunchKernelGGL(scan_tiles_kernel, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, D.col_ptr, n_cnt,
-                               static_cast<uint32_t *>(sums), static_cast<const uint32_t *>(nullptr));
-            hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanBlock), 0, ctx->stream, static_cast<uint32_t *>(sums), tiles);
-            hipLaunchKernelGGL(scan_tiles_kernel, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, D.col_ptr, n_cnt,
-                               static_cast<uint32_t *>(nullptr), static_cast<const uint32_t *>(sums));
-            if (hipMemcpyAsync(cursor, D.col_ptr, (size_t)n_cnt * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
-            if (nnz) {
                 const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)M.n_rows + 255) / 256, 65535);
                 with_fl(hf.fl, [&](auto FL) {
-                    hipLaunchKernelGGL(csc_fill_kernel<decltype(FL)::value>, dim3(blocks), dim3(256), 0, ctx->stream, D.row_ptr, D.col_idx, D.vals, M.n_rows, static_cast<uint32_t *>(cursor), D.row_idx, D.vals_t);
+                    hipLaunchKernelGGL(csc_fill_kernel<decltype(FL)::value>, dim3(blocks), dim3(256), 0, ctx->stream, D.row_ptr, D.col_idx, D.vals, M.n_rows, cursor, D.row_idx, D.vals_t);
                 });
             }
             if (hipGetLastError() != hipSuccess || stream_wait(ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
@@ -5485,9 +5390,7 @@ int32_t zip_ccs_create(int32_t device, const zip_sparse_matrix *mats, uint32_t t
         if ((rc = pool_alloc(ctx, tab, (void **)&c->second))) break;
         if ((rc = pool_alloc(ctx, (size_t)(40 + kCcsMaxMatrices) * 64, (void **)&c->small_d))) break;
         if ((rc = pool_alloc(ctx, (((size_t)1 << (s / 2)) + ((size_t)1 << (s - s / 2))) * elem, (void **)&c->eq_half))) break;
-        int cus = 256;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-        c->dot_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)m + 255) / 256, (uint64_t)cus * 4);
+        c->dot_blocks = (uint32_t)std::min<uint64_t>(((uint64_t)m + 255) / 256, (uint64_t)ctx->num_cus * 4);
         if ((rc = pool_alloc(ctx, (size_t)c->dot_blocks * elem, (void **)&c->partials))) break;
     } while (0);
     if (rc) {
@@ -5512,9 +5415,8 @@ int32_t zip_ccs_set_z(zip_ccs *c, const int64_t *z, size_t z_len, zip_mem_kind k
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
     if (z_len > c->m) return fail(ctx, ZIP_ERR_SHAPE, "z has %zu entries, the matrices %u columns", z_len, c->m);
-    HostField hf;
+    const HostField &hf = c->field;
     int32_t rc;
-    if ((rc = ccs_field(c, &hf))) return rc;
     Scratch in(ctx);
     const int64_t *z_d = z;
     if (kind == ZIP_MEM_HOST && z_len) {
@@ -5535,9 +5437,8 @@ int32_t zip_ccs_eq_table(zip_ccs *c, const uint64_t *r, uint32_t slot) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
     if (slot > 1) return fail(ctx, ZIP_ERR_INVALID_PARAM, "slot %u: 0 = eq(beta), 1 = eq(r_x)", slot);
-    HostField hf;
+    const HostField &hf = c->field;
     int32_t rc;
-    if ((rc = ccs_field(c, &hf))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(c->small_d, r, (size_t)c->s * c->fl * 8, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = with_fl(c->fl, [&](auto FL) { return ccs_eq_table_fl<decltype(FL)::value>(c, c->small_d, slot, hf); }))) return rc;
     HIP_TRY(ctx, stream_wait(ctx->stream));
@@ -5553,8 +5454,7 @@ int32_t zip_ccs_second_table(zip_ccs *c, const uint64_t *r_x, const uint64_t *ga
     if (!c->have_z) return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_ccs_set_z has not run");
     int32_t rc;
     if ((rc = zip_ccs_eq_table(c, r_x, 1))) return rc;
-    HostField hf;
-    if ((rc = ccs_field(c, &hf))) return rc;
+    const HostField &hf = c->field;
     uint64_t *gamma_d = c->small_d + (size_t)32 * 8, *vs_d = c->small_d + (size_t)33 * 8;
     HIP_TRY(ctx, hipMemcpyAsync(gamma_d, gamma, (size_t)c->fl * 8, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = with_fl(c->fl, [&](auto FL) { return ccs_second_fl<decltype(FL)::value>(c, gamma_d, vs_d, hf); }))) return rc;
@@ -5573,8 +5473,7 @@ int32_t zip_ccs_eval_matrices(zip_ccs *c, const uint64_t *r_x, const uint64_t *r
     if ((rc = zip_ccs_eq_table(c, r_x, 0))) return rc;  // both eq slots are overwritten
     if ((rc = zip_ccs_eq_table(c, r_y, 1))) return rc;
     c->have_second = false;
-    HostField hf;
-    if ((rc = ccs_field(c, &hf))) return rc;
+    const HostField &hf = c->field;
     uint64_t *out_d = c->small_d + (size_t)33 * 8;
     if ((rc = with_fl(c->fl, [&](auto FL) { return ccs_eval_matrices_fl<decltype(FL)::value>(c, out_d, hf); }))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(v_xy_out, out_d, (size_t)c->t * c->fl * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -5624,27 +5523,23 @@ int32_t zip_ccs_batch_create(int32_t device, const zip_sparse_matrix *mats, uint
     // usage errors, before a device is looked for: NULLs, the ranges, the matrices, then this entry point's own size limit
     if (!mats || !out) return ZIP_ERR_NULL;
     *out = nullptr;
-    if (t < 1 || t > (uint32_t)kCcsMaxMatrices || s < 1 || s > 28) return ZIP_ERR_INVALID_PARAM;  // (zip_ccs_create's ranges)
     if (limbs < 2 || limbs > 4 || capacity < 1 || capacity > 65535) return ZIP_ERR_INVALID_PARAM;
-    if (int32_t rc = ccs_check_matrices(mats, t, 1u << s)) return rc;
+    if (int32_t rc = ccs_check_matrices(mats, t, s)) return rc;  // (zip_ccs_create's ranges and rules)
     if (s > kCcsBatchMaxVars) return ZIP_ERR_UNSUPPORTED;
     static_assert(kCcsBatchMaxVars == kBatchSumcheckMaxVars, "the tables feed zip_sumcheck_prove_batch");
     const uint32_t m = 1u << s;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ZIP_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
+    zip_ctx *ctx = nullptr;
+    int32_t rc = private_ctx_create(device, true, &ctx);
+    if (rc) return rc;
     const size_t elem = (size_t)limbs * 8, tab = (size_t)m * elem;
     const size_t tables_bytes = (size_t)capacity * (t + 4) * tab, z_bytes = (size_t)capacity * m * 8;
     {   // what cannot fit is refused without asking the allocator for it
         size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return ZIP_ERR_HIP;
-        if (tables_bytes + z_bytes > total_b) return ZIP_ERR_ALLOC;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) rc = ZIP_ERR_HIP;
+        else if (tables_bytes + z_bytes > total_b) rc = ZIP_ERR_ALLOC;
     }
-    zip_ctx *ctx = new (std::nothrow) zip_ctx();
-    zip_ccs_batch *b = new (std::nothrow) zip_ccs_batch();
-    if (!ctx || !b) { delete ctx; delete b; return ZIP_ERR_ALLOC; }
-    ctx->device = device;
-    ctx->recycle = true;
+    zip_ccs_batch *b = rc ? nullptr : new (std::nothrow) zip_ccs_batch();
+    if (!b) { zip_ctx_destroy(ctx); return rc ? rc : ZIP_ERR_ALLOC; }
     ctx->h2d_bounce_threshold = (size_t)256 << 10;  // (as zip_ccs_create)
     b->ctx = ctx;
     b->t = t;
@@ -5654,52 +5549,27 @@ int32_t zip_ccs_batch_create(int32_t device, const zip_sparse_matrix *mats, uint
     b->capacity = capacity;
     b->mats.t = t;
     b->mats.m = m;
-    int32_t rc = ZIP_OK;
     do {
-        if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { ctx->stream = nullptr; rc = ZIP_ERR_HIP; break; }
         std::vector<void *> tmp;  // per-matrix cursors and tile sums: released once the stream has passed them
-        const uint32_t n_cnt = m + 1, tiles = (n_cnt + kScanTile - 1) / kScanTile;
         for (uint32_t k = 0; k < t && rc == ZIP_OK; k++) {
             const zip_sparse_matrix &M = mats[k];
-            const uint32_t nnz = M.row_ptr[M.n_rows];
-            uint32_t *row_ptr = nullptr, *col_idx = nullptr, *col_ptr = nullptr, *row_idx = nullptr, *cursor = nullptr, *sums = nullptr;
-            int64_t *vals = nullptr, *vals_t = nullptr;
-            if ((rc = pool_alloc(ctx, (size_t)(M.n_rows + 1) * 4, (void **)&row_ptr))) break;
-            if ((rc = pool_alloc(ctx, (size_t)nnz * 4, (void **)&col_idx))) break;
-            if ((rc = pool_alloc(ctx, (size_t)n_cnt * 4, (void **)&col_ptr))) break;
-            if ((rc = pool_alloc(ctx, (size_t)nnz * 4, (void **)&row_idx))) break;
-            if ((rc = pool_alloc(ctx, (size_t)nnz * 8, (void **)&vals))) break;
-            if ((rc = pool_alloc(ctx, (size_t)nnz * 8, (void **)&vals_t))) break;
-            if ((rc = pool_alloc(ctx, (size_t)n_cnt * 4, (void **)&cursor))) break;
+            zip_ccs::Mat D;
+            uint32_t *cursor = nullptr, *sums = nullptr;
+            if ((rc = ccs_upload_matrix(ctx, M, m, 8, D, &cursor, &sums))) break;
             tmp.push_back(cursor);
-            if ((rc = pool_alloc(ctx, (size_t)tiles * 4, (void **)&sums))) break;
             tmp.push_back(sums);
-            b->mats.row_ptr[k] = row_ptr;
-            b->mats.col_idx[k] = col_idx;
-            b->mats.vals[k] = vals;
-            b->mats.col_ptr[k] = col_ptr;
-            b->mats.row_idx[k] = row_idx;
-            b->mats.vals_t[k] = vals_t;
+            b->mats.row_ptr[k] = D.row_ptr;
+            b->mats.col_idx[k] = D.col_idx;
+            b->mats.vals[k] = reinterpret_cast<const int64_t *>(D.vals);
+            b->mats.col_ptr[k] = D.col_ptr;
+            b->mats.row_idx[k] = D.row_idx;
+            b->mats.vals_t[k] = reinterpret_cast<const int64_t *>(D.vals_t);
             b->mats.n_rows[k] = M.n_rows;
-            if ((rc = copy_h2d_bounced(ctx, row_ptr, M.row_ptr, (size_t)(M.n_rows + 1) * 4, ctx->stream))) break;
-            if (hipMemsetAsync(col_ptr, 0, (size_t)n_cnt * 4, ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
-            if (nnz) {
-                if ((rc = copy_h2d_bounced(ctx, col_idx, M.col_idx, (size_t)nnz * 4, ctx->stream))) break;
-                if ((rc = copy_h2d_bounced(ctx, vals, M.values, (size_t)nnz * 8, ctx->stream))) break;
-                const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)nnz + 255) / 256, 65535);
-                hipLaunchKernelGGL(csc_count_kernel, dim3(blocks), dim3(256), 0, ctx->stream, col_idx, nnz, col_ptr);
-            }
-            // col_ptr = inclusive scan of the counters (counts sit at [col + 1], so col_ptr[0] = 0)
-            hipLaunchKernelGGL(scan_tiles_kernel, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, col_ptr, n_cnt, sums,
-                               static_cast<const uint32_t *>(nullptr));
-            hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanBlock), 0, ctx->stream, sums, tiles);
-            hipLaunchKernelGGL(scan_tiles_kernel, dim3(tiles), dim3(kScanBlock), 0, ctx->stream, col_ptr, n_cnt,
-                               static_cast<uint32_t *>(nullptr), static_cast<const uint32_t *>(sums));
-            if (hipMemcpyAsync(cursor, col_ptr, (size_t)n_cnt * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
-            if (nnz) {  // the int64 values travel as one-limb elements
+            if (D.nnz) {  // the int64 values travel as one-limb elements
+                if ((rc = copy_h2d_bounced(ctx, D.vals, M.values, (size_t)D.nnz * 8, ctx->stream))) break;
                 const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)M.n_rows + 255) / 256, 65535);
-                hipLaunchKernelGGL(csc_fill_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, row_ptr, col_idx,
-                                   reinterpret_cast<const uint64_t *>(vals), M.n_rows, cursor, row_idx, reinterpret_cast<uint64_t *>(vals_t));
+                hipLaunchKernelGGL(csc_fill_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, D.row_ptr, D.col_idx, D.vals, M.n_rows, cursor,
+                                   D.row_idx, D.vals_t);
             }
             if (hipGetLastError() != hipSuccess) { rc = ZIP_ERR_HIP; break; }
         }
@@ -5907,21 +5777,16 @@ int32_t zip_merkle_trees(int32_t device, const uint64_t *leaves, uint32_t leaf_l
                          uint32_t num_trees, zip_mem_kind kind, uint8_t *layers_out) {
     if (!leaves || !layers_out) return ZIP_ERR_NULL;
     if (leaf_limbs < 1 || leaf_limbs > 8 || depth > 24 || num_trees == 0) return ZIP_ERR_INVALID_PARAM;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ZIP_ERR_NO_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return ZIP_ERR_NO_DEVICE;
     // a throw-away ctx gives us the stream / pool / error plumbing
-    zip_ctx *ctx = new (std::nothrow) zip_ctx();
-    if (!ctx) return ZIP_ERR_ALLOC;
-    ctx->device = device;
-    int32_t rc = ZIP_OK;
+    zip_ctx *ctx = nullptr;
+    int32_t rc = private_ctx_create(device, false, &ctx);
+    if (rc) return rc;
     const uint32_t n = 1u << depth;
     const size_t leaf_bytes = (size_t)num_trees * n * leaf_limbs * 8;
     const size_t tree_bytes = (size_t)num_trees * 2 * n * 32;
     const size_t out_w = ((size_t)2 * n - 1) * 32;
     void *leaves_d = nullptr, *layers_d = nullptr, *roots_d = nullptr;
     do {
-        if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
         if (kind == ZIP_MEM_HOST) {
             if ((rc = pool_alloc(ctx, leaf_bytes, &leaves_d))) break;
             if (hipMemcpyAsync(leaves_d, leaves, leaf_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }
