@@ -300,8 +300,7 @@ int32_t zinc_prover_prove_spec(const zinc_linear_code_spec *spec, const zip_spar
  * (zip_ccs_batch), the tables of all proofs are built with a launch count that does not depend on n_instances, and each of
  * the two sumchecks is one zip_sumcheck_prove_batch; ZIP_HIP_BATCH=0, one instance and every other shape take the loop.
  * Every shape check runs on every instance before any transcript is touched.  with_pcs != 0 adds the PCS step of every
- * proof, one after the other: each proof draws its code's permutations from its own transcript (prover.rs:313), a batch
- * commit has one code for all members.
+ * proof (zinc_prover_pcs_step_batch below).
  *   spec          NULL: the default LinearCodeSpec
  *   outputs       instance-major, each instance with its own number of limbs, per instance as zinc_prover_prove;
  *                 zip_proofs_out: n_instances handles when with_pcs != 0 (each freed with zinc_zip_proof_free) */
@@ -311,6 +310,19 @@ int32_t zinc_prover_prove_batch(const zinc_linear_code_spec *spec, const zip_spa
                                 const size_t *w_len, zinc_transcript *const *transcripts, const uint64_t *moduli,
                                 const uint32_t *limbs, int32_t device, int32_t with_pcs, uint64_t *msgs1_out, uint64_t *msgs2_out,
                                 uint64_t *v_s_out, uint64_t *r_y_out, zinc_zip_proof **zip_proofs_out);
+
+/* The PCS step of zinc_prover_prove_batch alone (ZincProver::pcs_step_batch; tools/pcs_batch_times.py times it): for
+ * n_instances proofs of one circuit of 2^s columns, z[i] (z_len[i] entries, zero-extended), the point r_y[i] (s elements
+ * of limbs[i] limbs, instance-major) and the transcript as the Spartan part left them.  Every proof draws the two seeds of
+ * its RAA code from its own transcript (prover.rs:313); from the line profiles/pcs_step_batch.md sets on, all proofs are
+ * committed by one zip_batch_commit_codes and opened by one zip_batch_open_eval_fields + zip_batch_open_fields.  The loop
+ * over the one-proof step runs instead when ZIP_HIP_BATCH=0 is set, there is one instance, the spec asks for more than
+ * one proximity test, the codeword is above 8192, the limb counts differ, or n_instances is below that line
+ * (ZIP_HIP_PCS_MIN_BATCH=n moves it).  Same ZipProofs, transcripts and errors either way.
+ *   zip_proofs_out  n_instances handles (each freed with zinc_zip_proof_free) */
+int32_t zinc_prover_pcs_step_batch(const zinc_linear_code_spec *spec, uint32_t s, uint32_t n_instances, const int64_t *const *z,
+                                   const size_t *z_len, const uint64_t *r_y, zinc_transcript *const *transcripts,
+                                   const uint64_t *moduli, const uint32_t *limbs, int32_t device, zinc_zip_proof **zip_proofs_out);
 
 /* ZincVerifier (src/zinc/verifier.rs): SpartanVerifier::verify (:105-139), and with with_pcs != 0 also
  * verify_pcs_proof (:221-273: RaaCode::new from the transcript, MultilinearZip::verify, the matrix MLEs at

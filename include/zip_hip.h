@@ -47,7 +47,9 @@ extern "C" {
  * zip_ctx_set_proximity_tests / zip_ctx_proximity_tests: a ctx that never calls the setter behaves as before.  So is
  * zip_sumcheck_init_products, and so is zip_sumcheck_grid_counts.  So are zip_sumcheck_prove_batch and
  * zip_sumcheck_batch_counts: many small sumchecks in one launch, beside the one-at-a-time form that is unchanged.  So are the
- * zip_ccs_batch_* entry points: the Spartan tables of many proofs of one circuit, beside zip_ccs.) */
+ * zip_ccs_batch_* entry points: the Spartan tables of many proofs of one circuit, beside zip_ccs.  So are
+ * zip_batch_commit_codes, zip_batch_open_eval_fields, zip_batch_open_fields and zip_batch_codes_counts: a batch whose
+ * members have their own code and field, beside the shared-code batch that is unchanged.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -321,6 +323,51 @@ int32_t zip_batch_open_eval(zip_batch *b, const uint64_t *q0_mont, const zip_fie
                             zip_mem_kind out_kind);
 int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont,
                        const zip_field *field, uint8_t *proofs_out, zip_mem_kind out_kind);
+
+/* ---- batches whose members have their own code and their own field ----------------------
+ * A batch of Zinc proofs of one circuit (ZincProver::prove_batch): every proof draws the two seeds of its RAA code and
+ * its field from its own transcript (prover.rs:313), so the members of its PCS step share the geometry and nothing else.
+ * Only the commit reads a code -- the row combinations read the witness, the column openings read row entries and trees
+ * -- so ONE entry point takes the permutations per member, and the two open calls take the fields per member.
+ *
+ * zip_batch_commit_codes: zip_batch_commit with one RAA code per member.
+ *   perms1, perms2   HOST, n_polys * codeword_len entries each, member-major: member i's slices are what
+ *                    zip_params.perm1 / perm2 would be for it.  They are uploaded once, into the batch's storage.
+ * The ctx supplies geometry, streams and pools; its own permutations are not read.  Roots, rows and layers of member i
+ * are byte-identical to a plain zip_commit on a ctx created with member i's permutations.  The result is an ordinary
+ * zip_batch: zip_batch_size / _member / _free, zip_batch_open_eval / _open (which never read a permutation) and
+ * everything a member handle serves work on it unchanged; members are complete and unhinted, nothing re-runs a commit.
+ * Errors, before anything reaches the device, in zip_batch_commit's order with two additions: ZIP_ERR_NULL also for
+ * perms1 / perms2; ZIP_ERR_INVALID_PARAM (n_polys, row-sharded ctx); ZIP_ERR_UNSUPPORTED (codeword_len above 8192: the
+ * geometry is not built -- a Zinc batch has at most 2^16 rows, codewords of 1024 --, n_polys * num_rows beyond 32 bits);
+ * ZIP_ERR_SHAPE (n_evals); last, ZIP_ERR_INVALID_PARAM for a slice that is not a permutation of [0, codeword_len)
+ * (zip_ctx_create's test, per member).
+ *
+ * zip_batch_open_eval_fields, zip_batch_open_fields: the two open calls with one field per member.
+ *   fields     HOST, n_polys pointers; fields[i] is member i's field.  All share one `limbs` (as in zip_ccs_batch_set_z),
+ *              each has its own modulus; q0_mont's slice i holds Montgomery limbs of fields[i]
+ * Layouts, the stream stride (zip_proof_len depends on limbs only) and everything else are those of the one-field calls;
+ * stream i is byte-identical to zip_open of member i with fields[i].  Both work on a batch from either commit entry point.
+ * Errors in the one-field calls' order, where those look at their field: ZIP_ERR_NULL (fields, a fields[i]), then
+ * ZIP_ERR_INVALID_PARAM (limbs outside {2, 3, 4}, differing limb counts, a modulus that is even or 1) -- all before
+ * anything reaches the device.
+ *
+ * zip_batch_codes_counts: process-wide, monotonic, kept like zip_batch_verify_calls: zip_batch_commit_codes calls that
+ * reached the device, the members they committed, and calls of the two _fields entry points that reached the device.
+ * Any pointer may be NULL.
+ *
+ * Not part of this family: a batched verifier with a code and a field per member (zip_batch_verify would need the
+ * members' permutations in its two encode kernels and their fields in all five: the natural follow-up; until then such
+ * proofs are verified one at a time with zip_verify); codewords of 16384 and above; more than one proximity test in a
+ * batch; row-sharded contexts. */
+int32_t zip_batch_commit_codes(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uint32_t n_polys, zip_mem_kind evals_kind,
+                               const uint32_t *perms1, const uint32_t *perms2, uint8_t *roots_out, zip_batch **out);
+int32_t zip_batch_open_eval_fields(zip_batch *b, const uint64_t *q0_mont, const zip_field *const *fields, uint64_t *rows_out,
+                                   zip_mem_kind out_kind);
+int32_t zip_batch_open_fields(zip_batch *b, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols,
+                              const uint64_t *q0_mont, const zip_field *const *fields, uint8_t *proofs_out,
+                              zip_mem_kind out_kind);
+void zip_batch_codes_counts(uint64_t *commits, uint64_t *members, uint64_t *field_opens);
 
 /* ---- streaming proof writer -------------------------------
  * zip_open with the stream delivered to `sink` in order, piece by piece (u', then groups of opened

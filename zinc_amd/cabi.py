@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "zip_ccs_batch_second_tables", "zip_ccs_batch_table", "zip_ccs_batch_download", "zip_ccs_batch_counts",
     "zip_batch_commit", "zip_batch_size", "zip_batch_free", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open",
     "zip_batch_verify", "zip_batch_verify_calls",
+    "zip_batch_commit_codes", "zip_batch_open_eval_fields", "zip_batch_open_fields", "zip_batch_codes_counts",
     "zip_prime_test_base2", "zip_get_prime", "zip_prime_launch_counts",
 )
 
@@ -294,7 +295,13 @@ def lib():
     L.zip_batch_member.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
     L.zip_batch_open_eval.argtypes = [vp, u64p, C.POINTER(ZipField), u64p, C.c_int]
     L.zip_batch_open.argtypes = [vp, i64p, u32p, C.c_uint32, u64p, C.POINTER(ZipField), u8p, C.c_int]
-    for fn in ("zip_batch_commit", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open"):
+    L.zip_batch_commit_codes.argtypes = [vp, i64p, C.c_size_t, C.c_uint32, C.c_int, u32p, u32p, u8p, C.POINTER(vp)]
+    L.zip_batch_open_eval_fields.argtypes = [vp, u64p, vp, u64p, C.c_int]
+    L.zip_batch_open_fields.argtypes = [vp, i64p, u32p, C.c_uint32, u64p, vp, u8p, C.c_int]
+    L.zip_batch_codes_counts.argtypes = [C.POINTER(C.c_uint64)] * 3
+    L.zip_batch_codes_counts.restype = None
+    for fn in ("zip_batch_commit", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open", "zip_batch_commit_codes",
+               "zip_batch_open_eval_fields", "zip_batch_open_fields"):
         getattr(L, fn).restype = C.c_int32
     L.zip_commitment_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.zip_commit_download.argtypes = [vp, u64p, u8p, u8p]
@@ -464,6 +471,25 @@ class ZipContext:
         h = C.c_void_p()
         rc = lib().zip_batch_commit(self._h, ptr, n, n_polys, kind, roots.ctypes.data if roots is not None else None, C.byref(h))
         self._check(rc, "zip_batch_commit")
+        return Batch(self, h, evals_2d if kind == MEM_DEVICE else None, roots)
+
+    def batch_commit_codes(self, evals_2d, perms1_2d, perms2_2d, want_roots=True):
+        """zip_batch_commit_codes: batch_commit with one RAA code per member.  perms1_2d / perms2_2d: [n_polys,
+        codeword_len] uint32, member i's rows being what perm1 / perm2 of a ZipContext for it would be; this ctx's own
+        permutations are not read.  -> Batch, as batch_commit."""
+        ptr, kind = _ptr(evals_2d)
+        n = evals_2d.size if isinstance(evals_2d, np.ndarray) else evals_2d.numel()
+        n_polys = evals_2d.shape[0] if len(evals_2d.shape) > 1 else 1
+        p1 = np.ascontiguousarray(perms1_2d, dtype=np.uint32) if perms1_2d is not None else None
+        p2 = np.ascontiguousarray(perms2_2d, dtype=np.uint32) if perms2_2d is not None else None
+        assert p1 is None or p1.size == n_polys * self.codeword_len
+        assert p2 is None or p2.size == n_polys * self.codeword_len
+        roots = np.zeros((n_polys, self.num_rows, 32), dtype=np.uint8) if want_roots else None
+        h = C.c_void_p()
+        rc = lib().zip_batch_commit_codes(self._h, ptr, n, n_polys, kind, p1.ctypes.data if p1 is not None else None,
+                                          p2.ctypes.data if p2 is not None else None,
+                                          roots.ctypes.data if roots is not None else None, C.byref(h))
+        self._check(rc, "zip_batch_commit_codes")
         return Batch(self, h, evals_2d if kind == MEM_DEVICE else None, roots)
 
     def commit_open(self, evals, coeffs, cols, q0_mont, field, out=None, want_roots=True, keep=False):
@@ -815,6 +841,45 @@ class Batch:
         c._check(rc, "zip_batch_open")
         return res
 
+    @staticmethod
+    def _field_ptrs(fields):
+        """zip_field *const * over a list of ZipField (None entries stay NULL); the list keeps the fields alive"""
+        arr = (C.POINTER(ZipField) * max(len(fields), 1))()
+        for i, f in enumerate(fields):
+            if f is not None:
+                arr[i] = C.pointer(f)
+        return arr
+
+    def open_eval_fields(self, q0_mont, fields, out=None):
+        """zip_batch_open_eval_fields: open_eval with fields[i] (a ZipField, all of one limb count) for polynomial i;
+        q0_mont's slice i holds Montgomery limbs of fields[i]."""
+        c = self.ctx
+        limbs = fields[0].limbs
+        q0 = np.ascontiguousarray(q0_mont, dtype=np.uint64) if q0_mont is not None else None
+        res = out if out is not None else np.zeros((len(self), c.row_len, limbs), dtype=np.uint64)
+        optr, okind = _ptr(res)
+        arr = self._field_ptrs(fields)
+        rc = lib().zip_batch_open_eval_fields(self._h, q0.ctypes.data if q0 is not None else None, C.cast(arr, C.c_void_p), optr, okind)
+        c._check(rc, "zip_batch_open_eval_fields")
+        return res
+
+    def open_fields(self, coeffs, cols, q0_mont, fields, out=None):
+        """zip_batch_open_fields: open with fields[i] for polynomial i -> [n_polys, proof_len] bytes, stream i what
+        zip_open of member i with fields[i] writes."""
+        c = self.ctx
+        limbs = fields[0].limbs
+        cols = np.ascontiguousarray(cols, dtype=np.uint32).reshape(len(self), -1)
+        coeffs_c = np.ascontiguousarray(coeffs, dtype=np.int64) if coeffs is not None else None
+        q0 = np.ascontiguousarray(q0_mont, dtype=np.uint64) if q0_mont is not None else None
+        n_cols = cols.shape[1]
+        res = out if out is not None else np.zeros((len(self), c.proof_len(n_cols, limbs)), dtype=np.uint8)
+        optr, okind = _ptr(res)
+        arr = self._field_ptrs(fields)
+        rc = lib().zip_batch_open_fields(self._h, coeffs_c.ctypes.data if coeffs_c is not None else None, cols.ctypes.data, n_cols,
+                                         q0.ctypes.data if q0 is not None else None, C.cast(arr, C.c_void_p), optr, okind)
+        c._check(rc, "zip_batch_open_fields")
+        return res
+
 
 class Commitment:
     """Device-resident MultilinearZipData (+ roots) behind a zip_commitment handle."""
@@ -933,6 +998,14 @@ def merkle_trees(leaves, depth, device=0):
 def batch_verify_calls() -> int:
     """zip_batch_verify_calls: zip_batch_verify calls of this process that reached the device"""
     return lib().zip_batch_verify_calls()
+
+
+def batch_codes_counts():
+    """zip_batch_codes_counts: (zip_batch_commit_codes calls that reached the device, members they committed, calls of the
+    two _fields opens that reached the device) in this process so far"""
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    lib().zip_batch_codes_counts(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
 
 
 def sumcheck_launch_counts():

@@ -38,8 +38,13 @@ struct BatchCombineArgs {
 
 constexpr uint32_t kBatchCombineThreads = 64;
 
-template <int FL, bool DO_INT, bool QUIRK>
-__global__ void __launch_bounds__(kBatchCombineThreads) batch_combine_kernel(BatchCombineArgs a, FieldDev<FL> f) {
+// The signed-modulus quirk (make_field, combine_rows_kernel) of the members of one launch: none of them, all of them
+// (one modulus: zip_batch_open), or decided per member at run time, quirk_mod == 0 meaning none (batch_combine_fields_kernel)
+enum BatchQuirk { kQuirkNone = 0, kQuirkAlways = 1, kQuirkPerMember = 2 };
+
+// polynomial blockIdx.y in the field f (quirk_mod: its 2^(64 FL) - q where that fits 64 bits, see BatchQuirk)
+template <int FL, bool DO_INT, int QUIRK>
+__device__ __forceinline__ void batch_combine_body(const BatchCombineArgs &a, const FieldDev<FL> &f, uint64_t quirk_mod) {
     const uint32_t col = blockIdx.x * kBatchCombineThreads + threadIdx.x;
     const uint32_t b = blockIdx.y;
     const uint32_t R = a.num_rows;
@@ -71,8 +76,8 @@ __global__ void __launch_bounds__(kBatchCombineThreads) batch_combine_kernel(Bat
             const uint64_t t[2] = {cb, 0};
             add_n<2>(Kc, t);
         }
-        if (QUIRK) {  // (the field half only: see combine_rows_kernel)
-            const uint64_t mag = (w < 0 ? (uint64_t)0 - (uint64_t)w : (uint64_t)w) % a.quirk_mod;
+        if (QUIRK == kQuirkAlways || (QUIRK == kQuirkPerMember && quirk_mod)) {  // (the field half only: see combine_rows_kernel)
+            const uint64_t mag = (w < 0 ? (uint64_t)0 - (uint64_t)w : (uint64_t)w) % quirk_mod;
             const uint64_t qb = (uint64_t)((w < 0) ? -(int64_t)mag : (int64_t)mag) ^ kBias;
             w0 = (uint32_t)qb;
             w1 = (uint32_t)(qb >> 32);
@@ -143,6 +148,28 @@ __global__ void __launch_bounds__(kBatchCombineThreads) batch_combine_kernel(Bat
             for (int i = 0; i < FL; i++) dst[i] = __builtin_bswap64(ra[FL - 1 - i]);
         }
     }
+}
+
+template <int FL, bool DO_INT, bool QUIRK>
+__global__ void __launch_bounds__(kBatchCombineThreads) batch_combine_kernel(BatchCombineArgs a, FieldDev<FL> f) {
+    batch_combine_body<FL, DO_INT, QUIRK ? kQuirkAlways : kQuirkNone>(a, f, a.quirk_mod);
+}
+
+// One field per polynomial (zip_batch_open_eval_fields, zip_batch_open_fields): polynomial b's field constants and
+// quirk_mod are entry b of a device array.  The entry sits at a wave-uniform address, so it is read through the scalar
+// cache (as kernels_spartan_batch.cuh reads its per-instance arguments); BatchCombineArgs.quirk_mod is not read, and
+// q0 is never shared: with one row, polynomial b multiplies by ITS 1_mont.
+template <int FL>
+struct BatchFieldInst {
+    FieldDev<FL> f;
+    uint64_t quirk_mod;  // 0: this member's modulus has no quirk
+};
+
+template <int FL, bool DO_INT>
+__global__ void __launch_bounds__(kBatchCombineThreads)
+batch_combine_fields_kernel(BatchCombineArgs a, const BatchFieldInst<FL> *__restrict__ inst) {
+    const BatchFieldInst<FL> &m = inst[blockIdx.y];
+    batch_combine_body<FL, DO_INT, kQuirkPerMember>(a, m.f, m.quirk_mod);
 }
 
 // ---------------------------------------------------------------------------

@@ -79,6 +79,9 @@ struct CommitArgs {
     unsigned long long *clock;
     // raa_commit_slab_kernel (cw 32768 / 65536): [gridDim.x][cw] 16-byte entries, one slab per workgroup
     uint4 *slab;
+    // raa_commit_kernel<.., CODES> (zip_batch_commit_codes): the rows are those of MEMBERS of 2^log_member_rows rows each,
+    // and member m = row >> log_member_rows has its own RAA code: perm1 / perm2 hold one slice of cw entries per member
+    uint32_t log_member_rows;
 #ifdef ZIPK_DEBUG_STAMPS
     // tools/wg_spread.py, tools/ubench_pipeline.hip: kStampRec words per workgroup (100 MHz wall clock):
     // [0] start [1] end [2] XCC id | HW_ID << 8 [3..5] time in the scan passes / hash phase / chunk ends [6] rows done
@@ -807,7 +810,13 @@ __device__ __forceinline__ uint32_t opaque_zero(uint32_t dep) {
 // predicated off by a per-lane, row-invariant bit mask.  That variant needs one VGPR more than the 96 of the
 // plain one and is allowed 104 (4 x 104 of the 512 per SIMD still leave room for three gather waves, and the
 // gather's LDS image limits it to two workgroups per CU beside this kernel anyway).
-template <int E, bool HASH, int MODE = kStoreAll>
+// CODES = one RAA code per member of a batch (CommitArgs.log_member_rows): the indices held are those of ONE member, and a
+// row of another member reloads them from that member's slice first.  The member of a row is wave-uniform (the row comes
+// from blockIdx and the round), so the test is a scalar branch.  The reload pays what the round-3 form above paid per
+// row -- its first use waits for the previous row's stores -- but only where the member changes; with one workgroup
+// per row that is every row, which the launches this serves (a batch of small polynomials: bound by the number of
+// launches, not by issue rate) accept.  The row loop is the plain one: rows are not assigned member-major.
+template <int E, bool HASH, int MODE = kStoreAll, bool CODES = false>
 __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
     constexpr bool MASKED = MODE != kStoreAll;
     // packed commits keep natural ownership in the output phase (OwnLeaves8): three barriers per row, no transposition
@@ -838,19 +847,22 @@ __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
     // 1.528-1.537 instead of 1.564-1.574 ms (alternated four times).  (The round-3 form was removed: EXPERIMENTS.md.)
     // The unpacking is kept inside the row loop (`^ z`, an opaque 0): hoisted, it is 16 more registers (109).
     uint32_t pidx[E];
+    size_t code_at = 0;  // CODES: where the slice of the member held starts in perm1 / perm2
     auto load_pidx = [&](uint32_t t) {
 #pragma unroll
         for (int e = 0; e < E; e++) {
             uint32_t v1 = 0, v2 = 0;
             if (active) {
-                v1 = a.perm1[t * E + e] & (row_len - 1);  // repeat: t0[j] = row[j mod row_len]
-                const uint32_t p2 = a.perm2[t * E + e];
+                v1 = a.perm1[code_at + t * E + e] & (row_len - 1);  // repeat: t0[j] = row[j mod row_len]
+                const uint32_t p2 = a.perm2[code_at + t * E + e];
                 v2 = (p2 & (E - 1)) * PS + (p2 >> LOGE);
             }
             pidx[e] = v1 | (v2 << 16);
         }
     };
-    load_pidx(tid0);
+    static_assert(!CODES || (HASH && MODE == kStoreAll), "a code per member: full, hashed commits only");
+    uint32_t member_held = 0xFFFFFFFFu;  // CODES: no member's indices yet (the first row loads them)
+    if constexpr (!CODES) load_pidx(tid0);
     // ... the lane's store mask under an opening hint ...
     const uint32_t smask = !(MASKED && active) ? 0xFFFFFFFFu
                            : OWN               ? store_mask_own8(a.need, cw, tid0)
@@ -900,6 +912,14 @@ __global__ void __launch_bounds__(1024, 4) raa_commit_kernel(CommitArgs a) {
         const uint32_t tid = tid0 + z;
         const int64_t *in = a.evals + (size_t)row * row_len;
         uint64_t *out_row = a.rows + (size_t)row * cw * (a.compact_rows ? 2 : 4);
+        if constexpr (CODES) {
+            const uint32_t member = row >> a.log_member_rows;  // (wave-uniform)
+            if (member != member_held) {
+                member_held = member;
+                code_at = (size_t)member * cw;
+                load_pidx(tid0);
+            }
+        }
 
         const bool has_next = row + gridDim.x < a.num_rows;
         if (!(prefetch && round)) {

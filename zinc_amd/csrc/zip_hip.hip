@@ -206,10 +206,11 @@ struct zip_ctx {
 };
 
 // The device storage of a zip_batch: the row entries, trees and roots of all its polynomials in one block each (and the
-// library's copy of a HOST witness).  The batch and every member handle taken from it (zip_batch_member) hold a
-// reference; the blocks return to the pool with the last of them.
+// library's copy of a HOST witness; for zip_batch_commit_codes the members' permutations, perm1 slices then perm2
+// slices).  The batch and every member handle taken from it (zip_batch_member) hold a reference; the blocks return to
+// the pool with the last of them.
 struct BatchStore {
-    void *rows = nullptr, *layers = nullptr, *roots = nullptr, *evals = nullptr;
+    void *rows = nullptr, *layers = nullptr, *roots = nullptr, *evals = nullptr, *perms = nullptr;
     std::function<void(BatchStore &)> release;
     BatchStore() = default;
     BatchStore(const BatchStore &) = delete;
@@ -892,11 +893,11 @@ int32_t ensure_dynamic_lds(zip_ctx *ctx, const void *kern, size_t bytes) {
 
 // ------------------------------------------------------------------ commit dispatch
 // Persistent launch: as many workgroups as stay resident together (at most one per row).
-template <int E, bool HASH, int MODE = kStoreAll>
+template <int E, bool HASH, int MODE = kStoreAll, bool CODES = false>
 int32_t launch_commit(zip_ctx *ctx, const CommitArgs &a, uint32_t threads, uint32_t grid, hipStream_t st) {
     // wave totals + E planes of (threads + 32/E) slots of 12 bytes + the witness row (+ the opening tables)
     size_t lds = 512 + (size_t)E * (threads + 32 / E) * 12 + (size_t)a.row_len * 8 + 4 * kFinisherFlagWords;
-    auto kern = raa_commit_kernel<E, HASH, MODE>;
+    auto kern = raa_commit_kernel<E, HASH, MODE, CODES>;
     if (int32_t rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
     LaunchTimer t(ctx, HASH ? "raa_commit_kernel" : "raa_encode_kernel", st);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, a);
@@ -1139,6 +1140,23 @@ int32_t dispatch_commit(zip_ctx *ctx, CommitArgs a, uint32_t grid, hipStream_t s
         case 4: return launch_commit<4, HASH>(ctx, a, g.threads, grid, st);
         case 2: return launch_commit<2, HASH>(ctx, a, g.threads, grid, st);
         default: return launch_commit<1, HASH>(ctx, a, g.threads, grid, st);
+    }
+}
+
+// zip_batch_commit_codes: a.perm1 / a.perm2 hold one slice per member of 2^a.log_member_rows rows.  Built for the
+// geometries of raa_commit_kernel (cw <= 8192), stored in full and hashed.
+constexpr uint32_t kMaxCodesCodeword = 8192;
+int32_t dispatch_commit_codes(zip_ctx *ctx, CommitArgs a, uint32_t grid, hipStream_t st) {
+    const CommitGeom g = commit_geom(a.cw, a.row_len);
+    a.nact = a.cw / g.e < g.threads ? a.cw / g.e : g.threads;
+    a.pk = nullptr;
+    a.need = nullptr;
+    switch (g.e) {
+        case 8: return launch_commit<8, true, kStoreAll, true>(ctx, a, g.threads, grid, st);
+        case 4: return launch_commit<4, true, kStoreAll, true>(ctx, a, g.threads, grid, st);
+        case 2: return launch_commit<2, true, kStoreAll, true>(ctx, a, g.threads, grid, st);
+        case 1: return launch_commit<1, true, kStoreAll, true>(ctx, a, g.threads, grid, st);
+        default: return fail(ctx, ZIP_ERR_UNSUPPORTED, "a code per member is not built for codeword %u", a.cw);
     }
 }
 
@@ -2694,6 +2712,30 @@ int32_t launch_batch_combine_fl(zip_ctx *ctx, BatchCombineArgs a, uint32_t n_pol
 int32_t launch_batch_combine(zip_ctx *ctx, const BatchCombineArgs &a, uint32_t n_polys, bool do_int, const HostField &hf) {
     return with_fl(hf.fl, [&](auto FL) { return launch_batch_combine_fl<decltype(FL)::value>(ctx, a, n_polys, do_int, hf); });
 }
+
+// BatchFieldInst<FL>[B] for batch_combine_fields_kernel, and the members' 1_mont (what a one-row batch multiplies by)
+template <int FL>
+void batch_fill_field_args(const std::vector<HostField> &hf, std::vector<unsigned char> *inst, std::vector<uint64_t> *ones) {
+    inst->assign(hf.size() * sizeof(BatchFieldInst<FL>), 0);
+    ones->resize(hf.size() * FL);
+    BatchFieldInst<FL> *a = reinterpret_cast<BatchFieldInst<FL> *>(inst->data());
+    for (size_t i = 0; i < hf.size(); i++) {
+        a[i].f = to_dev<FL>(hf[i]);
+        a[i].quirk_mod = hf[i].quirk_mod;
+        memcpy(ones->data() + i * FL, hf[i].r, 8 * FL);
+    }
+}
+
+template <int FL>
+int32_t launch_batch_combine_fields_fl(zip_ctx *ctx, const BatchCombineArgs &a, uint32_t n_polys, bool do_int, const void *inst_d) {
+    const dim3 grid((a.row_len + kBatchCombineThreads - 1) / kBatchCombineThreads, n_polys), block(kBatchCombineThreads);
+    const BatchFieldInst<FL> *inst = static_cast<const BatchFieldInst<FL> *>(inst_d);
+    LaunchTimer t(ctx, "batch_combine_fields_kernel", ctx->stream);
+    if (do_int) hipLaunchKernelGGL((batch_combine_fields_kernel<FL, true>), grid, block, 0, ctx->stream, a, inst);
+    else hipLaunchKernelGGL((batch_combine_fields_kernel<FL, false>), grid, block, 0, ctx->stream, a, inst);
+    HIP_TRY(ctx, hipGetLastError());
+    return ZIP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3988,15 +4030,25 @@ int32_t zip_job_wait(zip_job *j, uint8_t *roots_out) {
 // The verifier's side, batch_verify_z (verify_z.rs:40-58), is zip_batch_verify beside zip_verify below: five launches
 // whatever B is (kernels_batch_verify.cuh), the verdicts folded on the device, B reports copied back.
 // =====================================================================================================
-int32_t zip_batch_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uint32_t n_polys, zip_mem_kind evals_kind,
-                         uint8_t *roots_out, zip_batch **out) {
+// Process-wide (zip_batch_codes_counts): zip_batch_commit_codes calls that reached the device, the members they committed,
+// and the calls of zip_batch_open_eval_fields / zip_batch_open_fields that reached the device
+static std::atomic<uint64_t> g_batch_codes_commits{0}, g_batch_codes_members{0}, g_batch_field_opens{0};
+
+// zip_batch_commit (codes == false: the ctx's permutations for every member) and zip_batch_commit_codes (perms1 / perms2:
+// HOST, one slice of codeword_len entries per member)
+static int32_t batch_commit_impl(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uint32_t n_polys, zip_mem_kind evals_kind,
+                                 bool codes, const uint32_t *perms1, const uint32_t *perms2, uint8_t *roots_out, zip_batch **out) {
     if (!ctx || !evals || !out) return ZIP_ERR_NULL;
     *out = nullptr;
+    if (codes && (!perms1 || !perms2)) return ZIP_ERR_NULL;
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
     const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len;
     if (n_polys == 0 || n_polys > 65535)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "a batch holds 1 .. 65535 polynomials (got %u)", n_polys);
     if (ctx->rows_local != R) return fail(ctx, ZIP_ERR_INVALID_PARAM, "batches need an unsharded ctx");
+    if (codes && cw > kMaxCodesCodeword)
+        return fail(ctx, ZIP_ERR_UNSUPPORTED, "a code per member is built for codewords up to %u: the geometry of codeword %u is "
+                    "not built", kMaxCodesCodeword, cw);
     if (cw > 16384)
         return fail(ctx, ZIP_ERR_UNSUPPORTED, "batches serve codewords up to 16384 (got %u): larger polynomials are not launch-bound, "
                     "use zip_commit_open_begin", cw);
@@ -4005,7 +4057,24 @@ int32_t zip_batch_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uin
     if (n_evals != (size_t)n_polys * R * C)
         return fail(ctx, ZIP_ERR_SHAPE, "A batch of %u polynomials has an incorrect number of evaluations (%zu) for the expected "
                     "matrix size (%zu each)", n_polys, n_evals, (size_t)R * C);
+    if (codes) {  // zip_ctx_create's test of a permutation, per member
+        std::vector<uint8_t> seen(cw);
+        for (uint32_t i = 0; i < n_polys; i++)
+            for (int k = 0; k < 2; k++) {
+                const uint32_t *perm = (k ? perms2 : perms1) + (size_t)i * cw;
+                std::fill(seen.begin(), seen.end(), 0);
+                for (uint32_t j = 0; j < cw; j++) {
+                    if (perm[j] >= cw || seen[perm[j]])
+                        return fail(ctx, ZIP_ERR_INVALID_PARAM, "member %u: perm%d is not a permutation of [0, %u)", i, k + 1, cw);
+                    seen[perm[j]] = 1;
+                }
+            }
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (codes) {
+        g_batch_codes_commits++;
+        g_batch_codes_members += n_polys;
+    }
     const uint32_t total = n_polys * R;
     zip_batch *b = new (std::nothrow) zip_batch();
     if (!b) return ZIP_ERR_ALLOC;
@@ -4024,6 +4093,7 @@ int32_t zip_batch_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uin
             pool_release(ctx, s.layers);
             pool_release(ctx, s.roots);
             pool_release(ctx, s.evals);
+            pool_release(ctx, s.perms);
         };
     }
     BatchStore &S = *b->store;
@@ -4038,6 +4108,13 @@ int32_t zip_batch_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uin
             if ((rc = copy_h2d_bounced(ctx, S.evals, evals, n_evals * 8, ctx->s_commit))) break;
             b->evals_d = static_cast<const int64_t *>(S.evals);
         }
+        const size_t perm_words = (size_t)n_polys * cw;
+        if (codes) {  // every member's permutations, once: all perm1 slices, then all perm2 slices
+            if ((rc = pool_alloc(ctx, 2 * perm_words * 4, &S.perms))) break;
+            uint32_t *pd = static_cast<uint32_t *>(S.perms);
+            if ((rc = copy_h2d_bounced(ctx, pd, perms1, perm_words * 4, ctx->s_commit))) break;
+            if ((rc = copy_h2d_bounced(ctx, pd + perm_words, perms2, perm_words * 4, ctx->s_commit))) break;
+        }
         // the launch of commit_impl for `total` rows: as many workgroups as stay resident, equal chunks of about four
         // rounds (a chunk end is where the kernel builds the upper tree levels of the rows it has finished)
         const CommitGeom geom = commit_geom(cw, C);
@@ -4049,8 +4126,9 @@ int32_t zip_batch_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uin
         CommitArgs a{};
         a.classes = 1;
         a.evals = b->evals_d;
-        a.perm1 = ctx->perm1_d;
-        a.perm2 = ctx->perm2_d;
+        a.perm1 = codes ? static_cast<const uint32_t *>(S.perms) : ctx->perm1_d;
+        a.perm2 = codes ? static_cast<const uint32_t *>(S.perms) + perm_words : ctx->perm2_d;
+        a.log_member_rows = ilog2(R);
         a.rows = static_cast<uint64_t *>(S.rows);
         a.compact_rows = 1u;
         a.layers = static_cast<uint32_t *>(S.layers);
@@ -4059,7 +4137,7 @@ int32_t zip_batch_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uin
         a.num_rows = total;
         a.rounds_per_chunk = rpc;
         a.roots = static_cast<uint32_t *>(S.roots);
-        if ((rc = dispatch_commit<true>(ctx, a, G, ctx->s_commit))) break;
+        if ((rc = codes ? dispatch_commit_codes(ctx, a, G, ctx->s_commit) : dispatch_commit<true>(ctx, a, G, ctx->s_commit))) break;
         // the handle and its members are complete when this call returns: nothing later has to wait for the commit
         hipError_t e = stream_wait(ctx->s_commit);
         if (e != hipSuccess) { rc = fail(ctx, ZIP_ERR_HIP, "batch commit failed: %s", hipGetErrorString(e)); break; }
@@ -4071,6 +4149,22 @@ int32_t zip_batch_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uin
     }
     *out = b;
     return ZIP_OK;
+}
+
+int32_t zip_batch_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uint32_t n_polys, zip_mem_kind evals_kind,
+                         uint8_t *roots_out, zip_batch **out) {
+    return batch_commit_impl(ctx, evals, n_evals, n_polys, evals_kind, false, nullptr, nullptr, roots_out, out);
+}
+
+int32_t zip_batch_commit_codes(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uint32_t n_polys, zip_mem_kind evals_kind,
+                               const uint32_t *perms1, const uint32_t *perms2, uint8_t *roots_out, zip_batch **out) {
+    return batch_commit_impl(ctx, evals, n_evals, n_polys, evals_kind, true, perms1, perms2, roots_out, out);
+}
+
+void zip_batch_codes_counts(uint64_t *commits, uint64_t *members, uint64_t *field_opens) {
+    if (commits) *commits = g_batch_codes_commits.load();
+    if (members) *members = g_batch_codes_members.load();
+    if (field_opens) *field_opens = g_batch_field_opens.load();
 }
 
 uint32_t zip_batch_size(const zip_batch *b) { return b ? b->n_polys : 0; }
@@ -4107,18 +4201,53 @@ int32_t zip_batch_member(zip_batch *b, uint32_t index, zip_commitment **out) {
     return ZIP_OK;
 }
 
-int32_t zip_batch_open_eval(zip_batch *b, const uint64_t *q0_mont, const zip_field *field, uint64_t *rows_out,
-                            zip_mem_kind out_kind) {
+// The fields of a _fields call: FieldConfig::new per member, before anything reaches the device.  Every NULL first, then
+// the limb counts (one for all, 2 .. 4), then the moduli (odd, above 1); neighbours with the same modulus share the work.
+static int32_t batch_member_fields(zip_ctx *ctx, const zip_field *const *fields, uint32_t B, std::vector<HostField> *out) {
+    if (!fields) return fail(ctx, ZIP_ERR_NULL, "fields is NULL");
+    for (uint32_t i = 0; i < B; i++)
+        if (!fields[i]) return fail(ctx, ZIP_ERR_NULL, "fields[%u] is NULL", i);
+    const uint32_t fl = fields[0]->limbs;
+    if (fl < 2 || fl > 4) return fail(ctx, ZIP_ERR_INVALID_PARAM, "field limbs %u not in {2,3,4}", fl);
+    for (uint32_t i = 1; i < B; i++)
+        if (fields[i]->limbs != fl)
+            return fail(ctx, ZIP_ERR_INVALID_PARAM, "member %u: a field of %u limbs, member 0 has %u", i, fields[i]->limbs, fl);
+    out->resize(B);
+    for (uint32_t i = 0; i < B; i++) {
+        if (i && !memcmp(fields[i]->modulus, fields[i - 1]->modulus, 8 * (size_t)fl)) {
+            (*out)[i] = (*out)[i - 1];
+            continue;
+        }
+        if (int32_t rc = make_field_uncached(ctx, fields[i], &(*out)[i])) return rc;
+    }
+    return ZIP_OK;
+}
+
+// The one-field calls (fields == nullptr) and the _fields calls (field == nullptr) share everything but the field checks
+// -- the latter's run before the device is touched -- and the row combination's kernel.
+static int32_t batch_open_eval_impl(zip_batch *b, const uint64_t *q0_mont, const zip_field *field, const zip_field *const *fields,
+                                    bool per_member, uint64_t *rows_out, zip_mem_kind out_kind) {
     if (!b || !rows_out) return ZIP_ERR_NULL;
     zip_ctx *ctx = b->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!per_member) HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
     HostField hf;
+    std::vector<HostField> hfs;
     int32_t rc;
-    if ((rc = make_field(ctx, field, &hf))) return rc;
     const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, B = b->n_polys;
+    if (per_member) {
+        if ((rc = batch_member_fields(ctx, fields, B, &hfs))) return rc;
+        hf = hfs[0];
+    } else if ((rc = make_field(ctx, field, &hf))) return rc;
     const bool single = R == 1;
     if (!single && !q0_mont) return fail(ctx, ZIP_ERR_NULL, "q0_mont is NULL");
+    std::vector<unsigned char> inst_h;
+    std::vector<uint64_t> ones_h;
+    if (per_member) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        g_batch_field_opens++;
+        with_fl(hf.fl, [&](auto FL) { batch_fill_field_args<decltype(FL)::value>(hfs, &inst_h, &ones_h); });
+    }
     const size_t bytes = (size_t)B * C * hf.fl * 8;
     Scratch res(ctx), small(ctx);
     uint64_t *out_d = rows_out;
@@ -4127,40 +4256,68 @@ int32_t zip_batch_open_eval(zip_batch *b, const uint64_t *q0_mont, const zip_fie
         out_d = res.as<uint64_t>();
     }
     SmallInputs si;
-    si.src[1] = single ? hf.r : q0_mont;  // one row: the evaluation row is map_to_field(evals) = 1_mont * w (open_z.rs:84-88)
-    si.bytes[1] = single ? (size_t)hf.fl * 8 : (size_t)B * R * hf.fl * 8;
+    // one row: the evaluation row is map_to_field(evals) = 1_mont * w (open_z.rs:84-88), 1_mont of the member's field
+    si.src[1] = !single ? (const void *)q0_mont : per_member ? (const void *)ones_h.data() : (const void *)hf.r;
+    si.bytes[1] = single && !per_member ? (size_t)hf.fl * 8 : (size_t)B * R * hf.fl * 8;
+    si.src[3] = inst_h.data();
+    si.bytes[3] = inst_h.size();
     unsigned char *sb;
     if ((rc = stage_small(ctx, si, small, &sb))) return rc;
     BatchCombineArgs a{};
     a.evals = b->evals_d;
     a.q0 = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
-    a.q0_shared = single ? 1u : 0u;
+    a.q0_shared = single && !per_member ? 1u : 0u;
     a.num_rows = R;
     a.row_len = C;
     a.m_limbs = ctx->p.m_limbs;
     a.quirk_mod = hf.quirk_mod;
     a.row_limbs = out_d;
-    if ((rc = launch_batch_combine(ctx, a, B, false, hf))) return rc;
+    if (per_member)
+        rc = with_fl(hf.fl, [&](auto FL) { return launch_batch_combine_fields_fl<decltype(FL)::value>(ctx, a, B, false, sb + si.off[3]); });
+    else rc = launch_batch_combine(ctx, a, B, false, hf);
+    if (rc) return rc;
     if (out_kind == ZIP_MEM_HOST) return deliver(ctx, rows_out, ZIP_MEM_HOST, out_d, bytes);
     HIP_TRY(ctx, stream_wait(ctx->stream));  // q0 was read from host memory
     return ZIP_OK;
 }
 
-int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont,
-                       const zip_field *field, uint8_t *proofs_out, zip_mem_kind out_kind) {
+int32_t zip_batch_open_eval(zip_batch *b, const uint64_t *q0_mont, const zip_field *field, uint64_t *rows_out,
+                            zip_mem_kind out_kind) {
+    return batch_open_eval_impl(b, q0_mont, field, nullptr, false, rows_out, out_kind);
+}
+
+int32_t zip_batch_open_eval_fields(zip_batch *b, const uint64_t *q0_mont, const zip_field *const *fields, uint64_t *rows_out,
+                                   zip_mem_kind out_kind) {
+    return batch_open_eval_impl(b, q0_mont, nullptr, fields, true, rows_out, out_kind);
+}
+
+static int32_t batch_open_impl(zip_batch *b, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont,
+                               const zip_field *field, const zip_field *const *fields, bool per_member, uint8_t *proofs_out,
+                               zip_mem_kind out_kind) {
     if (!b || !proofs_out || (n_cols && !cols)) return ZIP_ERR_NULL;
     zip_ctx *ctx = b->ctx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!per_member) HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
     HostField hf;
+    std::vector<HostField> hfs;
     int32_t rc;
-    if ((rc = refuse_extra_tests(ctx, "zip_batch_open"))) return rc;
-    if ((rc = make_field(ctx, field, &hf))) return rc;
+    if ((rc = refuse_extra_tests(ctx, per_member ? "zip_batch_open_fields" : "zip_batch_open"))) return rc;
     const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, B = b->n_polys;
+    if (per_member) {
+        if ((rc = batch_member_fields(ctx, fields, B, &hfs))) return rc;
+        hf = hfs[0];
+    } else if ((rc = make_field(ctx, field, &hf))) return rc;
     const bool single = R == 1;
     if (!single && (!coeffs || !q0_mont)) return fail(ctx, ZIP_ERR_NULL, "coeffs / q0_mont is NULL");
     if ((uint64_t)B * n_cols > 0xFFFFFFFFull) return fail(ctx, ZIP_ERR_UNSUPPORTED, "%u x %u openings exceed 2^32", B, n_cols);
     if ((rc = check_cols(ctx, cols, B * n_cols))) return rc;
+    std::vector<unsigned char> inst_h;
+    std::vector<uint64_t> ones_h;
+    if (per_member) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        g_batch_field_opens++;
+        with_fl(hf.fl, [&](auto FL) { batch_fill_field_args<decltype(FL)::value>(hfs, &inst_h, &ones_h); });
+    }
     const size_t stream_bytes = zip_proof_len(ctx, n_cols, hf.fl), total = (size_t)B * stream_bytes;
     const size_t u_bytes = single ? 0 : (size_t)C * ctx->p.m_limbs * 8;
     const size_t col_bytes = (size_t)n_cols * column_bytes(ctx);
@@ -4175,10 +4332,12 @@ int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols
         si.src[0] = coeffs;
         si.bytes[0] = (size_t)B * R * 8;
     }
-    si.src[1] = single ? hf.r : q0_mont;
-    si.bytes[1] = single ? (size_t)hf.fl * 8 : (size_t)B * R * hf.fl * 8;
+    si.src[1] = !single ? (const void *)q0_mont : per_member ? (const void *)ones_h.data() : (const void *)hf.r;
+    si.bytes[1] = single && !per_member ? (size_t)hf.fl * 8 : (size_t)B * R * hf.fl * 8;
     si.src[2] = cols;
     si.bytes[2] = (size_t)B * n_cols * 4;
+    si.src[3] = inst_h.data();
+    si.bytes[3] = inst_h.size();
     unsigned char *sb;
     if ((rc = stage_small(ctx, si, small, &sb))) return rc;
     // 1. every polynomial's u' and evaluation row, straight to their places in its stream
@@ -4186,7 +4345,7 @@ int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols
     a.evals = b->evals_d;
     a.coeffs = single ? nullptr : reinterpret_cast<const int64_t *>(sb + si.off[0]);
     a.q0 = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
-    a.q0_shared = single ? 1u : 0u;
+    a.q0_shared = single && !per_member ? 1u : 0u;
     a.num_rows = R;
     a.row_len = C;
     a.m_limbs = ctx->p.m_limbs;
@@ -4194,7 +4353,10 @@ int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols
     a.uprime = single ? nullptr : out_d;
     a.row_be = out_d + u_bytes + col_bytes;
     a.out_stride = stream_bytes;
-    if ((rc = launch_batch_combine(ctx, a, B, !single, hf))) return rc;
+    if (per_member)
+        rc = with_fl(hf.fl, [&](auto FL) { return launch_batch_combine_fields_fl<decltype(FL)::value>(ctx, a, B, !single, sb + si.off[3]); });
+    else rc = launch_batch_combine(ctx, a, B, !single, hf);
+    if (rc) return rc;
     // 2. every polynomial's column openings
     if (n_cols) {
         BatchOpenColsArgs g{};
@@ -4219,6 +4381,16 @@ int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols
     if (out_kind == ZIP_MEM_HOST) return deliver(ctx, proofs_out, ZIP_MEM_HOST, out_d, total);
     HIP_TRY(ctx, stream_wait(ctx->stream));  // coeffs, cols and q0 were read from host memory
     return ZIP_OK;
+}
+
+int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont,
+                       const zip_field *field, uint8_t *proofs_out, zip_mem_kind out_kind) {
+    return batch_open_impl(b, coeffs, cols, n_cols, q0_mont, field, nullptr, false, proofs_out, out_kind);
+}
+
+int32_t zip_batch_open_fields(zip_batch *b, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont,
+                              const zip_field *const *fields, uint8_t *proofs_out, zip_mem_kind out_kind) {
+    return batch_open_impl(b, coeffs, cols, n_cols, q0_mont, nullptr, fields, true, proofs_out, out_kind);
 }
 
 // =====================================================================================================

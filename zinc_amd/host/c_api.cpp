@@ -728,6 +728,34 @@ int32_t zinc_prover_prove_batch(const zinc_linear_code_spec *spec, const zip_spa
     });
 }
 
+int32_t zinc_prover_pcs_step_batch(const zinc_linear_code_spec *spec, uint32_t s, uint32_t n_instances, const int64_t *const *z,
+                                   const size_t *z_len, const uint64_t *r_y, zinc_transcript *const *transcripts,
+                                   const uint64_t *moduli, const uint32_t *limbs, int32_t device, zinc_zip_proof **zip_proofs_out) {
+    if (!z || !z_len || !r_y || !transcripts || !moduli || !limbs || !zip_proofs_out) return ZINC_ERR_NULL;
+    for (uint32_t i = 0; i < n_instances; i++) {
+        if (!transcripts[i] || (z_len[i] && !z[i])) return ZINC_ERR_NULL;
+        zip_proofs_out[i] = nullptr;
+    }
+    return guarded([&] {
+        const zinc::ccs::CCS_Z ccs = square_ccs(1, s);  // (the PCS step reads m and s_prime alone)
+        std::vector<zinc::ZincProver::ZVector> zs(n_instances);
+        std::vector<zinc::KeccakTranscript *> tr(n_instances);
+        std::vector<std::vector<Limbs>> points(n_instances);
+        std::vector<FieldConfig> f;
+        size_t at = 0;
+        for (uint32_t i = 0; i < n_instances; i++) {
+            zs[i] = {z[i], z_len[i]};
+            tr[i] = &transcripts[i]->t;
+            f.push_back(FieldConfig::make(moduli + (size_t)i * 4, limbs[i]));
+            points[i].assign(s, Limbs{});
+            for (uint32_t k = 0; k < s; k++)
+                for (uint32_t j = 0; j < limbs[i]; j++) points[i][k][j] = r_y[at++];
+        }
+        auto proofs = zinc::ZincProver(spec_of(spec), device).pcs_step_batch(ccs, zs, points, tr, f);
+        for (uint32_t i = 0; i < n_instances; i++) zip_proofs_out[i] = new zinc_zip_proof{std::move(proofs[i]), limbs[i]};
+    });
+}
+
 int32_t zinc_verifier_verify(const zip_sparse_matrix *constraints, uint32_t t, uint32_t s, uint32_t d, uint32_t q,
                              const uint32_t *s_masks, const int64_t *c, zinc_transcript *transcript, const uint64_t *modulus,
                              uint32_t limbs, int32_t device, zinc_prepared_ccs *prepared, const uint64_t *msgs1,

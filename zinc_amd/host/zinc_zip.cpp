@@ -1218,6 +1218,107 @@ zip::ZipProof zip::commit_z_mle_and_prove_evaluation(const LinearCodeSpec &lc_sp
     return out;
 }
 
+// The same for B proofs whose z fill one geometry, each with its own main transcript (hence its own RAA code: :313)
+// and its own field: ONE zip_batch_commit_codes, ONE zip_batch_open_eval_fields, the walk of B fresh PcsTranscripts and
+// v_i = <row_i, q1_i> on the host, ONE zip_batch_open_fields.  What is shared is the geometry, and with it the ctx
+// (streams, pools) and the witness block; per member are the permutations (read by the commit alone), the field, the
+// point, the challenges.  The caller has made sure of what the batch serves (one proximity test, codewords up to 8192,
+// one limb count); everything a member's own step would throw is thrown here at the same member, in the same order.
+std::vector<zip::ZipProof> zip::commit_z_mle_and_prove_evaluation_batch(const LinearCodeSpec &lc_spec, size_t m,
+                                                                        const std::vector<PcsBatchMember> &members, int device) {
+    const size_t B = members.size();
+    std::vector<ZipProof> out(B);
+    if (!B) return out;
+    PcsStageTimer timer;
+    // 1. per proof, in the reference's order: the code from its transcript, the two permutations, the point's tensors
+    MultilinearZipParams param;
+    std::vector<uint32_t> perms1, perms2;
+    std::vector<uint64_t> q0_all;
+    std::vector<std::vector<uint64_t>> q1(B);
+    uint32_t cw = 0, fl = members[0].config->limbs;
+    for (size_t i = 0; i < B; i++) {
+        const PcsBatchMember &mb = members[i];
+        KeccakSeedSource seeds(*mb.transcript);
+        const RaaCode code = RaaCode::make(lc_spec, m, seeds);  // prover.rs:313
+        if (i == 0) {
+            param = MultilinearZip::setup(m, code, device);     // :314; the ctx of the geometry, cached like any other
+            cw = code.codeword_len();
+            perms1.resize(B * (size_t)cw);
+            perms2.resize(B * (size_t)cw);
+            std::memcpy(perms1.data(), param.perm1.data(), (size_t)cw * 4);
+            std::memcpy(perms2.data(), param.perm2.data(), (size_t)cw * 4);
+        } else {
+            const auto p1 = shuffle_seeded_perm(code.perm_1_seed, cw), p2 = shuffle_seeded_perm(code.perm_2_seed, cw);
+            std::memcpy(perms1.data() + i * cw, p1.data(), (size_t)cw * 4);
+            std::memcpy(perms2.data() + i * cw, p2.data(), (size_t)cw * 4);
+        }
+        if (mb.r_y_len != param.num_vars)
+            throw ZipError(ZipError::InvalidPcsParam, "IncorrectLength: the point does not have num_vars coordinates");
+        std::vector<uint64_t> q0;
+        point_to_tensor(*mb.config, param.num_rows, mb.r_y, mb.r_y_len, q0, q1[i]);
+        q0_all.insert(q0_all.end(), q0.begin(), q0.end());
+    }
+    timer.lap("batch: codes + tensors");
+    zip_ctx *ctx = param.ctx.get();
+    const uint32_t num_rows = param.num_rows, row_len = param.linear_code.row_len, n_cols = param.linear_code.num_column_opening;
+    // 2. one commit: the members' z, polynomial-major
+    IntVec packed(B * m);
+    for (size_t i = 0; i < B; i++) std::memcpy(packed.data() + i * m, members[i].z_evals, m * 8);
+    std::vector<uint8_t> roots(B * (size_t)num_rows * 32);
+    zip_batch *raw = nullptr;
+    check(ctx, zip_batch_commit_codes(ctx, packed.data(), B * m, (uint32_t)B, ZIP_MEM_HOST, perms1.data(), perms2.data(), roots.data(), &raw),
+          "zip_batch_commit_codes");
+    std::shared_ptr<zip_batch> batch(raw, zip_batch_free);
+    timer.lap("batch: commit");
+    // 3. every evaluation row, each in its member's field
+    std::vector<zip_field> zf(B);
+    std::vector<const zip_field *> zfp(B);
+    for (size_t i = 0; i < B; i++) {
+        zf[i] = members[i].config->to_abi();
+        zfp[i] = &zf[i];
+    }
+    const uint64_t *q0p = q0_all.empty() ? nullptr : q0_all.data();
+    std::vector<uint64_t> rows(B * (size_t)row_len * fl);
+    check(ctx, zip_batch_open_eval_fields(raw, q0p, zfp.data(), rows.data(), ZIP_MEM_HOST), "zip_batch_open_eval_fields");
+    timer.lap("batch: evaluation rows");
+    // 4. per proof: v = <row, q1> (:317-319; what zip_commitment_mle_eval computes -- a one-column matrix evaluates to its
+    // entry), then the walk of a FRESH PcsTranscript (:316): coefficients, columns, the row's absorption
+    std::vector<int64_t> coeffs(num_rows > 1 ? B * (size_t)num_rows : 0);
+    std::vector<uint32_t> cols(B * (size_t)n_cols);
+    std::vector<PcsTranscript> walks(B);
+    for (size_t i = 0; i < B; i++) {
+        const FieldConfig &f = *members[i].config;
+        const uint64_t *row = rows.data() + i * (size_t)row_len * fl;
+        Limbs v{};
+        for (uint32_t c = 0; c < row_len; c++) {
+            Limbs t{}, q = f.r;
+            for (uint32_t k = 0; k < fl; k++) t[k] = row[(size_t)c * fl + k];
+            if (row_len > 1)
+                for (uint32_t k = 0; k < fl; k++) q[k] = q1[i][(size_t)c * fl + k];
+            f.mul_assign(t, q);
+            f.add_assign(v, t);
+        }
+        out[i].v = v;
+        MultilinearZip::batch_open_challenges(num_rows, row_len, cw, n_cols, f, walks[i], row, 1,
+                                              coeffs.empty() ? nullptr : coeffs.data() + i * num_rows, cols.data() + i * n_cols);
+    }
+    timer.lap("batch: v + transcripts");
+    // 5. every proof stream in one call, cut into the ZipProofs
+    const size_t len = zip_proof_len(ctx, n_cols, fl);
+    ByteStream streams;
+    streams.resize(B * len);
+    check(ctx, zip_batch_open_fields(raw, coeffs.empty() ? nullptr : coeffs.data(), cols.data(), n_cols, q0p, zfp.data(), streams.data(),
+                                     ZIP_MEM_HOST),
+          "zip_batch_open_fields");
+    for (size_t i = 0; i < B; i++) {
+        out[i].z_comm.roots.resize(num_rows);
+        std::memcpy(out[i].z_comm.roots.data(), roots.data() + i * (size_t)num_rows * 32, (size_t)num_rows * 32);
+        out[i].pcs_proof.assign(streams.begin() + i * len, streams.begin() + (i + 1) * len);
+    }
+    timer.lap("batch: open");
+    return out;
+}
+
 namespace {
 sumcheck::ProverOutput prove_as_subprotocol_impl(KeccakTranscript &transcript, const std::vector<const uint64_t *> &mles,
                                                  uint32_t nvars, uint32_t degree, const zip_sumcheck_comb *comb,
@@ -1861,16 +1962,73 @@ std::vector<ZincProof> ZincProver::prove_batch(const zip_sparse_matrix *matrices
                                                const std::vector<KeccakTranscript *> &transcripts,
                                                const std::vector<FieldConfig> &configs, std::vector<std::vector<Limbs>> *r_y_out) const {
     auto spartan = spartan_prove_batch(matrices, ccs, zs, transcripts, configs);
-    // The PCS step stays a loop: every proof draws the permutations of its RAA code from its own transcript
-    // (prover.rs:313), zip_batch_commit has one code for all its members.
+    std::vector<std::vector<Limbs>> r_y(zs.size());
+    for (size_t i = 0; i < zs.size(); i++) r_y[i] = std::move(spartan[i].second);
+    StageTimer timer;
+    auto zip_proofs = pcs_step_batch(ccs, zs, r_y, transcripts, configs);
+    timer.lap("pcs_step_batch");
     std::vector<ZincProof> out(zs.size());
-    if (r_y_out) r_y_out->clear();
     for (size_t i = 0; i < zs.size(); i++) {
         out[i].spartan_proof = std::move(spartan[i].first);
-        out[i].zip_proof = pcs_step(zs[i].z, zs[i].len, ccs, spartan[i].second, *transcripts[i], configs[i]);
-        if (r_y_out) r_y_out->push_back(std::move(spartan[i].second));
+        out[i].zip_proof = std::move(zip_proofs[i]);
     }
+    if (r_y_out) *r_y_out = std::move(r_y);
     return out;
+}
+
+namespace {
+// From how many proofs on the PCS step is taken as one batch: where commit_codes + the two _fields opens beat the loop
+// over pcs_step by more than the loop's own spread (profiles/pcs_step_batch.md, 1000 openings, 4 limbs).  That is ONE
+// measured point: 256 proofs at 2^10 rows (1.41x).  The batch LOSES everywhere else it was measured -- B = 2, 3, 4, 8, 16
+// at 2^10 .. 2^16 (0.17x .. 0.89x; 1.11x at 2^10 x 16 is inside the loop's spread) and B = 256 at 2^12, 2^14, 2^16
+// (0.78x, 0.52x, 0.47x) -- so the loop stays there: a proof stream is 7.4 .. 84 MB at these sizes, and the batch moves all
+// of them through one device block and one host block before cutting them.  A size between the measured ones takes the
+// rule of the next larger one; above 2^10 rows there is no line.
+// ZIP_HIP_PCS_MIN_BATCH=n (n >= 2, read per call) puts the line at n for every size: how tools/pcs_batch_times.py measures
+// the batch below the line.
+size_t min_pcs_batch(size_t s_prime) {
+    if (const char *e = std::getenv("ZIP_HIP_PCS_MIN_BATCH")) {
+        const long n = std::atol(e);
+        if (n >= 2) return (size_t)n;
+    }
+    return s_prime <= 10 ? 256 : SIZE_MAX;
+}
+}  // namespace
+
+std::vector<zip::ZipProof> ZincProver::pcs_step_batch(const ccs::CCS_Z &ccs, const std::vector<ZVector> &zs,
+                                                      const std::vector<std::vector<Limbs>> &r_y,
+                                                      const std::vector<KeccakTranscript *> &transcripts,
+                                                      const std::vector<FieldConfig> &configs) const {
+    const size_t B = zs.size();
+    if (r_y.size() != B || transcripts.size() != B || configs.size() != B)
+        throw std::logic_error("pcs_step_batch: one point, one transcript and one field per z");
+    // the geometry RaaCode::make will give every member (code_raa.rs:43), known before a transcript is touched
+    const uint64_t cw = ccs.m && !(ccs.m & (ccs.m - 1)) ? zip::next_pow2(zip::isqrt(ccs.m)) * lc_spec_.repetition_factor : UINT64_MAX;
+    bool batched = zip::batch_path_enabled() && B >= 2 && B <= 65535 && lc_spec_.num_proximity_testing <= 1 && cw <= 8192 &&
+                   B >= min_pcs_batch(ccs.s_prime);
+    for (size_t i = 1; i < B && batched; i++) batched = configs[i].limbs == configs[0].limbs;
+    std::vector<zip::ZipProof> out(B);
+    if (!batched) {
+        for (size_t i = 0; i < B; i++) out[i] = pcs_step(zs[i].z, zs[i].len, ccs, r_y[i], *transcripts[i], configs[i]);
+        return out;
+    }
+    // z_mle = from_evaluations_slice(s_prime, z_ccs), as pcs_step pads it
+    const size_t n_mle = (size_t)1 << ccs.s_prime;
+    std::vector<IntVec> padded(B);
+    std::vector<zip::PcsBatchMember> members(B);
+    for (size_t i = 0; i < B; i++) {
+        members[i].z_evals = zs[i].z;
+        if (zs[i].len != n_mle) {
+            padded[i].assign(n_mle, 0);
+            std::memcpy(padded[i].data(), zs[i].z, std::min(zs[i].len, n_mle) * 8);
+            members[i].z_evals = padded[i].data();
+        }
+        members[i].r_y = r_y[i].data();
+        members[i].r_y_len = r_y[i].size();
+        members[i].transcript = transcripts[i];
+        members[i].config = &configs[i];
+    }
+    return zip::commit_z_mle_and_prove_evaluation_batch(lc_spec_, ccs.m, members, device_);
 }
 
 // ---------------------------------------------------------------------------- sumcheck verifier

@@ -348,6 +348,20 @@ struct ZipProof {
 ZipProof commit_z_mle_and_prove_evaluation(const LinearCodeSpec &lc_spec, const int64_t *z_evals, size_t m,
                                            const Limbs *r_y, size_t r_y_len, KeccakTranscript &transcript,
                                            const FieldConfig &config, int device = 0);
+// The PCS step of B proofs whose z fill ONE geometry (m evaluations each) in one commit and one open: each proof's code
+// comes from its own main transcript, so the members share the geometry and nothing else -- zip_batch_commit_codes takes
+// the permutations per member, zip_batch_open_eval_fields / zip_batch_open_fields the fields.  Per proof the result, the
+// main transcript afterwards and whatever is thrown are those of commit_z_mle_and_prove_evaluation called member after
+// member.  The caller sees to what the device batch serves: one proximity test, codeword_len <= 8192, one limb count.
+struct PcsBatchMember {
+    const int64_t *z_evals = nullptr;  // m evaluations
+    const Limbs *r_y = nullptr;
+    size_t r_y_len = 0;
+    KeccakTranscript *transcript = nullptr;
+    const FieldConfig *config = nullptr;
+};
+std::vector<ZipProof> commit_z_mle_and_prove_evaluation_batch(const LinearCodeSpec &lc_spec, size_t m,
+                                                              const std::vector<PcsBatchMember> &members, int device = 0);
 
 }  // namespace zip
 
@@ -519,9 +533,16 @@ class ZincProver {
     std::vector<SpartanOutput> spartan_prove_batch(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs,
                                                    const std::vector<ZVector> &zs, const std::vector<KeccakTranscript *> &transcripts,
                                                    const std::vector<FieldConfig> &configs) const;
-    // spartan_prove_batch, then the PCS step of every proof as the loop of commit_z_mle_and_prove_evaluation: each proof
-    // draws the permutations of its RAA code from its own transcript (prover.rs:313), and zip_batch_commit has ONE code
-    // for all its members -- a PCS step with per-member codes is not built.
+    // The PCS step of B proofs of one ccs, r_y[i] and transcripts[i] as spartan_prove_batch left them: the ZipProofs,
+    // the transcripts afterwards and the errors of the loop over pcs_step, member after member.  One commit and one open
+    // for all of them (zip::commit_z_mle_and_prove_evaluation_batch) -- unless ZIP_HIP_BATCH=0 is set, there is one
+    // instance, the spec asks for more than one proximity test, the codeword is above 8192, the fields differ in their
+    // limb count, or B is below the line of min_pcs_batch (zinc_zip.cpp; ZIP_HIP_PCS_MIN_BATCH=n moves it): then the loop.
+    std::vector<zip::ZipProof> pcs_step_batch(const ccs::CCS_Z &ccs, const std::vector<ZVector> &zs,
+                                              const std::vector<std::vector<Limbs>> &r_y,
+                                              const std::vector<KeccakTranscript *> &transcripts,
+                                              const std::vector<FieldConfig> &configs) const;
+    // spartan_prove_batch, then pcs_step_batch.
     std::vector<ZincProof> prove_batch(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs, const std::vector<ZVector> &zs,
                                        const std::vector<KeccakTranscript *> &transcripts, const std::vector<FieldConfig> &configs,
                                        std::vector<std::vector<Limbs>> *r_y_out = nullptr) const;

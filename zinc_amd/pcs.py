@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = (
     "zinc_zip_proof_num_roots", "zinc_zip_proof_read", "zinc_zip_proof_free", "zinc_zip_release_cached_contexts", "zinc_sumcheck_prove_product", "zinc_sumcheck_prove_ccs", "zinc_zip_data_download", "zinc_zip_data_upload", "zinc_merkle_tree_new",
     "zinc_prover_prove", "zinc_prover_prepare", "zinc_prepared_ccs_free", "zinc_verifier_verify",
     "zinc_sumcheck_prove_products", "zinc_sumcheck_verify", "zinc_sumcheck_prove_batch", "zinc_prover_prove_batch",
+    "zinc_prover_pcs_step_batch",
     "zinc_zip_batch_commit", "zinc_zip_batch_open", "zinc_zip_batch_open_challenges",
     "zinc_zip_batch_verify", "zinc_zip_batch_verify_challenges",
     "zinc_get_prime", "zinc_draw_random_field", "zinc_verifier_verify_checked",
@@ -157,6 +158,7 @@ def lib():
                                         C.POINTER(vp)]
         L.zinc_prover_prove_batch.argtypes = [C.POINTER(LinearCodeSpec), vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
                                               C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+        L.zinc_prover_pcs_step_batch.argtypes = [C.POINTER(LinearCodeSpec), C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_int32, vp]
         L.zinc_prover_prepare.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_int32, C.POINTER(vp)]
         L.zinc_prepared_ccs_free.argtypes = [vp]
         L.zinc_prepared_ccs_free.restype = None
@@ -798,9 +800,45 @@ class ZincProver:
         return self._run_batch(matrices, s, d, S, c, xs, ws, transcripts, fields, False)
 
     def prove_batch(self, matrices, s, d, S, c, xs, ws, transcripts, fields):
-        """spartan_prove_batch, then the PCS step of every proof, one after the other (each proof draws its code from its
-        own transcript) -> a list of the dicts prove returns."""
+        """spartan_prove_batch, then the PCS step of every proof (ZincProver::pcs_step_batch): each proof draws its code
+        from its own transcript, and from the line profiles/pcs_step_batch.md sets on all of them are committed in one
+        zip_batch_commit_codes and opened in one pair of _fields calls; ZIP_HIP_BATCH=0, one proof, more than one proximity
+        test and every other shape take the loop over the one-proof step, with the same bytes -> a list of the dicts
+        prove returns."""
         return self._run_batch(matrices, s, d, S, c, xs, ws, transcripts, fields, True)
+
+    def pcs_step_batch(self, s, zs, r_ys, transcripts, fields):
+        """The PCS step of prove_batch alone (ZincProver::pcs_step_batch; tools/pcs_batch_times.py): zs[i] the z vector
+        (x || 1 || w) of proof i, r_ys[i] its point [s, limbs] and transcripts[i] as spartan_prove_batch left them
+        -> a list of zip_proof dicts (z_comm, v, pcs_proof)."""
+        B = len(zs)
+        assert len(r_ys) == B and len(transcripts) == B and len(fields) == B
+        z = [np.ascontiguousarray(v, dtype=np.int64).reshape(-1) for v in zs]
+        n = max(B, 1)
+        zp = (C.c_void_p * n)(*[v.ctypes.data for v in z])
+        zl = (C.c_size_t * n)(*[v.size for v in z])
+        trs = (C.c_void_p * n)(*[tr._h for tr in transcripts])
+        limbs = np.array([f.limbs for f in fields], dtype=np.uint32)
+        moduli = np.zeros((n, 4), dtype=np.uint64)
+        for i, f in enumerate(fields):
+            moduli[i, :f.limbs] = np.asarray(f._m, dtype=np.uint64)[:f.limbs]
+        ry = np.concatenate([np.ascontiguousarray(r, dtype=np.uint64).reshape(-1) for r in r_ys]) if B else np.zeros(1, np.uint64)
+        assert ry.size == s * int(limbs.sum()) or not B
+        hs = (C.c_void_p * n)()
+        _check(lib().zinc_prover_pcs_step_batch(_spec_ptr(self.spec), s, B, zp, zl, ry.ctypes.data, trs, moduli.ctypes.data,
+                                                limbs.ctypes.data, self.device, hs))
+        out = []
+        for i, fl in enumerate(int(v) for v in limbs):
+            h = C.c_void_p(hs[i])
+            try:
+                roots = np.zeros((lib().zinc_zip_proof_num_roots(h), 32), np.uint8)
+                v = np.zeros(fl, np.uint64)
+                proof = np.zeros(lib().zinc_zip_proof_len(h), np.uint8)
+                lib().zinc_zip_proof_read(h, roots.ctypes.data, v.ctypes.data, proof.ctypes.data)
+            finally:
+                lib().zinc_zip_proof_free(h)
+            out.append(dict(z_comm=roots, v=v, pcs_proof=proof))
+        return out
 
 
 class ZincVerifier:
