@@ -324,6 +324,31 @@ int32_t zinc_prover_pcs_step_batch(const zinc_linear_code_spec *spec, uint32_t s
                                    const size_t *z_len, const uint64_t *r_y, zinc_transcript *const *transcripts,
                                    const uint64_t *moduli, const uint32_t *limbs, int32_t device, zinc_zip_proof **zip_proofs_out);
 
+/* zinc_verifier_verify_spec (with_pcs != 0) for n_instances proofs of ONE circuit, each with its own transcript and field
+ * (ZincVerifier::verify_batch): results_out[i] and transcripts[i] afterwards are what the loop over zinc_verifier_verify
+ * leaves, for rejected proofs as well, and the call does not stop at the first reject.  From the line
+ * profiles/verify_batch.md sets on (2 instances up to 2^10 rows and at 2^14, 16 at 2^12 and 2^16;
+ * ZIP_HIP_VERIFY_MIN_BATCH=n moves it to n at every size), with one limb count, s <= 16, one
+ * proximity test and codewords up to 16384, the PCS part of all proofs is ONE zip_batch_verify_codes call -- a code and a
+ * field per proof, the streams read where they lie -- and the matrix MLEs are ONE zip_ccs_batch_eval_matrices; ZIP_HIP_BATCH=0,
+ * one instance and every other shape take the loop.
+ *   per-instance arrays, as zinc_prover_prove_batch writes them: msgs1 / msgs2 / v_s instance-major, instance i with
+ *   limbs[i] limbs per element; moduli n_instances * 4 limbs; roots[i] (n_roots[i] hashes), v instance-major (limbs[i]
+ *   each), pcs_proofs[i] (pcs_proof_lens[i] bytes, read in place)
+ *   results_out   n_instances codes: ZINC_OK, ZINC_ERR_SPARTAN (a sumcheck or the final equation failed) or
+ *                 ZINC_ERR_INVALID_OPEN (the Zip verifier rejected) -- ZINC_ERR_INVALID_PARAM where verify gives that
+ *   messages_out  may be NULL; else n_instances slots of message_cap bytes: the NUL-terminated (cut if need be) message
+ *                 of what zinc_verifier_verify would have reported for that proof alone, empty for an accepted one
+ * The function result is ZINC_OK when every proof has its outcome; ZINC_ERR_NULL, ZINC_ERR_PANIC (a shape the reference
+ * panics on, found on the first member that has it before any device work) and ZINC_ERR_DEVICE are the call's own. */
+int32_t zinc_verifier_verify_batch(const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                                   uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c, uint32_t n_instances,
+                                   zinc_transcript *const *transcripts, const uint64_t *moduli, const uint32_t *limbs,
+                                   int32_t device, const uint64_t *msgs1, const uint64_t *msgs2, const uint64_t *v_s,
+                                   const uint8_t *const *roots, const size_t *n_roots, const uint64_t *v,
+                                   const uint8_t *const *pcs_proofs, const size_t *pcs_proof_lens, int32_t *results_out,
+                                   char *messages_out, size_t message_cap);
+
 /* ZincVerifier (src/zinc/verifier.rs): SpartanVerifier::verify (:105-139), and with with_pcs != 0 also
  * verify_pcs_proof (:221-273: RaaCode::new from the transcript, MultilinearZip::verify, the matrix MLEs at
  * (r_x, r_y) on the device, the final equation) -- Verifier::verify without its draw_random_field check (with it:

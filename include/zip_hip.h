@@ -49,7 +49,8 @@ extern "C" {
  * zip_sumcheck_batch_counts: many small sumchecks in one launch, beside the one-at-a-time form that is unchanged.  So are the
  * zip_ccs_batch_* entry points: the Spartan tables of many proofs of one circuit, beside zip_ccs.  So are
  * zip_batch_commit_codes, zip_batch_open_eval_fields, zip_batch_open_fields and zip_batch_codes_counts: a batch whose
- * members have their own code and field, beside the shared-code batch that is unchanged.) */
+ * members have their own code and field, beside the shared-code batch that is unchanged.  So are zip_batch_verify_codes,
+ * zip_batch_verify_codes_counts and zip_ccs_batch_eval_matrices: the verifier's side of such a batch.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -356,10 +357,10 @@ int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols
  * reached the device, the members they committed, and calls of the two _fields entry points that reached the device.
  * Any pointer may be NULL.
  *
- * Not part of this family: a batched verifier with a code and a field per member (zip_batch_verify would need the
- * members' permutations in its two encode kernels and their fields in all five: the natural follow-up; until then such
- * proofs are verified one at a time with zip_verify); codewords of 16384 and above; more than one proximity test in a
- * batch; row-sharded contexts. */
+ * The verifier's side of this family, zip_batch_verify_codes, is declared with zip_batch_verify below.
+ *
+ * Not part of this family: codewords above 8192 in the commit (the verifier serves them up to 16384); more than one
+ * proximity test in a batch; row-sharded contexts. */
 int32_t zip_batch_commit_codes(zip_ctx *ctx, const int64_t *evals, size_t n_evals, uint32_t n_polys, zip_mem_kind evals_kind,
                                const uint32_t *perms1, const uint32_t *perms2, uint8_t *roots_out, zip_batch **out);
 int32_t zip_batch_open_eval_fields(zip_batch *b, const uint64_t *q0_mont, const zip_field *const *fields, uint64_t *rows_out,
@@ -451,6 +452,46 @@ int32_t zip_batch_verify(zip_ctx *ctx, uint32_t n_polys, const uint8_t *roots, c
                          uint32_t n_cols, const uint64_t *q0_mont, const uint64_t *q1_mont, const uint64_t *evals_mont,
                          const zip_field *field, zip_verify_report *reports);
 uint64_t zip_batch_verify_calls(void);
+
+/* zip_batch_verify_codes: zip_batch_verify for the proofs of a Zinc batch (ZincVerifier::verify_batch): member i has its
+ * own RAA code, its own field and its own stream buffer, and shares the ctx's geometry with the others and nothing else.
+ *   ctx         geometry, stream and pools; its own permutations are not read (as in zip_batch_commit_codes)
+ *   perms1, perms2   HOST, n_polys * codeword_len entries each, member-major, as for zip_batch_commit_codes.  Every slice
+ *               is tested as zip_ctx_create tests a permutation -- the encode kernel indexes with these values
+ *   fields      HOST, n_polys pointers, one `limbs` shared, each its own modulus (the rules of zip_batch_open_fields);
+ *               slice i of q0_mont, q1_mont and evals_mont holds Montgomery limbs of fields[i]
+ *   proofs, proof_lens   HOST arrays of n_polys entries: ONE pointer and ONE length per member -- the members are
+ *               independent proofs with their own buffers.  proofs_kind HOST: stream i is copied into its slot of one
+ *               pooled device block.  DEVICE: it is read in place and must be 8-byte aligned.
+ *               A member with proof_lens[i] < zip_proof_len gets ZIP_VERIFY_MALFORMED with zero counts and never reaches
+ *               the device (its pointer is not looked at); every other member is still verified: the members share no
+ *               transcript, so none comes "after" another.
+ *   roots, coeffs, cols, q0_mont, q1_mont, evals_mont   HOST, polynomial-major, as in zip_batch_verify
+ *   reports     HOST, n_polys entries.  reports[i] equals, field by field, what zip_verify returns for member i's slices on
+ *               a ctx created with member i's permutations and fields[i], for every input, both documented deviations
+ *               included.  A batch may mix moduli with and without the signed-modulus quirk.
+ * The same five kernel launches as zip_batch_verify whatever n_polys is (the member is a grid dimension; what differs
+ * between members is one entry of a device array read through the scalar cache), one device-to-host copy of the
+ * reports, one synchronisation.
+ * Constraints: zip_batch_verify's (unsharded ctx, one proximity test, codeword_len <= 16384 -- not the 8192 of
+ * zip_batch_commit_codes: the encode kernel reads its permutations from memory --, 1 <= n_polys <= 65535,
+ * n_polys * n_cols within 32 bits).
+ * Errors, all before anything reaches the device, in this order: ZIP_ERR_NULL (ctx, roots, proofs, proof_lens, reports,
+ * evals_mont, cols when n_cols != 0, perms1, perms2); ZIP_ERR_INVALID_PARAM (n_polys, row-sharded ctx);
+ * ZIP_ERR_UNSUPPORTED (more than one proximity test, codeword_len above 16384, n_polys * n_cols beyond 32 bits);
+ * ZIP_ERR_NULL (fields, a fields[i]); ZIP_ERR_INVALID_PARAM (limbs outside {2, 3, 4}, differing limb counts, a modulus
+ * that is even or 1); ZIP_ERR_NULL (a needed coeffs / q0_mont / q1_mont); ZIP_ERR_INVALID_PARAM (a column index >=
+ * codeword_len); ZIP_ERR_NULL (the proofs[i] of a member that is long enough); ZIP_ERR_INVALID_PARAM (a misaligned DEVICE
+ * stream); last, ZIP_ERR_INVALID_PARAM for a slice that is not a permutation of [0, codeword_len).
+ * zip_batch_verify_codes_counts: process-wide, monotonic, kept like zip_batch_codes_counts: calls that reached the
+ * device, and the members they verified (short members are not among them).  Either pointer may be NULL.
+ * Not part of this: more than one proximity test in a batch; batches on zip_mctx. */
+int32_t zip_batch_verify_codes(zip_ctx *ctx, uint32_t n_polys, const uint32_t *perms1, const uint32_t *perms2,
+                               const uint8_t *roots, const uint8_t *const *proofs, const size_t *proof_lens,
+                               zip_mem_kind proofs_kind, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols,
+                               const uint64_t *q0_mont, const uint64_t *q1_mont, const uint64_t *evals_mont,
+                               const zip_field *const *fields, zip_verify_report *reports);
+void zip_batch_verify_codes_counts(uint64_t *calls, uint64_t *members);
 
 /* ---- sumcheck prover --------------------------------------------
  * IPForMLSumcheck::prove_round (src/sumcheck/prover.rs:62-180) for the two combination functions
@@ -664,7 +705,7 @@ int32_t zip_ccs_download(zip_ccs *c, zip_ccs_table_kind which, uint32_t index, u
  * them.  A zip_ccs_batch holds the matrices ONCE, as the integers they are -- CSR as given and the CSC form, built at
  * creation, both with int64 values; no Montgomery copy of them exists, a kernel maps a value into the instance's field
  * where it uses it -- and the tables of up to `capacity` proofs.  Every call below launches a number of kernels that does
- * not depend on n (the instance is a grid dimension): set_z 2, eq_tables 1, second_tables 3.
+ * not depend on n (the instance is a grid dimension): set_z 2, eq_tables 1, second_tables 3, eval_matrices 3.
  *   zip_ccs_batch_create   t 1..7, s 1..16 (the bound of zip_sumcheck_prove_batch, which these tables feed), limbs 2..4,
  *                          capacity 1..65535.  Device memory: capacity * (t + 4) tables of 2^s * limbs * 8 bytes, and
  *                          capacity * 2^s * 8 bytes for the z of a HOST set_z; ZIP_ERR_ALLOC when that cannot be had.
@@ -689,6 +730,18 @@ int32_t zip_ccs_download(zip_ccs *c, zip_ccs_table_kind which, uint32_t index, u
  *                          one synchronisation.
  *                          Both: ZIP_ERR_NULL for a NULL argument, then ZIP_ERR_INVALID_PARAM for slot > 1 and for a
  *                          handle on which set_z has not run.
+ *   zip_ccs_batch_eval_matrices  the verifier's V_xy: per instance i, in fields[i], mle[M_k](r_x_i, r_y_i) for every matrix
+ *                          k -- what zip_ccs_eval_matrices gives on a zip_ccs of that field.  r_x, r_y: HOST, n * s * limbs
+ *                          each, instance-major; v_xy_out: HOST, n * t * limbs.  The verifier has no z: the call takes
+ *                          the fields itself and does not need set_z to have run.  It builds eq(r_x_i) and eq(r_y_i) in
+ *                          the two eq slots and sums over the integer CSR, every value mapped into the instance's field
+ *                          where it is used.  One upload, three launches whatever n is, one copy back, one
+ *                          synchronisation.  It REPLACES what a previous set_z and the calls after it left, as set_z
+ *                          does: afterwards the table calls (eq_tables, second_tables, table, download) answer
+ *                          ZIP_ERR_INVALID_PARAM until the next set_z.
+ *                          Errors before anything reaches the device, in set_z's order: ZIP_ERR_NULL (b, fields, r_x,
+ *                          r_y, v_xy_out, a fields[i]); ZIP_ERR_INVALID_PARAM (n outside 1..capacity; a field whose limbs
+ *                          differ from the handle's; a modulus that is even or 1).
  *   zip_ccs_batch_table    device pointer of a table of 2^s elements of `instance` (< n), which / index as for
  *                          zip_ccs_table; valid until the next call that rebuilds it or zip_ccs_batch_free.  set_z and
  *                          eq_tables only enqueue their work; this call (and download, and second_tables) waits for what
@@ -696,9 +749,10 @@ int32_t zip_ccs_download(zip_ccs *c, zip_ccs_table_kind which, uint32_t index, u
  *                          ZIP_ERR_INVALID_PARAM: set_z has not run, instance >= n, a table that has not been built.
  *   zip_ccs_batch_download the same table copied to the HOST (tests)
  *   zip_ccs_batch_counts   process-wide, monotonic, kept like zip_sumcheck_batch_counts: kernel launches of set_z /
- *                          eq_tables / second_tables so far, and the instances handed to set_z.  Any pointer may be NULL.
- * Calls on one handle are serialised inside the library.  Not part of this: the verifier's V_xy (zip_ccs_eval_matrices)
- * in a batch, a circuit per instance, s above 16.  Additive: the ABI version stays 3. */
+ *                          eq_tables / second_tables / eval_matrices so far, and the instances handed to set_z.  Any
+ *                          pointer may be NULL.
+ * Calls on one handle are serialised inside the library.  Not part of this: a circuit per instance, s above 16.
+ * Additive: the ABI version stays 3. */
 typedef struct zip_ccs_batch zip_ccs_batch;
 int32_t zip_ccs_batch_create(int32_t device, const zip_sparse_matrix *matrices, uint32_t t, uint32_t s, uint32_t limbs,
                              uint32_t capacity, zip_ccs_batch **out);
@@ -711,6 +765,8 @@ int32_t zip_ccs_batch_second_tables(zip_ccs_batch *b, const uint64_t *r_x, const
 int32_t zip_ccs_batch_table(zip_ccs_batch *b, uint32_t instance, zip_ccs_table_kind which, uint32_t index,
                             const uint64_t **table_dev);
 int32_t zip_ccs_batch_download(zip_ccs_batch *b, uint32_t instance, zip_ccs_table_kind which, uint32_t index, uint64_t *out);
+int32_t zip_ccs_batch_eval_matrices(zip_ccs_batch *b, const zip_field *const *fields, uint32_t n, const uint64_t *r_x,
+                                    const uint64_t *r_y, uint64_t *v_xy_out);
 void zip_ccs_batch_counts(uint64_t *kernel_launches, uint64_t *instances);
 
 /* Diagnostic: FieldMap for Int<4> (src/conversion.rs:86-100) of n arbitrary 256-bit values, as the

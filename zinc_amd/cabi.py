@@ -38,8 +38,9 @@ EXPORTED_SYMBOLS = (
     "zip_ccs_second_table", "zip_ccs_table", "zip_ccs_download", "zip_ccs_eval_matrices",
     "zip_ccs_batch_create", "zip_ccs_batch_free", "zip_ccs_batch_last_error", "zip_ccs_batch_set_z", "zip_ccs_batch_eq_tables",
     "zip_ccs_batch_second_tables", "zip_ccs_batch_table", "zip_ccs_batch_download", "zip_ccs_batch_counts",
+    "zip_ccs_batch_eval_matrices",
     "zip_batch_commit", "zip_batch_size", "zip_batch_free", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open",
-    "zip_batch_verify", "zip_batch_verify_calls",
+    "zip_batch_verify", "zip_batch_verify_calls", "zip_batch_verify_codes", "zip_batch_verify_codes_counts",
     "zip_batch_commit_codes", "zip_batch_open_eval_fields", "zip_batch_open_fields", "zip_batch_codes_counts",
     "zip_prime_test_base2", "zip_get_prime", "zip_prime_launch_counts",
 )
@@ -225,6 +226,11 @@ def lib():
     L.zip_batch_verify.argtypes = [vp, C.c_uint32, u8p, vp, C.c_int, C.c_size_t, i64p, u32p, C.c_uint32, u64p, u64p, u64p,
                                    C.POINTER(ZipField), C.POINTER(VerifyReport)]
     L.zip_batch_verify.restype = C.c_int32
+    L.zip_batch_verify_codes.argtypes = [vp, C.c_uint32, u32p, u32p, u8p, vp, vp, C.c_int, i64p, u32p, C.c_uint32, u64p, u64p, u64p,
+                                         vp, C.POINTER(VerifyReport)]
+    L.zip_batch_verify_codes.restype = C.c_int32
+    L.zip_batch_verify_codes_counts.argtypes = [C.POINTER(C.c_uint64)] * 2
+    L.zip_batch_verify_codes_counts.restype = None
     L.zip_batch_verify_calls.argtypes = []
     L.zip_batch_verify_calls.restype = C.c_uint64
     L.zip_mle_eval.argtypes = [vp, i64p, C.c_int, u64p, u64p, C.POINTER(ZipField), u64p]
@@ -280,6 +286,8 @@ def lib():
     L.zip_ccs_batch_second_tables.argtypes = [vp, u64p, u64p, u64p]
     L.zip_ccs_batch_table.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(vp)]
     L.zip_ccs_batch_download.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32, u64p]
+    L.zip_ccs_batch_eval_matrices.argtypes = [vp, vp, C.c_uint32, u64p, u64p, u64p]
+    L.zip_ccs_batch_eval_matrices.restype = C.c_int32
     L.zip_ccs_batch_counts.argtypes = [C.POINTER(C.c_uint64)] * 2
     L.zip_ccs_batch_counts.restype = None
     for fn in ("zip_ccs_batch_create", "zip_ccs_batch_set_z", "zip_ccs_batch_eq_tables", "zip_ccs_batch_second_tables",
@@ -643,6 +651,49 @@ class ZipContext:
         return [{"verdict": r.verdict, "column": r.column, "bad_merkle_paths": r.bad_merkle_paths,
                  "malformed_paths": r.malformed_paths} for r in reps]
 
+    def batch_verify_codes(self, perms1_2d, perms2_2d, roots, proofs, coeffs, cols, q0_mont, q1_mont, evals_mont, fields,
+                           proof_lens=None):
+        """zip_batch_verify_codes: batch_verify with one RAA code, one field and one stream buffer per member.
+        perms1_2d / perms2_2d: [n, codeword_len] uint32 (this ctx's own permutations are not read); proofs: a list of n
+        numpy uint8 arrays, or of n CUDA tensors read in place; fields: n ZipField of one limb count; the other arrays as
+        for batch_verify, slice i in Montgomery form of fields[i].  proof_lens: the bytes to treat as available per
+        member (default: all of each).  -> a list of n report dicts."""
+        roots_c = np.ascontiguousarray(roots, dtype=np.uint8)
+        cols_c = np.ascontiguousarray(cols, dtype=np.uint32)
+        n_polys, n_cols = cols_c.shape
+        limbs = fields[0].limbs
+        p1 = np.ascontiguousarray(perms1_2d, dtype=np.uint32)
+        p2 = np.ascontiguousarray(perms2_2d, dtype=np.uint32)
+        coeffs_c = None if coeffs is None else np.ascontiguousarray(coeffs, dtype=np.int64)
+        q0 = None if q0_mont is None else np.ascontiguousarray(q0_mont, dtype=np.uint64)
+        q1 = None if q1_mont is None else np.ascontiguousarray(q1_mont, dtype=np.uint64)
+        ev = np.ascontiguousarray(evals_mont, dtype=np.uint64)
+        assert len(proofs) == n_polys and len(fields) == n_polys
+        assert p1.size == n_polys * self.codeword_len and p2.size == n_polys * self.codeword_len
+        assert roots_c.size == n_polys * self.num_rows * 32 and ev.size == n_polys * limbs
+        assert coeffs_c is None or coeffs_c.size == n_polys * self.num_rows
+        assert q0 is None or q0.size == n_polys * self.num_rows * limbs
+        assert q1 is None or q1.size == n_polys * self.row_len * limbs
+        host = isinstance(proofs[0], np.ndarray)
+        keep = [np.ascontiguousarray(p, dtype=np.uint8) for p in proofs] if host else list(proofs)
+        ptrs = [_ptr(p)[0] for p in keep]
+        lens = [p.size if host else p.numel() * p.element_size() for p in keep]
+        if proof_lens is not None:
+            assert all(a <= b for a, b in zip(proof_lens, lens))
+            lens = list(proof_lens)
+        pa = (C.c_void_p * n_polys)(*ptrs)
+        la = (C.c_size_t * n_polys)(*lens)
+        fa = Batch._field_ptrs(fields)
+        reps = (VerifyReport * n_polys)()
+        rc = lib().zip_batch_verify_codes(self._h, n_polys, p1.ctypes.data, p2.ctypes.data, roots_c.ctypes.data,
+                                          C.cast(pa, C.c_void_p), C.cast(la, C.c_void_p), MEM_HOST if host else MEM_DEVICE,
+                                          None if coeffs_c is None else coeffs_c.ctypes.data, cols_c.ctypes.data, n_cols,
+                                          None if q0 is None else q0.ctypes.data, None if q1 is None else q1.ctypes.data,
+                                          ev.ctypes.data, C.cast(fa, C.c_void_p), reps)
+        self._check(rc, "zip_batch_verify_codes")
+        return [{"verdict": r.verdict, "column": r.column, "bad_merkle_paths": r.bad_merkle_paths,
+                 "malformed_paths": r.malformed_paths} for r in reps]
+
     def mle_eval(self, evals, q0_mont, q1_mont, field: ZipField):
         ptr, kind = _ptr(evals)
         q0 = None if q0_mont is None else np.ascontiguousarray(q0_mont, dtype=np.uint64)
@@ -1000,6 +1051,14 @@ def batch_verify_calls() -> int:
     return lib().zip_batch_verify_calls()
 
 
+def batch_verify_codes_counts():
+    """zip_batch_verify_codes_counts: (zip_batch_verify_codes calls that reached the device, members they verified) in this
+    process so far"""
+    a, b = C.c_uint64(), C.c_uint64()
+    lib().zip_batch_verify_codes_counts(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
 def batch_codes_counts():
     """zip_batch_codes_counts: (zip_batch_commit_codes calls that reached the device, members they committed, calls of the
     two _fields opens that reached the device) in this process so far"""
@@ -1296,6 +1355,21 @@ class CcsBatch:
         self._check(lib().zip_ccs_batch_second_tables(self._h, r_x.ctypes.data, gamma.ctypes.data, vs.ctypes.data),
                     "zip_ccs_batch_second_tables")
         return vs
+
+    def eval_matrices(self, fields, r_x, r_y):
+        """zip_ccs_batch_eval_matrices: the verifier's V_xy.  fields: n ZipField; r_x, r_y: [n, s, limbs] Montgomery limbs
+        of fields[i].  Returns [n, t, limbs].  Needs no set_z and replaces what one left: the table calls are refused
+        until the next set_z."""
+        n = len(fields)
+        r_x = np.ascontiguousarray(r_x, dtype=np.uint64)
+        r_y = np.ascontiguousarray(r_y, dtype=np.uint64)
+        assert r_x.shape == (n, self.s, self.limbs) and r_y.shape == (n, self.s, self.limbs)
+        fa = (C.POINTER(ZipField) * max(n, 1))(*[C.pointer(f) for f in fields])
+        out = np.zeros((n, self.t, self.limbs), dtype=np.uint64)
+        self._check(lib().zip_ccs_batch_eval_matrices(self._h, C.cast(fa, C.c_void_p), n, r_x.ctypes.data, r_y.ctypes.data,
+                                                      out.ctypes.data), "zip_ccs_batch_eval_matrices")
+        self.n = 0
+        return out
 
     def table(self, instance, which, index=0) -> int:
         """Device address of a table of 2^s field elements of one proof."""

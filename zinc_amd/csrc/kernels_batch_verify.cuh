@@ -50,15 +50,17 @@ __device__ __forceinline__ void batch_enc_load_wire(EncElem<L, FIELD> &x, const 
     }
 }
 
+// polynomial blockIdx.x: its stream starts at `stream`, its code is (perm1, perm2), its field f
 template <int L, bool FIELD>
-__global__ void __launch_bounds__(1024) batch_encode_kernel(BatchEncodeArgs a, FieldDev<L> f) {
+__device__ __forceinline__ void batch_encode_body(const BatchEncodeArgs &a, const FieldDev<L> &f, const uint8_t *stream,
+                                                  const uint32_t *perm1, const uint32_t *perm2) {
     extern __shared__ __align__(16) unsigned char benc_smem[];
     using El = EncElem<L, FIELD>;
     El *tot = reinterpret_cast<El *>(benc_smem);  // [blockDim.x]
     const uint32_t T = blockDim.x, tid = threadIdx.x, b = blockIdx.x, cw = a.cw;
-    const uint64_t *in = reinterpret_cast<const uint64_t *>(a.proofs + (size_t)b * a.stream_bytes + a.in_at);
+    const uint64_t *in = reinterpret_cast<const uint64_t *>(stream + a.in_at);
     const bool ovf = raa_encode_row<L, FIELD>([&](uint32_t c, El &x) { batch_enc_load_wire<L, FIELD>(x, in + (size_t)c * L); },
-                                              a.row_len, cw, a.perm1, a.perm2, a.tmp + (size_t)b * cw * L,
+                                              a.row_len, cw, perm1, perm2, a.tmp + (size_t)b * cw * L,
                                               a.out + (size_t)b * cw * L, f, tot);
     if constexpr (!FIELD) {
         const int any = __syncthreads_or(ovf ? 1 : 0);
@@ -103,6 +105,38 @@ __global__ void __launch_bounds__(1024) batch_encode_kernel(BatchEncodeArgs a, F
     }
 }
 
+template <int L, bool FIELD>
+__global__ void __launch_bounds__(1024) batch_encode_kernel(BatchEncodeArgs a, FieldDev<L> f) {
+    batch_encode_body<L, FIELD>(a, f, a.proofs + (size_t)blockIdx.x * a.stream_bytes, a.perm1, a.perm2);
+}
+
+// ---------------------------------------------------------------------------------------
+// One code and one field per polynomial (zip_batch_verify_codes): what differs between the members of a batch of Zinc
+// proofs is entry b of a device array.  The entry sits at a wave-uniform address (blockIdx.x here, blockIdx.y in the
+// column kernel), so its field constants and pointers are read through the scalar cache, as batch_combine_fields_kernel
+// and kernels_spartan_batch.cuh read theirs.  The args' proofs / stream_bytes / perm1 / perm2 / quirk are not read.
+// ---------------------------------------------------------------------------------------
+template <int FL>
+struct BatchVerifyMember {
+    FieldDev<FL> f, fq;            // the member's field, and that of 2^256 - q (= f unless quirk)
+    const uint8_t *stream;         // where its proof stream starts (8-byte aligned)
+    const uint32_t *perm1, *perm2; // its RAA code: codeword_len entries each
+    uint32_t quirk;                // 1: the modulus is a negative Int<4> in the reference (see opening_terms)
+};
+
+// FIELD: L == FL and the member's field encodes; else encode_wide, which reads no field (L = 8 for every FL)
+template <int L, bool FIELD, int FL>
+__global__ void __launch_bounds__(1024) batch_encode_codes_kernel(BatchEncodeArgs a, const BatchVerifyMember<FL> *__restrict__ inst) {
+    const BatchVerifyMember<FL> &m = inst[blockIdx.x];
+    if constexpr (FIELD) {
+        static_assert(L == FL, "encode_f runs in the member's field");
+        batch_encode_body<L, true>(a, m.f, m.stream, m.perm1, m.perm2);
+    } else {
+        const FieldDev<L> unused{};
+        batch_encode_body<L, false>(a, unused, m.stream, m.perm1, m.perm2);
+    }
+}
+
 // ---------------------------------------------------------------------------------------
 // Every (polynomial, opening): hash the paths, form the two column inner products, compare them with the encoded
 // combined rows.  A 256-thread workgroup serves ONE polynomial (blockIdx.y) and
@@ -127,8 +161,10 @@ struct BatchVerifyColsArgs {
     uint32_t *flags, *bad_merkle, *malformed;  // [n_polys][n_cols]
 };
 
+// polynomial blockIdx.y: its stream starts at `stream`; f, fq and quirk are its field's
 template <int FL>
-__global__ void __launch_bounds__(256) batch_verify_columns_kernel(BatchVerifyColsArgs a, FieldDev<FL> f, FieldDev<FL> fq) {
+__device__ __forceinline__ void batch_verify_columns_body(const BatchVerifyColsArgs &a, const FieldDev<FL> &f, const FieldDev<FL> &fq,
+                                                          bool quirk, const uint8_t *stream) {
     constexpr int W = 6 + FL;
     __shared__ uint64_t wave_sum[4][W];
     __shared__ uint32_t s_bad[256], s_mal[256];
@@ -150,7 +186,7 @@ __global__ void __launch_bounds__(256) batch_verify_columns_kernel(BatchVerifyCo
         col = a.cols[(size_t)b * a.n_cols + ci];
         const uint32_t d = a.depth, rec_bytes = 8 + 32 * d;
         const size_t col_bytes = (size_t)R * (32 + rec_bytes);
-        const uint8_t *base = a.proofs + (size_t)b * a.stream_bytes + a.openings_at + (size_t)ci * col_bytes;
+        const uint8_t *base = stream + a.openings_at + (size_t)ci * col_bytes;
         const int64_t *coeffs = a.coeffs ? a.coeffs + (size_t)b * R : nullptr;
         const uint64_t *q0 = a.q0 ? a.q0 + (size_t)b * R * FL : nullptr;
         const uint32_t *roots = a.roots + (size_t)b * R * 8;
@@ -158,7 +194,7 @@ __global__ void __launch_bounds__(256) batch_verify_columns_kernel(BatchVerifyCo
         for (uint32_t r = r0; r < R; r += 256) {
             uint64_t v[4];
             fe_load<4>(v, reinterpret_cast<const uint64_t *>(base + (size_t)r * 32));
-            opening_terms<FL, true>(v, coeffs ? coeffs + r : nullptr, q0 ? q0 + (size_t)r * FL : nullptr, f, fq, a.quirk != 0, si, sf);
+            opening_terms<FL, true>(v, coeffs ? coeffs + r : nullptr, q0 ? q0 + (size_t)r * FL : nullptr, f, fq, quirk, si, sf);
             const uint64_t *rec = reinterpret_cast<const uint64_t *>(base + (size_t)R * 32 + (size_t)r * rec_bytes);
             const MerkleRecord m = check_merkle_record(v, rec, d, col, roots + (size_t)r * 8);
             n_mal += m == kMerkleMalformed;
@@ -198,6 +234,19 @@ __global__ void __launch_bounds__(256) batch_verify_columns_kernel(BatchVerifyCo
     a.flags[slot] = column_flags<FL>(si, sf, a.enc_u ? a.enc_u + at * 8 : nullptr, 8, a.enc_f + at * FL);
     a.bad_merkle[slot] = s_bad[o];
     a.malformed[slot] = s_mal[o];
+}
+
+template <int FL>
+__global__ void __launch_bounds__(256) batch_verify_columns_kernel(BatchVerifyColsArgs a, FieldDev<FL> f, FieldDev<FL> fq) {
+    batch_verify_columns_body<FL>(a, f, fq, a.quirk != 0, a.proofs + (size_t)blockIdx.y * a.stream_bytes);
+}
+
+// zip_batch_verify_codes: the quirk is the member's, decided at run time as kQuirkPerMember is in batch_combine_body
+template <int FL>
+__global__ void __launch_bounds__(256) batch_verify_columns_codes_kernel(BatchVerifyColsArgs a,
+                                                                          const BatchVerifyMember<FL> *__restrict__ inst) {
+    const BatchVerifyMember<FL> &m = inst[blockIdx.y];
+    batch_verify_columns_body<FL>(a, m.f, m.fq, m.quirk != 0, m.stream);
 }
 
 // ---------------------------------------------------------------------------------------

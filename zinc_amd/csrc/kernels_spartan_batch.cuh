@@ -7,6 +7,7 @@
 //   ccs_batch_eq_kernel       build_eq_x_r from two half tables built in LDS          sumcheck/utils.rs:102-177
 //   ccs_batch_second_kernel   sum_k gamma_i^k * compute_eval_table_sparse(M_k, eq)    sparse_matrix.rs:165-182 + prover.rs:279-290
 //   ccs_batch_vs_kernel       V_s[k] = <M_k z_i, eq(r_x)>, one workgroup each         prover.rs:330-347
+//   ccs_batch_eval_matrices_kernel  the verifier's V_xy[k] = mle[M_k](r_x_i, r_y_i)   verifier.rs (zip_ccs_eval_matrices)
 //
 // The matrices are held ONCE, as the int64 values the caller gave (CSR, and the CSC form csc_fill_kernel<1> makes of
 // them): a kernel maps a value into the instance's field where it uses it (field_from_i64 with the instance's FieldDev
@@ -218,6 +219,58 @@ __global__ void __launch_bounds__(kCcsBatchVsThreads) ccs_batch_vs_kernel(const 
         __syncthreads();
     }
     if (tid < FL) vs[((size_t)blockIdx.y * gridDim.x + k) * FL + tid] = red[tid];
+}
+
+// grid (t, n): out[(i * t + k)] = mle[M_k](r_x_i, r_y_i) = sum_rows eq0[row] (x) sum_e phi_i(vals[k][e]) (x) eq1[col[e]], the
+// verifier's V_xy (zinc/verifier.rs: evaluate the matrices' MLEs at the two sumcheck points; matrix_eval_partials_kernel
+// for one field).  eq slot 0 holds eq(r_x_i), slot 1 eq(r_y_i).  One workgroup walks the n_rows[k] rows of the integer CSR,
+// a thread per row, and folds its threads' sums in LDS as ccs_batch_vs_kernel does; field additions commute, so the
+// value does not depend on the order.
+template <int FL>
+__global__ void __launch_bounds__(kCcsBatchVsThreads) ccs_batch_eval_matrices_kernel(CcsBatchMats M,
+                                                                                     const CcsBatchInst<FL> *__restrict__ inst,
+                                                                                     uint64_t *__restrict__ out) {
+    __shared__ uint64_t red[kCcsBatchVsThreads * FL];
+    const CcsBatchInst<FL> &a = inst[blockIdx.y];
+    const FieldDev<FL> f = a.f;
+    const uint64_t quirk_mod = a.quirk_mod;
+    const uint32_t tid = threadIdx.x, k = blockIdx.x;
+    const uint64_t *eq_x = a.eq[0], *eq_y = a.eq[1];
+    const uint32_t *row_ptr = M.row_ptr[k], *col_idx = M.col_idx[k];
+    const int64_t *vals = M.vals[k];
+    const uint32_t n_rows = M.n_rows[k] < M.m ? M.n_rows[k] : M.m;
+    uint64_t acc[FL];
+#pragma unroll
+    for (int i = 0; i < FL; i++) acc[i] = 0;
+    for (uint32_t row = tid; row < n_rows; row += kCcsBatchVsThreads) {
+        uint64_t in[FL];
+#pragma unroll
+        for (int i = 0; i < FL; i++) in[i] = 0;
+        for (uint32_t e = row_ptr[row]; e < row_ptr[row + 1]; e++) {
+            uint64_t v[FL], y[FL], t[FL];
+            field_from_i64<FL>(vals[e], f, quirk_mod, v);
+            fe_load<FL>(y, eq_y + (size_t)col_idx[e] * FL);
+            mont_mul<FL>(y, v, f, t);
+            fe_add<FL>(in, t, f);
+        }
+        uint64_t x[FL], t[FL];
+        fe_load<FL>(x, eq_x + (size_t)row * FL);
+        mont_mul<FL>(x, in, f, t);
+        fe_add<FL>(acc, t, f);
+    }
+    fe_store<FL>(red + (size_t)tid * FL, acc);
+    __syncthreads();
+    for (uint32_t w = kCcsBatchVsThreads / 2; w > 0; w >>= 1) {
+        if (tid < w) {
+            uint64_t p[FL], q[FL];
+            fe_load<FL>(p, red + (size_t)tid * FL);
+            fe_load<FL>(q, red + (size_t)(tid + w) * FL);
+            fe_add<FL>(p, q, f);
+            fe_store<FL>(red + (size_t)tid * FL, p);
+        }
+        __syncthreads();
+    }
+    if (tid < FL) out[((size_t)blockIdx.y * gridDim.x + k) * FL + tid] = red[tid];
 }
 
 }  // namespace zipk

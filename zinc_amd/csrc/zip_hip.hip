@@ -320,7 +320,7 @@ struct zip_ccs_batch {
     CcsBatchMats mats{};     // device pointers: CSR as uploaded, CSC built once at creation; int64 values in both
     uint64_t *tables = nullptr;  // capacity * (t + 4) tables of m elements: per instance z_f, mz[0..t), eq[0], eq[1], second
     int64_t *z_d = nullptr;      // the z vectors of a HOST set_z, one after the other (capacity * m entries)
-    void *args_d = nullptr;      // n CcsBatchInst<fl>
+    void *args_d = nullptr;      // n CcsBatchInst<fl>; zip_ccs_batch_eval_matrices: then every r_x, then every r_y
     uint64_t *chal_d = nullptr;  // capacity * (s + 1) elements: r of eq_tables, or r_x followed by every gamma
     uint64_t *vs_d = nullptr;    // capacity * t elements
     // what the asynchronous uploads read: kept until the stream has passed them (the next call that refills them waits)
@@ -523,7 +523,7 @@ struct Scratch {
 // buffer.  The staging buffer is reused by the next call, so every caller synchronises the
 // stream before returning (they all do: host inputs must be consumed before we return).
 struct SmallInputs {
-    static constexpr int N = 6;
+    static constexpr int N = 7;
     const void *src[N] = {};
     size_t bytes[N] = {};
     size_t off[N] = {};
@@ -1987,6 +1987,116 @@ int32_t run_batch_verify_fl(zip_ctx *ctx, const VerifyIn &in, const HostField &h
     return ZIP_OK;
 }
 
+// ---- zip_batch_verify_codes: the same five launches with a code and a field per member (BatchVerifyMember) ----
+// Process-wide (zip_batch_verify_codes_counts): calls that reached the device, and the members they verified
+std::atomic<uint64_t> g_batch_verify_codes_calls{0}, g_batch_verify_codes_members{0};
+
+// BatchVerifyMember<FL>[k]: member i's field, the start of its stream and its slices of the uploaded permutations
+template <int FL>
+void batch_fill_verify_members(const std::vector<HostField> &hf, const std::vector<const uint8_t *> &streams, const uint32_t *perms1_d,
+                               const uint32_t *perms2_d, uint32_t cw, std::vector<unsigned char> *inst) {
+    inst->assign(hf.size() * sizeof(BatchVerifyMember<FL>), 0);
+    BatchVerifyMember<FL> *m = reinterpret_cast<BatchVerifyMember<FL> *>(inst->data());
+    for (size_t i = 0; i < hf.size(); i++) {
+        const VerifyField<FL> vf = verify_field<FL>(hf[i]);
+        m[i].f = vf.fd;
+        m[i].fq = vf.fq;
+        m[i].quirk = vf.quirk;
+        m[i].stream = streams[i];
+        m[i].perm1 = perms1_d + i * cw;
+        m[i].perm2 = perms2_d + i * cw;
+    }
+}
+
+// in.proofs_d / in.stream_bytes are not read: the streams are the entries' (inst_d: BatchVerifyMember<FL>[in.n_polys])
+template <int FL>
+int32_t run_batch_verify_codes_fl(zip_ctx *ctx, const VerifyIn &in, const void *inst_d, zip_verify_report *reports) {
+    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len, M = ctx->p.m_limbs;
+    const uint32_t n_cols = in.n_cols, B = in.n_polys;
+    const bool single = R == 1;
+    const size_t u_bytes = single ? 0 : (size_t)C * M * 8;
+    const size_t cols_bytes = (size_t)n_cols * column_bytes(ctx);
+    const BatchVerifyMember<FL> *inst = static_cast<const BatchVerifyMember<FL> *>(inst_d);
+    Scratch enc_u(ctx), enc_f(ctx), tmp(ctx), misc(ctx);
+    int32_t rc;
+    if (!single && (rc = enc_u.get((size_t)B * cw * M * 8))) return rc;
+    if ((rc = enc_f.get((size_t)B * cw * FL * 8))) return rc;
+    if ((rc = tmp.get((size_t)B * cw * (single ? FL : M) * 8))) return rc;
+    // misc: as in run_batch_verify_fl
+    const size_t per_opening = (size_t)B * n_cols * 4;
+    const size_t misc_bytes = (size_t)B * (sizeof(zip_verify_report) + sizeof(VerifyHead)) + 3 * per_opening;
+    if ((rc = misc.get(misc_bytes))) return rc;
+    zip_verify_report *reports_d = misc.as<zip_verify_report>();
+    VerifyHead *head_d = reinterpret_cast<VerifyHead *>(reports_d + B);
+    uint32_t *flags_d = reinterpret_cast<uint32_t *>(head_d + B), *bad_d = flags_d + (size_t)B * n_cols,
+             *mal_d = bad_d + (size_t)B * n_cols;
+    BatchEncodeArgs e{};
+    e.row_len = C;
+    e.cw = cw;
+    e.tmp = tmp.as<uint64_t>();
+    e.head = head_d;
+    if (!single) {  // encode_wide(u')
+        const EncodeShape s = encode_shape<8, false>(cw);
+        auto kern = batch_encode_codes_kernel<8, false, FL>;
+        if ((rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), s.lds))) return rc;
+        e.in_at = 0;
+        e.out = enc_u.as<uint64_t>();
+        LaunchTimer t(ctx, "batch_encode_wide_codes_kernel");
+        hipLaunchKernelGGL(kern, dim3(B), dim3(s.threads), s.lds, ctx->stream, e, inst);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    {   // read_field_elements + encode_f + <row, q1>
+        const EncodeShape s = encode_shape<FL, true>(cw);
+        auto kern = batch_encode_codes_kernel<FL, true, FL>;
+        if ((rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), s.lds))) return rc;
+        e.in_at = u_bytes + cols_bytes;
+        e.out = enc_f.as<uint64_t>();
+        e.q1 = C > 1 ? in.q1_d : nullptr;
+        e.clear_overflow = single ? 1u : 0u;
+        LaunchTimer t(ctx, "batch_encode_field_codes_kernel");
+        hipLaunchKernelGGL(kern, dim3(B), dim3(s.threads), s.lds, ctx->stream, e, inst);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (n_cols) {
+        BatchVerifyColsArgs a{};
+        a.openings_at = u_bytes;
+        a.cols = in.cols_d;
+        a.coeffs = single ? nullptr : in.coeffs_d;
+        a.q0 = single ? nullptr : in.q0_d;
+        a.roots = reinterpret_cast<const uint32_t *>(in.roots_d);
+        a.enc_u = single ? nullptr : enc_u.as<uint64_t>();
+        a.enc_f = enc_f.as<uint64_t>();
+        a.num_rows = R;
+        a.depth = ctx->depth;
+        a.n_cols = n_cols;
+        a.cw = cw;
+        a.flags = flags_d;
+        a.bad_merkle = bad_d;
+        a.malformed = mal_d;
+        const uint32_t per_wg = R < 256 ? 256 / R : 1;  // openings per workgroup
+        LaunchTimer t(ctx, "batch_verify_columns_codes_kernel");
+        hipLaunchKernelGGL(batch_verify_columns_codes_kernel<FL>, dim3((n_cols + per_wg - 1) / per_wg, B), dim3(256), 0, ctx->stream, a, inst);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    {
+        BatchVerifyReportArgs a{};
+        a.flags = flags_d;
+        a.bad_merkle = bad_d;
+        a.malformed = mal_d;
+        a.head = head_d;
+        a.evals = in.evals_d;
+        a.n_cols = n_cols;
+        a.row_len = C;
+        a.reports = reports_d;
+        LaunchTimer t(ctx, "batch_verify_report_kernel");
+        hipLaunchKernelGGL(batch_verify_report_kernel<FL>, dim3(B), dim3(256), 0, ctx->stream, a);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(reports, reports_d, (size_t)B * sizeof(zip_verify_report), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, stream_wait(ctx->stream));
+    return ZIP_OK;
+}
+
 }  // namespace
 
 // ---- sumcheck prover -----------------------------------------
@@ -2685,6 +2795,18 @@ int32_t ccs_batch_second_fl(zip_ccs_batch *b, const uint64_t *gamma_d) {
         HIP_TRY(ctx, hipGetLastError());
     }
     g_ccs_batch_launches += 2;
+    return ZIP_OK;
+}
+
+// V_xy of every instance from eq slot 0 (r_x) and slot 1 (r_y) into vs_d
+template <int FL>
+int32_t ccs_batch_eval_matrices_fl(zip_ccs_batch *b) {
+    zip_ctx *ctx = b->ctx;
+    LaunchTimer t(ctx, "ccs_batch_eval_matrices_kernel");
+    hipLaunchKernelGGL(ccs_batch_eval_matrices_kernel<FL>, dim3(b->t, b->n), dim3(kCcsBatchVsThreads), 0, ctx->stream, b->mats,
+                       static_cast<const CcsBatchInst<FL> *>(b->args_d), b->vs_d);
+    HIP_TRY(ctx, hipGetLastError());
+    g_ccs_batch_launches++;
     return ZIP_OK;
 }
 }  // namespace
@@ -4937,6 +5059,134 @@ int32_t zip_batch_verify(zip_ctx *ctx, uint32_t n_polys, const uint8_t *roots, c
 
 uint64_t zip_batch_verify_calls(void) { return g_batch_verify_calls.load(); }
 
+// zip_batch_verify for the proofs of a Zinc batch: member i has its own code (slice i of perms1 / perms2), its own field
+// and its own stream buffer.  The members share no transcript, so a short stream is that member's matter alone.
+int32_t zip_batch_verify_codes(zip_ctx *ctx, uint32_t n_polys, const uint32_t *perms1, const uint32_t *perms2, const uint8_t *roots,
+                               const uint8_t *const *proofs, const size_t *proof_lens, zip_mem_kind proofs_kind, const int64_t *coeffs,
+                               const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont, const uint64_t *q1_mont,
+                               const uint64_t *evals_mont, const zip_field *const *fields, zip_verify_report *reports) {
+    if (!ctx || !roots || !proofs || !proof_lens || !reports || !evals_mont || (n_cols && !cols)) return ZIP_ERR_NULL;
+    if (!perms1 || !perms2) return ZIP_ERR_NULL;
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len;
+    if (n_polys == 0 || n_polys > 65535)
+        return fail(ctx, ZIP_ERR_INVALID_PARAM, "a batch holds 1 .. 65535 polynomials (got %u)", n_polys);
+    if (ctx->rows_local != R) return fail(ctx, ZIP_ERR_INVALID_PARAM, "batches need an unsharded ctx");
+    if (int32_t r = refuse_extra_tests(ctx, "zip_batch_verify_codes")) return r;
+    if (cw > 16384)
+        return fail(ctx, ZIP_ERR_UNSUPPORTED, "batches serve codewords up to 16384 (got %u): larger proofs are not launch-bound, "
+                    "use zip_verify", cw);
+    if ((uint64_t)n_polys * n_cols > 0xFFFFFFFFull)
+        return fail(ctx, ZIP_ERR_UNSUPPORTED, "%u x %u openings exceed 2^32", n_polys, n_cols);
+    // where zip_batch_verify looks at its field: the members' fields, by zip_batch_open_fields's rules
+    std::vector<HostField> hfs;
+    int32_t rc;
+    if ((rc = batch_member_fields(ctx, fields, n_polys, &hfs))) return rc;
+    const uint32_t fl = hfs[0].fl;
+    if (R > 1 && (!coeffs || !q0_mont)) return fail(ctx, ZIP_ERR_NULL, "coeffs / q0_mont is NULL");
+    if (C > 1 && !q1_mont) return fail(ctx, ZIP_ERR_NULL, "q1_mont is NULL");
+    if ((rc = check_cols(ctx, cols, n_polys * n_cols))) return rc;
+    const size_t len = zip_proof_len(ctx, n_cols, fl);
+    // a member whose stream is all there must have one; a DEVICE stream is read in place with 8-byte loads
+    for (uint32_t i = 0; i < n_polys; i++) {
+        if (proof_lens[i] < len) continue;
+        if (!proofs[i]) return fail(ctx, ZIP_ERR_NULL, "proofs[%u] is NULL", i);
+        if (proofs_kind != ZIP_MEM_HOST && (reinterpret_cast<uintptr_t>(proofs[i]) & 7))
+            return fail(ctx, ZIP_ERR_INVALID_PARAM, "member %u: a device stream must be 8-byte aligned", i);
+    }
+    {   // zip_ctx_create's test of a permutation, per member: the encode kernel indexes with these values
+        std::vector<uint8_t> seen(cw);
+        for (uint32_t i = 0; i < n_polys; i++)
+            for (int k = 0; k < 2; k++) {
+                const uint32_t *perm = (k ? perms2 : perms1) + (size_t)i * cw;
+                std::fill(seen.begin(), seen.end(), 0);
+                for (uint32_t j = 0; j < cw; j++) {
+                    if (perm[j] >= cw || seen[perm[j]])
+                        return fail(ctx, ZIP_ERR_INVALID_PARAM, "member %u: perm%d is not a permutation of [0, %u)", i, k + 1, cw);
+                    seen[perm[j]] = 1;
+                }
+            }
+    }
+    memset(reports, 0, (size_t)n_polys * sizeof *reports);
+    // the members that reach the device; a short stream is malformed as it is for zip_verify (pcs_transcript.rs:125-160)
+    std::vector<uint32_t> live;
+    live.reserve(n_polys);
+    for (uint32_t i = 0; i < n_polys; i++) {
+        if (proof_lens[i] < len) reports[i].verdict = ZIP_VERIFY_MALFORMED;
+        else live.push_back(i);
+    }
+    const uint32_t k = (uint32_t)live.size();
+    if (k == 0) return ZIP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    g_batch_verify_codes_calls++;
+    g_batch_verify_codes_members += k;
+    // the small inputs of the live members, contiguous: the caller's arrays when every member is live
+    const bool all = k == n_polys;
+    const bool single = R == 1;
+    std::vector<unsigned char> packed[8];
+    std::vector<HostField> live_hf;
+    auto gather = [&](int slot, const void *src, size_t per_member) -> const void * {
+        if (all || !src || !per_member) return src;
+        packed[slot].resize((size_t)k * per_member);
+        for (uint32_t j = 0; j < k; j++)
+            memcpy(packed[slot].data() + (size_t)j * per_member, static_cast<const unsigned char *>(src) + (size_t)live[j] * per_member, per_member);
+        return packed[slot].data();
+    };
+    if (!all)
+        for (uint32_t j = 0; j < k; j++) live_hf.push_back(hfs[live[j]]);
+    const std::vector<HostField> &mhf = all ? hfs : live_hf;
+    Scratch pbuf(ctx), perms(ctx), small(ctx);
+    // the codes, once: all perm1 slices of the live members, then all perm2 slices
+    const size_t perm_words = (size_t)k * cw;
+    if ((rc = perms.get(2 * perm_words * 4))) return rc;
+    uint32_t *perms_d = perms.as<uint32_t>();
+    if ((rc = copy_h2d_bounced(ctx, perms_d, gather(6, perms1, (size_t)cw * 4), perm_words * 4, ctx->stream))) return rc;
+    if ((rc = copy_h2d_bounced(ctx, perms_d + perm_words, gather(7, perms2, (size_t)cw * 4), perm_words * 4, ctx->stream))) return rc;
+    std::vector<const uint8_t *> streams(k);
+    if (proofs_kind == ZIP_MEM_HOST) {  // stream j into its slot of one pooled block
+        if ((rc = pbuf.get((size_t)k * len))) return rc;
+        for (uint32_t j = 0; j < k; j++) {
+            streams[j] = pbuf.as<uint8_t>() + (size_t)j * len;
+            if ((rc = copy_h2d_bounced(ctx, pbuf.as<uint8_t>() + (size_t)j * len, proofs[live[j]], len, ctx->stream))) return rc;
+        }
+    } else {
+        for (uint32_t j = 0; j < k; j++) streams[j] = proofs[live[j]];
+    }
+    std::vector<unsigned char> inst_h;
+    with_fl(fl, [&](auto FL) { batch_fill_verify_members<decltype(FL)::value>(mhf, streams, perms_d, perms_d + perm_words, cw, &inst_h); });
+    SmallInputs si;
+    si.src[0] = gather(0, coeffs, (size_t)R * 8);          si.bytes[0] = single ? 0 : (size_t)k * R * 8;
+    si.src[1] = gather(1, q0_mont, (size_t)R * fl * 8);    si.bytes[1] = single ? 0 : (size_t)k * R * fl * 8;
+    si.src[2] = gather(2, cols, (size_t)n_cols * 4);       si.bytes[2] = (size_t)k * n_cols * 4;
+    si.src[3] = gather(3, q1_mont, (size_t)C * fl * 8);    si.bytes[3] = C > 1 ? (size_t)k * C * fl * 8 : 0;
+    si.src[4] = gather(4, roots, (size_t)R * 32);          si.bytes[4] = (size_t)k * R * 32;
+    si.src[5] = gather(5, evals_mont, (size_t)fl * 8);     si.bytes[5] = (size_t)k * fl * 8;
+    si.src[6] = inst_h.data();                             si.bytes[6] = inst_h.size();
+    unsigned char *sb;
+    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
+    VerifyIn in{};
+    in.coeffs_d = reinterpret_cast<const int64_t *>(sb + si.off[0]);
+    in.q0_d = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
+    in.cols_d = reinterpret_cast<const uint32_t *>(sb + si.off[2]);
+    in.q1_d = reinterpret_cast<const uint64_t *>(sb + si.off[3]);
+    in.roots_d = sb + si.off[4];
+    in.evals_d = reinterpret_cast<const uint64_t *>(sb + si.off[5]);
+    in.n_cols = n_cols;
+    in.n_polys = k;
+    std::vector<zip_verify_report> live_reports(all ? 0 : k);
+    zip_verify_report *dst = all ? reports : live_reports.data();
+    if ((rc = with_fl(fl, [&](auto FL) { return run_batch_verify_codes_fl<decltype(FL)::value>(ctx, in, sb + si.off[6], dst); })))
+        return rc;
+    if (!all)
+        for (uint32_t j = 0; j < k; j++) reports[live[j]] = live_reports[j];
+    return ZIP_OK;
+}
+
+void zip_batch_verify_codes_counts(uint64_t *calls, uint64_t *members) {
+    if (calls) *calls = g_batch_verify_codes_calls.load();
+    if (members) *members = g_batch_verify_codes_members.load();
+}
+
 int32_t zip_commitment_mle_eval(zip_commitment *c, const uint64_t *q0_mont, const uint64_t *q1_mont,
                                 const zip_field *field, uint64_t *value_out) {
     if (!c) return ZIP_ERR_NULL;
@@ -5749,7 +5999,8 @@ int32_t zip_ccs_batch_create(int32_t device, const zip_sparse_matrix *mats, uint
         if ((rc = pool_alloc(ctx, tables_bytes, (void **)&b->tables))) break;
         if ((rc = pool_alloc(ctx, z_bytes, (void **)&b->z_d))) break;
         const size_t inst_bytes = with_fl(limbs, [](auto FL) { return sizeof(CcsBatchInst<decltype(FL)::value>); });
-        if ((rc = pool_alloc(ctx, (size_t)capacity * inst_bytes, &b->args_d))) break;
+        // (behind the entries: room for the two points per instance that zip_ccs_batch_eval_matrices uploads with them)
+        if ((rc = pool_alloc(ctx, (size_t)capacity * (inst_bytes + 2 * s * elem), &b->args_d))) break;
         if ((rc = pool_alloc(ctx, (size_t)capacity * (s + 1) * elem, (void **)&b->chal_d))) break;
         if ((rc = pool_alloc(ctx, (size_t)capacity * t * elem, (void **)&b->vs_d))) break;
         if (stream_wait(ctx->stream) != hipSuccess) { rc = ZIP_ERR_HIP; break; }  // ONE wait for all t transpositions
@@ -5916,6 +6167,58 @@ int32_t zip_ccs_batch_download(zip_ccs_batch *b, uint32_t instance, zip_ccs_tabl
     zip_ctx *ctx = b->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return copy_d2h_bounced(ctx, out, d, (size_t)b->m * b->fl * 8, ctx->stream);
+}
+
+int32_t zip_ccs_batch_eval_matrices(zip_ccs_batch *b, const zip_field *const *fields, uint32_t n, const uint64_t *r_x,
+                                    const uint64_t *r_y, uint64_t *v_xy_out) {
+    // usage errors, before anything reaches the device, in set_z's order: every NULL, then n, then the fields
+    if (!b || !fields || !r_x || !r_y || !v_xy_out) return ZIP_ERR_NULL;
+    zip_ctx *ctx = b->ctx;
+    const uint32_t scan = std::min(n, b->capacity);
+    for (uint32_t i = 0; i < scan; i++)
+        if (!fields[i]) return ZIP_ERR_NULL;
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (n < 1 || n > b->capacity) return fail(ctx, ZIP_ERR_INVALID_PARAM, "%u instances, the handle was made for 1..%u", n, b->capacity);
+    for (uint32_t i = 0; i < n; i++)
+        if (fields[i]->limbs != b->fl)
+            return fail(ctx, ZIP_ERR_INVALID_PARAM, "instance %u: a field of %u limbs, the handle was made for %u", i, fields[i]->limbs, b->fl);
+    std::vector<HostField> hf(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (i && !memcmp(fields[i]->modulus, fields[i - 1]->modulus, 8 * (size_t)b->fl)) {
+            hf[i] = hf[i - 1];
+            continue;
+        }
+        if (int32_t rc = make_field_uncached(ctx, fields[i], &hf[i])) return rc;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int32_t rc;
+    if ((rc = ccs_batch_wait(b))) return rc;  // the staging vectors of the previous call
+    // the instances of a previous set_z are replaced: the table calls answer ZIP_ERR_INVALID_PARAM until the next one
+    b->n = 0;
+    b->have_eq[0] = b->have_eq[1] = b->have_second = false;
+    const std::vector<const int64_t *> no_z(n, nullptr);
+    const std::vector<size_t> no_len(n, 0);
+    with_fl(b->fl, [&](auto FL) { ccs_batch_fill_args<decltype(FL)::value>(b, hf, no_z, no_len.data(), n); });
+    // one upload: the entries, every r_x, every r_y
+    const size_t inst_bytes = b->args_h.size(), r_words = (size_t)n * b->s * b->fl;
+    b->args_h.resize(inst_bytes + 2 * r_words * 8);
+    memcpy(b->args_h.data() + inst_bytes, r_x, r_words * 8);
+    memcpy(b->args_h.data() + inst_bytes + r_words * 8, r_y, r_words * 8);
+    b->in_flight = true;
+    HIP_TRY(ctx, hipMemcpyAsync(b->args_d, b->args_h.data(), b->args_h.size(), hipMemcpyHostToDevice, ctx->stream));
+    const uint64_t *r_d = reinterpret_cast<const uint64_t *>(static_cast<const unsigned char *>(b->args_d) + inst_bytes);
+    b->n = n;  // (the launchers size their grids by it)
+    rc = with_fl(b->fl, [&](auto FL) {
+        constexpr int L = decltype(FL)::value;
+        int32_t r = ccs_batch_eq_fl<L>(b, r_d, 0);
+        if (!r) r = ccs_batch_eq_fl<L>(b, r_d + r_words, 1);
+        if (!r) r = ccs_batch_eval_matrices_fl<L>(b);
+        return r;
+    });
+    b->n = 0;
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(v_xy_out, b->vs_d, (size_t)n * b->t * b->fl * 8, hipMemcpyDeviceToHost, ctx->stream));
+    return ccs_batch_wait(b);
 }
 
 void zip_ccs_batch_counts(uint64_t *kernel_launches, uint64_t *instances) {

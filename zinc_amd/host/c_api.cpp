@@ -756,6 +756,74 @@ int32_t zinc_prover_pcs_step_batch(const zinc_linear_code_spec *spec, uint32_t s
     });
 }
 
+int32_t zinc_verifier_verify_batch(const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                                   uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c, uint32_t n_instances,
+                                   zinc_transcript *const *transcripts, const uint64_t *moduli, const uint32_t *limbs,
+                                   int32_t device, const uint64_t *msgs1, const uint64_t *msgs2, const uint64_t *v_s,
+                                   const uint8_t *const *roots, const size_t *n_roots, const uint64_t *v,
+                                   const uint8_t *const *pcs_proofs, const size_t *pcs_proof_lens, int32_t *results_out,
+                                   char *messages_out, size_t message_cap) {
+    if (!constraints || !s_masks || !c || !transcripts || !moduli || !limbs || !msgs1 || !msgs2 || !v_s || !roots || !n_roots || !v ||
+        !pcs_proofs || !pcs_proof_lens || !results_out || (messages_out && !message_cap))
+        return ZINC_ERR_NULL;
+    for (uint32_t i = 0; i < n_instances; i++)
+        if (!transcripts[i] || (n_roots[i] && !roots[i]) || (pcs_proof_lens[i] && !pcs_proofs[i])) return ZINC_ERR_NULL;
+    return guarded([&] {
+        zinc::ccs::CCS_Z ccs = square_ccs(t, s);
+        ccs.q = q;
+        ccs.d = d;
+        for (uint32_t i = 0; i < q; i++) {
+            ccs.c.push_back(c[i]);
+            ccs.S.emplace_back();
+            for (uint32_t j = 0; j < 32; j++)
+                if ((s_masks[i] >> j) & 1u) ccs.S.back().push_back(j);
+        }
+        std::vector<zinc::SpartanProof> sp(n_instances);
+        std::vector<zinc::zip::MultilinearZipCommitment> comms(n_instances);
+        std::vector<Limbs> vs(n_instances);
+        std::vector<zinc::ZincVerifier::BatchProof> proofs(n_instances);
+        std::vector<zinc::KeccakTranscript *> tr(n_instances);
+        std::vector<FieldConfig> f;
+        size_t m1 = 0, m2 = 0, at_vs = 0, at_v = 0;  // instance-major, each instance with its own number of limbs
+        for (uint32_t i = 0; i < n_instances; i++) {
+            const uint32_t fl = limbs[i];
+            f.push_back(FieldConfig::make(moduli + (size_t)i * 4, fl));
+            auto take = [&](const uint64_t *src, size_t &at, size_t rounds, size_t per) {
+                zinc::sumcheck::SumcheckProof p;
+                for (size_t r = 0; r < rounds; r++) {
+                    p.msgs.emplace_back();
+                    for (size_t e = 0; e < per; e++, at += fl) p.msgs.back().push_back(load(src + at, fl));
+                }
+                return p;
+            };
+            sp[i].linearization_sumcheck = take(msgs1, m1, s, d + 2);
+            sp[i].second_sumcheck = take(msgs2, m2, s, 3);
+            for (uint32_t k = 0; k < t; k++, at_vs += fl) sp[i].V_s.push_back(load(v_s + at_vs, fl));
+            vs[i] = load(v + at_v, fl);
+            at_v += fl;
+            comms[i].roots.resize(n_roots[i]);
+            if (n_roots[i]) std::memcpy(comms[i].roots.data(), roots[i], n_roots[i] * 32);
+            proofs[i] = {&sp[i], &comms[i], &vs[i], pcs_proofs[i], pcs_proof_lens[i]};  // the proof bytes are read in place
+            tr[i] = &transcripts[i]->t;
+        }
+        const auto outcomes = zinc::ZincVerifier(spec_of(spec), device).verify_batch(constraints, ccs, proofs, tr, f);
+        for (uint32_t i = 0; i < n_instances; i++) {
+            const auto &o = outcomes[i];
+            using O = zinc::ZincVerifier::BatchOutcome;
+            results_out[i] = o.kind == O::Accepted  ? ZINC_OK
+                             : o.kind == O::Spartan ? ZINC_ERR_SPARTAN
+                             : o.zip_kind == ZipError::InvalidPcsParam ? ZINC_ERR_INVALID_PARAM
+                                                                       : ZINC_ERR_INVALID_OPEN;
+            if (messages_out) {
+                char *dst = messages_out + (size_t)i * message_cap;
+                const size_t n = std::min(o.message.size(), message_cap - 1);
+                std::memcpy(dst, o.message.data(), n);
+                dst[n] = 0;
+            }
+        }
+    });
+}
+
 int32_t zinc_verifier_verify(const zip_sparse_matrix *constraints, uint32_t t, uint32_t s, uint32_t d, uint32_t q,
                              const uint32_t *s_masks, const int64_t *c, zinc_transcript *transcript, const uint64_t *modulus,
                              uint32_t limbs, int32_t device, zinc_prepared_ccs *prepared, const uint64_t *msgs1,

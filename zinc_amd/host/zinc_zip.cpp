@@ -2228,4 +2228,198 @@ void ZincVerifier::verify(const ccs::Statement_Z &statement, const ZincProof &pr
     verify_pcs_proof(statement, proof.zip_proof, points, ccs, transcript, config, prepared);          // :66-73
 }
 
+// ---- B proofs of one circuit (zip_batch_verify_codes + zip_ccs_batch_eval_matrices) -------------------------------------
+namespace {
+// From how many proofs on verify_batch takes the batched path: per size the smallest B at which it beat the loop over
+// verify by more than the loop's own spread (tools/verify_batch_times.py, profiles/verify_batch.md: 1000 openings, 4
+// limbs, B = 2, 16 and, at 2^10 rows, 256).  2 proofs win at 2^10 and 2^14 rows (1.21x, 1.10x) and stay inside the loop's
+// spread at 2^12 and 2^16 (1.11x, 1.06x); 16 proofs win at every size (2.4x .. 3.7x).  Counts between 2 and 16 were not
+// measured and loop where 2 did not win; a size between the measured ones takes the rule of the next larger one.
+// ZIP_HIP_VERIFY_MIN_BATCH=n (n >= 2, read per call) puts the line at n for every size: how the tests and
+// tools/verify_batch_times.py reach the batched path below the line.
+size_t min_verify_batch(size_t s_prime) {
+    if (const char *e = std::getenv("ZIP_HIP_VERIFY_MIN_BATCH")) {
+        const long n = std::atol(e);
+        if (n >= 2) return (size_t)n;
+    }
+    return s_prime <= 10 ? 2 : s_prime <= 12 ? 16 : s_prime <= 14 ? 2 : 16;
+}
+
+// f(): true when it returned; false with the outcome `verify` would have ended in when it threw one of the verifier's own
+// errors.  Device failures and panics pass through: they are no verdict on a proof.
+template <class F>
+bool attempt(ZincVerifier::BatchOutcome &o, F &&f) {
+    try {
+        f();
+        return true;
+    } catch (const SpartanError &e) {
+        o.kind = ZincVerifier::BatchOutcome::Spartan;
+        o.message = e.what();
+    } catch (const ZipError &e) {
+        if (e.kind == ZipError::Device) throw;
+        o.kind = ZincVerifier::BatchOutcome::Zip;
+        o.zip_kind = e.kind;
+        o.message = e.what();
+    }
+    return false;
+}
+}  // namespace
+
+std::vector<ZincVerifier::BatchOutcome> ZincVerifier::verify_batch(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs,
+                                                                   const std::vector<const ZincProof *> &proofs,
+                                                                   const std::vector<KeccakTranscript *> &transcripts,
+                                                                   const std::vector<FieldConfig> &configs) const {
+    std::vector<BatchProof> views(proofs.size());
+    for (size_t i = 0; i < proofs.size(); i++) {
+        if (!proofs[i]) throw std::logic_error("verify_batch: a NULL proof");
+        const zip::ZipProof &zp = proofs[i]->zip_proof;
+        views[i] = {&proofs[i]->spartan_proof, &zp.z_comm, &zp.v, zp.pcs_proof.data(), zp.pcs_proof.size()};
+    }
+    return verify_batch(matrices, ccs, views, transcripts, configs);
+}
+
+std::vector<ZincVerifier::BatchOutcome> ZincVerifier::verify_batch(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs,
+                                                                   const std::vector<BatchProof> &proofs,
+                                                                   const std::vector<KeccakTranscript *> &transcripts,
+                                                                   const std::vector<FieldConfig> &configs) const {
+    const size_t B = proofs.size();
+    if (transcripts.size() != B || configs.size() != B) throw std::logic_error("verify_batch: one transcript and one field per proof");
+    if (!matrices && B) throw std::logic_error("verify_batch: no matrices");
+    // the shapes verify and spartan_verify panic on, on every member, before any transcript is touched
+    if (ccs.s == 0 || ccs.s > 28 || ccs.m != ((size_t)1 << ccs.s) || ccs.n != ccs.m || ccs.s_prime != ccs.s)
+        throw std::logic_error("m == n == 2^s is required (see ZincProver)");
+    for (size_t i = 0; i < B; i++) {
+        const BatchProof &p = proofs[i];
+        if (!transcripts[i] || !p.spartan_proof || !p.z_comm || !p.v || (!p.pcs_proof && p.pcs_proof_len))
+            throw std::logic_error("verify_batch: a NULL transcript or proof part");
+        if (p.spartan_proof->V_s.size() != ccs.t || ccs.S.size() != ccs.q || ccs.c.size() != ccs.q)
+            throw std::logic_error("index out of bounds: V_s / ccs.S / ccs.c sizes");
+        for (const auto &Si : ccs.S)
+            for (size_t j : Si)
+                if (j >= ccs.t) throw std::logic_error("index out of bounds: ccs.S refers to a missing V_s");
+    }
+    std::vector<BatchOutcome> out(B);
+    const uint32_t s = (uint32_t)ccs.s, t = (uint32_t)ccs.t;
+    // the geometry RaaCode::make will give every member (code_raa.rs:43), known before a transcript is touched
+    const uint64_t cw_all = zip::next_pow2(zip::isqrt(ccs.m)) * lc_spec_.repetition_factor;
+    bool batched = zip::batch_path_enabled() && B >= 2 && B <= 65535 && lc_spec_.num_proximity_testing <= 1 && cw_all <= 16384 &&
+                   s <= 16 && B >= min_verify_batch(ccs.s_prime);
+    for (size_t i = 1; i < B && batched; i++) batched = configs[i].limbs == configs[0].limbs;
+    if (!batched) {
+        ccs::Statement_Z st;
+        st.constraints.resize(t);  // the matrices go to the device straight from the caller's arrays
+        for (size_t i = 0; i < B; i++)
+            attempt(out[i], [&] {
+                const VerificationPoints points = spartan_verify(*proofs[i].spartan_proof, ccs, *transcripts[i], configs[i]);
+                PreparedCcs prep(matrices, t, s, configs[i], device_);  // per proof: every proof has its own field
+                verify_pcs_proof(st, *proofs[i].z_comm, *proofs[i].v, proofs[i].pcs_proof, proofs[i].pcs_proof_len, points, ccs,
+                                 *transcripts[i], configs[i], &prep);
+            });
+        return out;
+    }
+    const uint32_t fl = configs[0].limbs;
+    // 1. SpartanVerifier::verify per member: host work
+    std::vector<VerificationPoints> points(B);
+    std::vector<size_t> live;
+    for (size_t i = 0; i < B; i++)
+        if (attempt(out[i], [&] { points[i] = spartan_verify(*proofs[i].spartan_proof, ccs, *transcripts[i], configs[i]); })) live.push_back(i);
+    if (live.empty()) return out;
+    // 2. per survivor, in verify_pcs_proof's order: the code from its transcript (:234), then what MultilinearZip::verify
+    // does in front of the device call on a FRESH PcsTranscript over the proof bytes (:236)
+    zip::MultilinearZipParams param;
+    bool have_param = false;
+    uint32_t cw = 0, num_rows = 0, n_cols = 0;
+    std::vector<size_t> pcs;  // the members that reach zip_batch_verify_codes
+    std::vector<uint32_t> perms1, perms2, cols;
+    std::vector<int64_t> coeffs;
+    std::vector<uint64_t> q0, q1, evals;
+    std::vector<uint8_t> roots;
+    std::vector<const uint8_t *> streams;
+    std::vector<size_t> stream_lens;
+    for (size_t i : live) {
+        const BatchProof &p = proofs[i];
+        const FieldConfig &f = configs[i];
+        zip::KeccakSeedSource seeds(*transcripts[i]);
+        const zip::RaaCode code = zip::RaaCode::make(lc_spec_, ccs.m, seeds);
+        if (!have_param) {
+            param = zip::MultilinearZip::setup(ccs.m, code, device_);  // the ctx of the geometry, cached like any other
+            have_param = true;
+            cw = code.codeword_len();
+            num_rows = param.num_rows;
+            n_cols = param.linear_code.num_column_opening;
+        }
+        std::pair<std::vector<int64_t>, std::vector<uint32_t>> ch;
+        std::vector<uint64_t> q0_i, q1_i;
+        const bool reaches = attempt(out[i], [&] {
+            size_t point_len = ccs.s_prime;
+            zip::validate_input("verify", param.num_vars, param.num_vars, &point_len);
+            if (p.z_comm->roots.size() != num_rows) throw ZipError(ZipError::InvalidPcsOpen, "commitment has the wrong number of roots");
+            zip::PcsTranscript walk = zip::PcsTranscript::from_proof_view(p.pcs_proof, p.pcs_proof_len);
+            ch = zip::MultilinearZip::open_challenges(num_rows, cw, n_cols, param.linear_code.num_proximity_testing, f, walk);
+            zip::point_to_tensor(f, num_rows, points[i].rx_ry.data() + ccs.s, ccs.s_prime, q0_i, q1_i);
+        });
+        if (!reaches) continue;
+        pcs.push_back(i);
+        const auto p1 = zip::shuffle_seeded_perm(code.perm_1_seed, cw), p2 = zip::shuffle_seeded_perm(code.perm_2_seed, cw);
+        perms1.insert(perms1.end(), p1.begin(), p1.end());
+        perms2.insert(perms2.end(), p2.begin(), p2.end());
+        coeffs.insert(coeffs.end(), ch.first.begin(), ch.first.end());
+        cols.insert(cols.end(), ch.second.begin(), ch.second.end());
+        q0.insert(q0.end(), q0_i.begin(), q0_i.end());
+        q1.insert(q1.end(), q1_i.begin(), q1_i.end());
+        evals.insert(evals.end(), p.v->begin(), p.v->begin() + fl);
+        for (const auto &r : p.z_comm->roots) roots.insert(roots.end(), r.begin(), r.end());
+        streams.push_back(p.pcs_proof);
+        stream_lens.push_back(p.pcs_proof_len);
+    }
+    // 3. every proof stream in one call, read where it lies
+    std::vector<zip_verify_report> reports(pcs.size());
+    std::vector<zip_field> zf(pcs.size());
+    std::vector<const zip_field *> zfp(pcs.size());
+    for (size_t j = 0; j < pcs.size(); j++) {
+        zf[j] = configs[pcs[j]].to_abi();
+        zfp[j] = &zf[j];
+    }
+    if (!pcs.empty()) {
+        zip_ctx *ctx = param.ctx.get();
+        zip::check(ctx,
+                   zip_batch_verify_codes(ctx, (uint32_t)pcs.size(), perms1.data(), perms2.data(), roots.data(), streams.data(),
+                                          stream_lens.data(), ZIP_MEM_HOST, coeffs.empty() ? nullptr : coeffs.data(), cols.data(), n_cols,
+                                          q0.empty() ? nullptr : q0.data(), q1.empty() ? nullptr : q1.data(), evals.data(), zfp.data(),
+                                          reports.data()),
+                   "zip_batch_verify_codes");
+    }
+    // 4. V_xy (:248-261) of the same members over the circuit as integers
+    std::vector<uint64_t> vxy(pcs.size() * (size_t)t * fl);
+    if (!pcs.empty()) {
+        std::vector<uint64_t> rx(pcs.size() * (size_t)s * fl), ry(pcs.size() * (size_t)s * fl);
+        for (size_t j = 0; j < pcs.size(); j++)
+            for (size_t k = 0; k < s; k++) {
+                const std::vector<Limbs> &pt = points[pcs[j]].rx_ry;
+                std::copy(pt[k].begin(), pt[k].begin() + fl, rx.begin() + (j * s + k) * fl);
+                std::copy(pt[s + k].begin(), pt[s + k].begin() + fl, ry.begin() + (j * s + k) * fl);
+            }
+        CcsBatchHandle dev;
+        ccs_batch_check(nullptr, zip_ccs_batch_create(device_, matrices, t, s, fl, (uint32_t)pcs.size(), &dev.h), "zip_ccs_batch_create");
+        ccs_batch_check(dev.h, zip_ccs_batch_eval_matrices(dev.h, zfp.data(), (uint32_t)pcs.size(), rx.data(), ry.data(), vxy.data()),
+                        "zip_ccs_batch_eval_matrices");
+    }
+    // 5. per member, in the loop's order: the PCS verdict, then the last check (:264-271)
+    for (size_t j = 0; j < pcs.size(); j++) {
+        const size_t i = pcs[j];
+        const FieldConfig &f = configs[i];
+        attempt(out[i], [&] {
+            zip::throw_unless_accepted(reports[j].verdict);
+            std::vector<Limbs> V_xy(t);
+            for (size_t k = 0; k < t; k++)
+                for (uint32_t l = 0; l < fl; l++) V_xy[k][l] = vxy[(j * t + k) * fl + l];
+            Limbs lhs = lin_comb_V_s(f, points[i].gamma, V_xy);
+            f.mul_assign(lhs, *proofs[i].v);
+            if (lhs != points[i].e_y)
+                throw SpartanError(SpartanError::PcsVerification, "linear combination of powers of gamma and V_x != e_y");
+        });
+    }
+    return out;
+}
+
 }  // namespace zinc

@@ -597,6 +597,41 @@ class ZincVerifier {
                           const ccs::CCS_Z &ccs, KeccakTranscript &transcript, const FieldConfig &config,
                           PreparedCcs *prepared = nullptr) const;
 
+    // B proofs of ONE circuit, each with its own transcript and field (what ZincProver::prove_batch makes): for every
+    // proof exactly what `verify` does -- outcome i and transcripts[i] afterwards are what the loop over verify leaves,
+    // for rejected proofs as well -- but the call does not stop at the first reject: it returns one outcome per proof.
+    // The batched path: per member spartan_verify on the host (a member that fails there has its outcome and leaves the
+    // batch); per survivor RaaCode::make on its transcript, its two permutations, the squeezes of a fresh PcsTranscript
+    // and the point's tensors; ONE zip_batch_verify_codes with the streams passed by pointer; ONE
+    // zip_ccs_batch_eval_matrices over the circuit as integers (no PreparedCcs per field); per member, in the loop's
+    // order, the PCS verdict and then gamma-combination * v == e_y.
+    // The loop over verify runs instead with ZIP_HIP_BATCH=0, one instance, more than one proximity test, codewords above
+    // 16384, s above 16, differing limb counts, or B below the line of min_verify_batch (zinc_zip.cpp;
+    // ZIP_HIP_VERIFY_MIN_BATCH=n moves it).
+    // std::logic_error is a shape the reference panics on: thrown for the first member that has it, before any device
+    // work.  (An encode_wide overflow inside a proof stream, the one panic the device finds, is thrown when that member's
+    // turn comes, as the loop throws it; the batched path has then moved the later members' transcripts already.)
+    // Not part of this: the field check of verify_checked (check_field per member, which callers run first).
+    struct BatchProof {  // one ZincProof, its bytes borrowed
+        const SpartanProof *spartan_proof = nullptr;
+        const zip::MultilinearZipCommitment *z_comm = nullptr;
+        const Limbs *v = nullptr;
+        const uint8_t *pcs_proof = nullptr;
+        size_t pcs_proof_len = 0;
+    };
+    struct BatchOutcome {
+        enum Kind { Accepted, Spartan, Zip } kind = Accepted;
+        ZipError::Kind zip_kind = ZipError::InvalidPcsOpen;  // kind == Zip: InvalidPcsOpen, Transcript or InvalidPcsParam
+        std::string message;                                 // what() of what verify would have thrown for this proof alone
+        bool accepted() const { return kind == Accepted; }
+    };
+    std::vector<BatchOutcome> verify_batch(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs, const std::vector<BatchProof> &proofs,
+                                           const std::vector<KeccakTranscript *> &transcripts,
+                                           const std::vector<FieldConfig> &configs) const;
+    std::vector<BatchOutcome> verify_batch(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs, const std::vector<const ZincProof *> &proofs,
+                                           const std::vector<KeccakTranscript *> &transcripts,
+                                           const std::vector<FieldConfig> &configs) const;
+
   private:
     zip::LinearCodeSpec lc_spec_;
     int device_;

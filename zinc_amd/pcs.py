@@ -27,7 +27,7 @@ EXPORTED_SYMBOLS = (
     "zinc_zip_verify", "zinc_zip_evaluate", "zinc_commit_z_mle_and_prove_evaluation", "zinc_zip_proof_len",
     "zinc_zip_proof_num_roots", "zinc_zip_proof_read", "zinc_zip_proof_free", "zinc_zip_release_cached_contexts", "zinc_sumcheck_prove_product", "zinc_sumcheck_prove_ccs", "zinc_zip_data_download", "zinc_zip_data_upload", "zinc_merkle_tree_new",
     "zinc_prover_prove", "zinc_prover_prepare", "zinc_prepared_ccs_free", "zinc_verifier_verify",
-    "zinc_sumcheck_prove_products", "zinc_sumcheck_verify", "zinc_sumcheck_prove_batch", "zinc_prover_prove_batch",
+    "zinc_sumcheck_prove_products", "zinc_sumcheck_verify", "zinc_sumcheck_prove_batch", "zinc_prover_prove_batch", "zinc_verifier_verify_batch",
     "zinc_prover_pcs_step_batch",
     "zinc_zip_batch_commit", "zinc_zip_batch_open", "zinc_zip_batch_open_challenges",
     "zinc_zip_batch_verify", "zinc_zip_batch_verify_challenges",
@@ -158,6 +158,8 @@ def lib():
                                         C.POINTER(vp)]
         L.zinc_prover_prove_batch.argtypes = [C.POINTER(LinearCodeSpec), vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
                                               C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+        L.zinc_verifier_verify_batch.argtypes = [C.POINTER(LinearCodeSpec), vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
+                                                 C.c_uint32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
         L.zinc_prover_pcs_step_batch.argtypes = [C.POINTER(LinearCodeSpec), C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_int32, vp]
         L.zinc_prover_prepare.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_int32, C.POINTER(vp)]
         L.zinc_prepared_ccs_free.argtypes = [vp]
@@ -181,21 +183,27 @@ def lib():
     return _lib
 
 
+def _error(rc, msg):
+    """the exception object of a facade return code (None for OK)"""
+    if rc == OK:
+        return None
+    if rc == ERR_INVALID_PARAM:
+        return InvalidPcsParam(msg)
+    if rc == ERR_INVALID_OPEN:
+        return InvalidPcsOpen(msg)
+    if rc == ERR_PANIC:
+        return ReferencePanic(msg)
+    if rc == ERR_SPARTAN:
+        return SpartanError(msg)
+    if rc == ERR_FIELD_CONFIG:
+        return FieldConfigError(msg)
+    return DeviceError(msg)
+
+
 def _check(rc):
     if rc == OK:
         return
-    msg = lib().zinc_last_error().decode()
-    if rc == ERR_INVALID_PARAM:
-        raise InvalidPcsParam(msg)
-    if rc == ERR_INVALID_OPEN:
-        raise InvalidPcsOpen(msg)
-    if rc == ERR_PANIC:
-        raise ReferencePanic(msg)
-    if rc == ERR_SPARTAN:
-        raise SpartanError(msg)
-    if rc == ERR_FIELD_CONFIG:
-        raise FieldConfigError(msg)
-    raise DeviceError(msg)
+    raise _error(rc, lib().zinc_last_error().decode())
 
 
 def _limbs(value: int, n: int) -> np.ndarray:
@@ -890,6 +898,51 @@ class ZincVerifier:
         other work (:53-57; the check is the C++ mirror's, ZincVerifier::check_field).  None: no such check, the field
         is taken as handed."""
         return self._run(matrices, s, d, S, c, proof, transcript, field, True, prepared, public_input)
+
+    def verify_batch(self, matrices, s, d, S, c, proofs, transcripts, fields):
+        """verify for B proofs of ONE circuit (the dicts prove_batch returns), proofs[i] on transcripts[i] in fields[i]
+        (ZincVerifier::verify_batch) -> a list with None per accepted proof and, not raised, the exception object verify
+        would have raised for that proof alone (SpartanError / InvalidPcsOpen) otherwise.  Every transcript ends where
+        verify leaves it, for rejected proofs as well.  From the line profiles/verify_batch.md sets on (ZIP_HIP_VERIFY_MIN_BATCH=n
+        moves it) the PCS part of proofs of one limb count is one zip_batch_verify_codes and the matrix MLEs one
+        zip_ccs_batch_eval_matrices; otherwise, and with ZIP_HIP_BATCH=0, the loop over verify runs inside the call."""
+        B, t = len(proofs), len(matrices)
+        assert len(transcripts) == B and len(fields) == B
+        arr, _keep = ZincProver._abi_matrices(matrices)
+        masks = np.array([sum(1 << j for j in Si) for Si in S], dtype=np.uint32)
+        cv = np.array(c, dtype=np.int64)
+        n = max(B, 1)
+        limbs = np.array([f.limbs for f in fields], dtype=np.uint32)
+        moduli = np.zeros((n, 4), dtype=np.uint64)
+        for i, f in enumerate(fields):
+            moduli[i, :f.limbs] = np.asarray(f._m, dtype=np.uint64)[:f.limbs]
+
+        def flat(key, shape):
+            parts = []
+            for p, f in zip(proofs, fields):
+                a = np.ascontiguousarray(p[key], dtype=np.uint64)
+                assert a.shape == shape + (f.limbs,), (key, a.shape)
+                parts.append(a.reshape(-1))
+            return np.concatenate(parts) if parts else np.zeros(1, np.uint64)
+
+        m1, m2, vs = flat("msgs1", (s, d + 2)), flat("msgs2", (s, 3)), flat("V_s", (t,))
+        roots = [np.ascontiguousarray(p["zip_proof"]["z_comm"], dtype=np.uint8).reshape(-1, 32) for p in proofs]
+        streams = [np.ascontiguousarray(p["zip_proof"]["pcs_proof"], dtype=np.uint8).reshape(-1) for p in proofs]
+        v = np.concatenate([np.ascontiguousarray(p["zip_proof"]["v"], dtype=np.uint64).reshape(-1) for p in proofs]) if B else np.zeros(1, np.uint64)
+        assert v.size == int(limbs.sum()) or not B
+        trs = (C.c_void_p * n)(*[tr._h for tr in transcripts])
+        rp = (C.c_void_p * n)(*[r.ctypes.data for r in roots])
+        rn = (C.c_size_t * n)(*[r.shape[0] for r in roots])
+        pp = (C.c_void_p * n)(*[p.ctypes.data for p in streams])
+        pl = (C.c_size_t * n)(*[p.size for p in streams])
+        results = np.zeros(n, dtype=np.int32)
+        cap = 256
+        messages = C.create_string_buffer(n * cap)
+        _check(lib().zinc_verifier_verify_batch(_spec_ptr(self.spec), arr, t, s, d, len(S), masks.ctypes.data, cv.ctypes.data, B, trs,
+                                                moduli.ctypes.data, limbs.ctypes.data, self.device, m1.ctypes.data, m2.ctypes.data,
+                                                vs.ctypes.data, rp, rn, v.ctypes.data, pp, pl, results.ctypes.data, messages, cap))
+        raw = messages.raw
+        return [_error(int(results[i]), raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode()) for i in range(B)]
 
 
 class PreparedCcs:
