@@ -1172,20 +1172,25 @@ int orc_verify(const orc_params *p, const orc_field *f, const uint8_t *roots,
     uint32_t *cols = (uint32_t *)malloc(4 * (size_t)ncol);
     uint64_t *colvals = (uint64_t *)malloc((size_t)8 * K * R * ncol);
 
-    /* verify_testing, verify_z.rs:60-105 (num_proximity_testing == 1 supported) */
-    if (R > 1 && p->num_proximity_testing > 0) {
+    /* verify_testing, verify_z.rs:60-105: per proximity test, in order, the coefficients are squeezed, the
+     * combined row is read and encoded (:71-79); coeffs_m / enc_comb hold test t at [t * R] / [t * cw] */
+    const uint32_t T = R > 1 ? p->num_proximity_testing : 0;
+    if (T > 0) {
         uint64_t *coeffs = (uint64_t *)malloc((size_t)8 * p->n_limbs * R);
         uint64_t *comb = (uint64_t *)malloc((size_t)8 * M * C);
-        coeffs_m = (uint64_t *)malloc((size_t)8 * M * R);
-        enc_comb = (uint64_t *)malloc((size_t)8 * M * cw);
-        for (uint32_t r = 0; r < R; r++)
-            orc_tr_get_integer_challenge(fs, p->n_limbs, coeffs + (size_t)p->n_limbs * r);
-        for (uint32_t c = 0; c < C; c++)
-            if (rs_read_integer(&rs, comb + (size_t)M * c, M)) rc = ORC_ERR_TRANSCRIPT;
-        for (uint32_t r = 0; r < R; r++) wi_sext(coeffs_m + (size_t)M * r, M, coeffs + (size_t)p->n_limbs * r, p->n_limbs);
-        if (rc == ORC_OK &&
-            orc_raa_encode_row(comb, M, C, p->rep, p->perm1, p->perm2, enc_comb, M) != ORC_OK)
-            rc = ORC_ERR_OVERFLOW;
+        coeffs_m = (uint64_t *)malloc((size_t)8 * M * R * T);
+        enc_comb = (uint64_t *)malloc((size_t)8 * M * cw * T);
+        for (uint32_t t = 0; t < T && rc == ORC_OK; t++) {
+            uint64_t *cm = coeffs_m + (size_t)M * R * t;
+            for (uint32_t r = 0; r < R; r++)
+                orc_tr_get_integer_challenge(fs, p->n_limbs, coeffs + (size_t)p->n_limbs * r);
+            for (uint32_t c = 0; c < C; c++)
+                if (rs_read_integer(&rs, comb + (size_t)M * c, M)) rc = ORC_ERR_TRANSCRIPT;
+            for (uint32_t r = 0; r < R; r++) wi_sext(cm + (size_t)M * r, M, coeffs + (size_t)p->n_limbs * r, p->n_limbs);
+            if (rc == ORC_OK &&
+                orc_raa_encode_row(comb, M, C, p->rep, p->perm1, p->perm2, enc_comb + (size_t)M * cw * t, M) != ORC_OK)
+                rc = ORC_ERR_OVERFLOW;
+        }
         free(coeffs);
         free(comb);
     }
@@ -1201,9 +1206,11 @@ int orc_verify(const orc_params *p, const orc_field *f, const uint8_t *roots,
         if (R > 1) {
             uint64_t *ce = (uint64_t *)malloc((size_t)8 * M * R);
             for (uint32_t r = 0; r < R; r++) wi_sext(ce + (size_t)M * r, M, cv + (size_t)K * r, K);
-            if (inner_product_int(coeffs_m, ce, R, M, lhs)) rc = ORC_ERR_OVERFLOW;
+            for (uint32_t t = 0; t < T && rc == ORC_OK; t++) { /* every test on this column, :89-97 */
+                if (inner_product_int(coeffs_m + (size_t)M * R * t, ce, R, M, lhs)) rc = ORC_ERR_OVERFLOW;
+                if (rc == ORC_OK && memcmp(lhs, enc_comb + ((size_t)cw * t + col) * M, 8 * M) != 0) rc = ORC_ERR_PROOF;
+            }
             free(ce);
-            if (rc == ORC_OK && memcmp(lhs, enc_comb + (size_t)M * col, 8 * M) != 0) rc = ORC_ERR_PROOF;
         }
         /* ColumnOpening::verify_column, pcs/utils.rs:235-249.  The reference discards
          * the result (verify_z.rs:99) and stops reading the column's remaining proofs

@@ -13,6 +13,7 @@ both neighbours of a pair, the sorted list and the eighths per XCD.)
   C  (4096, 64, 8192)            13      scalar<1, 13>: the benchmark's instance, `has3` on wave 0
   D  (8192, 64, 16384)           14      scalar<1, 14> under STREAM=0 RPB=32 (by default this geometry gathers without
                                          an image, through open_columns_ilv_kernel<false, 1>: unchanged)
+                                         scalar<2, 14> under STREAM=0 RPB=64: D commits in one chunk of 64 rows
   RPB=64                                 scalar<2, D>: two passes per block
   RPB=40                                 blocks of 40 + 24 rows: not whole, open_columns_ilv_kernel's general loop"""
 import functools
@@ -36,6 +37,7 @@ KNOBS = {
     "rpb64": {"ZIP_HIP_GATHER_RPB": "64"},
     "rpb40": {"ZIP_HIP_GATHER_RPB": "40"},
     "image32": {"ZIP_HIP_GATHER_STREAM": "0", "ZIP_HIP_GATHER_RPB": "32"},
+    "image64": {"ZIP_HIP_GATHER_STREAM": "0", "ZIP_HIP_GATHER_RPB": "64"},
 }
 # 1, W - 1, W, W + 1, 2 W + 3 (8 does not divide them: the table is the sorted list), 8 | n (an eighth of the sorted
 # list per XCD: 1, 6 and 125 entries each), and the protocol's count
@@ -44,7 +46,8 @@ PATHS = ["commit_open", "hinted"]
 _CASES = ([(g, "none", n) for g in "BC" for n in COUNTS]
           + [(g, "rpb64", n) for g in "BC" for n in (WALK + 1, 48, 1000)]
           + [("C", "rpb40", 2 * WALK + 3), ("C", "rpb40", 48)]
-          + [("D", "image32", n) for n in (2 * WALK + 3, 1000)])
+          + [("D", "image32", n) for n in (2 * WALK + 3, 1000)]
+          + [("D", "image64", n) for n in (13, 1000)])  # scalar<2, 14>: D's one chunk of 64 rows as one block per opening
 
 
 @pytest.fixture(scope="module")

@@ -34,6 +34,22 @@ def test_oracle_stream_with_T_proximity_tests(num_vars, T):
         orc.lib().orc_tr_get_u64(orc.C.byref(px.copy_transcript(i.fs_after)))
 
 
+@pytest.mark.parametrize("T", [1, 2, 5, 8])
+def test_oracle_verifier_runs_every_proximity_test(T):
+    """orc_verify reads T proximity rows and holds every opened column to every one of them (verify_z.rs:66-103): its
+    own proof passes; a bit in any single u'_t, a T - 1 test stream and a T + 1 test stream do not."""
+    i = px.instance(9, T, n_cols=N_COLS, seed=9)
+    check = lambda z, proof: z.verify(i.f, i.roots, i.point, i.ev, proof)
+    assert check(i.z, i.proof) == 0
+    for t in range(T):
+        bad = i.proof.copy()
+        bad[(t * i.C + i.C - 1) * 64 + 9] ^= 1
+        assert check(i.z, bad) == orc.ORC_ERR_PROOF, t
+    for other in (T - 1, T + 1):
+        if other >= 1:
+            assert check(px.instance(9, other, n_cols=N_COLS, seed=9).z, i.proof) != 0, other
+
+
 @pytest.mark.parametrize("T", [1, 3])
 def test_oracle_one_row_matrix_has_no_test(T):
     """num_rows == 1 (open_z.rs:100): no proximity row, no coefficient squeezed, whatever T is."""
