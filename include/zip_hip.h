@@ -50,7 +50,9 @@ extern "C" {
  * zip_ccs_batch_* entry points: the Spartan tables of many proofs of one circuit, beside zip_ccs.  So are
  * zip_batch_commit_codes, zip_batch_open_eval_fields, zip_batch_open_fields and zip_batch_codes_counts: a batch whose
  * members have their own code and field, beside the shared-code batch that is unchanged.  So are zip_batch_verify_codes,
- * zip_batch_verify_codes_counts and zip_ccs_batch_eval_matrices: the verifier's side of such a batch.) */
+ * zip_batch_verify_codes_counts and zip_ccs_batch_eval_matrices: the verifier's side of such a batch.  So is
+ * zip_field_map_int, and so is the admission of (n_limbs, k_limbs, m_limbs) = (2, 8, 16) by zip_ctx_create: a triple that
+ * was refused is now served, every call on a (1, 4, 8) ctx means what it meant.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -79,9 +81,9 @@ typedef struct {
                             * supported: codeword_len <= 65536 (num_vars <= 30 at rep 2, <= 28 at rep 4);
                             * larger codewords exceed the 96-bit lanes: ZIP_ERR_UNSUPPORTED */
     uint32_t rep;          /* repetition factor (power of two)       code.rs:235-237 */
-    uint32_t n_limbs;      /* ZipTypes::N limbs, must be 1           traits/types.rs:225-240 */
-    uint32_t k_limbs;      /* ZipTypes::K limbs, must be 4 */
-    uint32_t m_limbs;      /* ZipTypes::M limbs, must be 8 */
+    uint32_t n_limbs;      /* ZipTypes::N limbs, must be 1 or 2      traits/types.rs:225-240 */
+    uint32_t k_limbs;      /* ZipTypes::K limbs, must be 4 (8 with n_limbs 2) */
+    uint32_t m_limbs;      /* ZipTypes::M limbs, must be 8 (16 with n_limbs 2); any other triple: ZIP_ERR_UNSUPPORTED */
     const uint32_t *perm1; /* HOST, codeword_len entries, a permutation of [0, codeword_len) */
     const uint32_t *perm2; /* HOST, codeword_len entries */
     int32_t device;        /* HIP device ordinal */
@@ -95,6 +97,36 @@ typedef struct {
     uint32_t limbs;      /* FIELD_LIMBS: 2, 3 or 4 */
     uint64_t modulus[8]; /* little-endian limbs, odd */
 } zip_field;
+
+/* ---- Two-limb witnesses: INT_LIMBS = 2 (src/field/int.rs:276-288: N = Int<2>, K = Int<8>, M = Int<16>) ------------------
+ * A ctx created with (n_limbs, k_limbs, m_limbs) = (2, 8, 16) commits, opens and verifies polynomials whose coefficients
+ * are 128-bit two's complement: two little-endian u64 limbs per value.  Every `const int64_t *evals` / `coeffs` argument
+ * of the calls below then points at 2 limbs per value (n_evals still COUNTS coefficients, ZIP_ERR_SHAPE as before; coeffs
+ * are full-range Int<2> challenges, get_integer_challenge(2)), and every size in this header that names k_limbs / m_limbs
+ * holds with 8 / 16:
+ *   rows        row_count * cw * 8 u64 (zip_commitment_device_ptrs, zip_commit_download, zip_commitment_upload); a leaf is
+ *               BLAKE3 of the 64-byte entry (int.rs:201-210), one compression as for Int<4>
+ *   u'          row_len * 16 u64 (zip_open_testing; row_len * 128 bytes at the head of the stream when num_rows > 1)
+ *   stream      [u' : row_len * 128 B, only if num_rows > 1] [n_cols x (num_rows x 64 B values, num_rows x {be64(depth),
+ *               depth x 32 B})] [row_len field elements]: zip_proof_len with k_limbs 8, m_limbs 16
+ * Served: zip_commit (with_merkle 0 and 1), zip_commit_hinted and zip_commit_open (same roots and bytes as zip_commit then
+ * zip_open; the hint is ignored, such a commit always stores every entry and every tree node, and the ctx never hints
+ * itself whatever zip_ctx_set_speculation or ZIP_HIP_SPECULATE say), zip_commitment_device_ptrs / zip_commit_download /
+ * zip_commitment_upload, zip_open_testing, zip_open_eval, zip_open_columns, zip_open, zip_mle_eval,
+ * zip_commitment_mle_eval, zip_verify (the same verdict order and the same two deliberate deviations), zip_proof_len.
+ * Codewords: every power of two up to 65536, the bound of the one-limb ctx (the scan lanes are 192 bits; honest entries
+ * need 128 + 2 log2(codeword_len) <= 160).
+ * The FieldMap of such a ctx (src/conversion.rs:86-100 over src/field.rs:536-568; zip_field_map_int pins both):
+ *   witness, Int<2>   W = FIELD_LIMBS words: for a modulus with its top bit set the signed-modulus reading (see
+ *                     zip_open_eval) reduces |w| modulo 2^(64 limbs) - q first, whenever that is <= |w| -- up to 2^127,
+ *                     so moduli that no 64-bit witness touches are touched here (q = 2^256 - 2^100 - 1); a two-limb
+ *                     modulus below 2^127 is a real reduction of |w|
+ *   entries, Int<8>   W = 8 > FIELD_LIMBS in the verifier: |v| mod q of the 512-bit magnitude, then the sign; never the quirk
+ * REFUSED with ZIP_ERR_UNSUPPORTED, a zip_ctx_last_error text that says "two-limb", and no launch: row shards
+ * (row_begin / row_count in zip_ctx_create, which has no ctx to leave a text in; zip_open_shard; zip_sum_partials),
+ * zip_ctx_set_proximity_tests above 1, zip_commit_open_begin, zip_open_stream, zip_batch_commit, zip_batch_commit_codes,
+ * zip_batch_verify, zip_batch_verify_codes (the other zip_batch_* calls take a batch, which such a ctx cannot make), and
+ * zip_mctx_create with such params.  The ctx stays usable after a refusal. */
 
 int32_t zip_abi_version(void);
 const char *zip_strerror(int32_t code);
@@ -772,6 +804,13 @@ void zip_ccs_batch_counts(uint64_t *kernel_launches, uint64_t *instances);
 /* Diagnostic: FieldMap for Int<4> (src/conversion.rs:86-100) of n arbitrary 256-bit values, as the
  * verifier applies it to column entries.  values: HOST n*4 limbs; out: HOST n*limbs Montgomery limbs. */
 int32_t zip_field_map_int256(zip_ctx *ctx, const uint64_t *values, uint32_t n, const zip_field *field, uint64_t *out);
+/* The same diagnostic for the two maps of a two-limb ctx (see "Two-limb witnesses" above): value_limbs == 2, the Int<2>
+ * witness map (W = FIELD_LIMBS: the signed-modulus reading applies when the modulus has its top bit set, for
+ * 2^(64 limbs) - q up to 2^127); value_limbs == 8, the verifier's map of Int<8> column entries (W = 8: |v| mod q of a
+ * 512-bit magnitude, then the sign, never the quirk).  values: HOST n * value_limbs limbs; out: HOST n * limbs Montgomery
+ * limbs.  Works on any ctx; another value_limbs is ZIP_ERR_UNSUPPORTED.  Additive: the ABI version stays 3. */
+int32_t zip_field_map_int(zip_ctx *ctx, const uint64_t *values, uint32_t n, uint32_t value_limbs, const zip_field *field,
+                          uint64_t *out);
 
 /* z_mle.map_to_field(config).evaluate(r_y) (src/zinc/prover.rs:317-319, poly_f/mle/dense.rs:35-41),
  * the step ZincProver runs between commit and open: <q0-combination of the rows, q1>.

@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = (
     "zip_open_columns", "zip_open_eval", "zip_proof_len", "zip_open", "zip_open_shard", "zip_sum_partials", "zip_merkle_trees",
     "zip_ctx_set_profiling", "zip_ctx_profile_read", "zip_ctx_commit_clock",
     "zip_mctx_create", "zip_mctx_destroy", "zip_mctx_last_error", "zip_mctx_shards", "zip_mctx_shard_ctx", "zip_mctx_set_witness",
-    "zip_mctx_commit_open", "zip_mctx_shard_openings", "zip_mctx_ends", "zip_mctx_roots", "zip_mctx_roots_path", "zip_verify", "zip_mle_eval", "zip_commitment_mle_eval", "zip_field_map_int256",
+    "zip_mctx_commit_open", "zip_mctx_shard_openings", "zip_mctx_ends", "zip_mctx_roots", "zip_mctx_roots_path", "zip_verify", "zip_mle_eval", "zip_commitment_mle_eval", "zip_field_map_int256", "zip_field_map_int",
     "zip_open_stream", "zip_sumcheck_init", "zip_sumcheck_round", "zip_sumcheck_round_begin", "zip_sumcheck_round_end", "zip_sumcheck_last_error", "zip_sumcheck_free",
     "zip_sumcheck_prove", "zip_sumcheck_launch_counts", "zip_sumcheck_grid_counts", "zip_sumcheck_init_products",
     "zip_sumcheck_prove_batch", "zip_sumcheck_batch_counts",
@@ -236,6 +236,8 @@ def lib():
     L.zip_mle_eval.argtypes = [vp, i64p, C.c_int, u64p, u64p, C.POINTER(ZipField), u64p]
     L.zip_commitment_mle_eval.argtypes = [vp, u64p, u64p, C.POINTER(ZipField), u64p]
     L.zip_field_map_int256.argtypes = [vp, u64p, C.c_uint32, C.POINTER(ZipField), u64p]
+    L.zip_field_map_int.argtypes = [vp, u64p, C.c_uint32, C.c_uint32, C.POINTER(ZipField), u64p]
+    L.zip_field_map_int.restype = C.c_int32
     L.zip_open_stream.argtypes = [vp, i64p, C.c_int, i64p, u32p, C.c_uint32, u64p, C.POINTER(ZipField), PROOF_SINK,
                                   vp, C.c_size_t]
     L.zip_sumcheck_init.argtypes = [C.c_int32, vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SumcheckComb),
@@ -386,6 +388,15 @@ def _ptr(x):
     raise TypeError(type(x))
 
 
+def _ints(x):
+    """Integer challenges / witness values for the ABI's `const int64_t *`: int64 as it is, uint64 limbs (the two-limb
+    form, [n, 2]) reinterpreted, anything else converted to int64."""
+    a = np.ascontiguousarray(x)
+    if a.dtype == np.uint64:
+        return a.view(np.int64)
+    return a if a.dtype == np.int64 else a.astype(np.int64)
+
+
 def geometry(num_vars, rep=2):
     """RaaCode::new + MultilinearZip::setup geometry (code_raa.rs:43,113; structs.rs:82)."""
     n = 1 << num_vars
@@ -414,7 +425,7 @@ class ZipContext:
         self.depth = max(cw - 1, 0).bit_length() if cw > 1 else 0
         self.rows_local = row_count or num_rows
         self.row_begin = row_begin
-        self.k_limbs, self.m_limbs = k_limbs, m_limbs
+        self.n_limbs, self.k_limbs, self.m_limbs = n_limbs, k_limbs, m_limbs
         self._perm1 = np.ascontiguousarray(perm1, dtype=np.uint32)
         self._perm2 = np.ascontiguousarray(perm2, dtype=np.uint32)
         p = ZipParams(num_vars, row_len, num_rows, cw, rep, n_limbs, k_limbs, m_limbs,
@@ -449,12 +460,17 @@ class ZipContext:
     def stream(self):
         return lib().zip_ctx_stream(self._h)
 
+    def _n_evals(self, evals):
+        """Coefficients in a witness array: a two-limb ctx (n_limbs=2) takes [n, 2] uint64 / int64 limbs per value."""
+        return (evals.size if isinstance(evals, np.ndarray) else evals.numel()) // self.n_limbs
+
     def commit(self, evals, with_merkle=True, want_roots=True, hint_cols=None):
-        """MultilinearZip::commit / commit_no_merkle.  evals: int64 numpy array or CUDA tensor.
+        """MultilinearZip::commit / commit_no_merkle.  evals: int64 numpy array or CUDA tensor ([n, 2] limbs on a
+        two-limb ctx).
         hint_cols: the column indices the caller is going to open (zip_commit_hinted): same roots, same handle, but
         the kernel skips the stores no opening of those columns reads."""
         ptr, kind = _ptr(evals)
-        n = evals.size if isinstance(evals, np.ndarray) else evals.numel()
+        n = self._n_evals(evals)
         roots = np.zeros((self.rows_local, 32), dtype=np.uint8) if (with_merkle and want_roots) else None
         h = C.c_void_p()
         rp = roots.ctypes.data if roots is not None else None
@@ -504,9 +520,9 @@ class ZipContext:
         """zip_commit_open: MultilinearZip::commit + open in one call (prover.rs:305-328).
         -> (proof, roots or None, Commitment or None)."""
         ptr, kind = _ptr(evals)
-        n = evals.size if isinstance(evals, np.ndarray) else evals.numel()
+        n = self._n_evals(evals)
         cols = np.ascontiguousarray(cols, dtype=np.uint32)
-        coeffs_c = np.ascontiguousarray(coeffs, dtype=np.int64) if coeffs is not None else None
+        coeffs_c = _ints(coeffs) if coeffs is not None else None
         q0 = np.ascontiguousarray(q0_mont, dtype=np.uint64) if q0_mont is not None else None
         roots = np.zeros((self.rows_local, 32), dtype=np.uint8) if want_roots else None
         res = out if out is not None else np.zeros(self.proof_len(cols.size, field.limbs), dtype=np.uint8)
@@ -525,9 +541,9 @@ class ZipContext:
         same buffers pays the numpy / ctypes conversions, ~10 us, once instead of per proof).  The arrays are kept alive by
         the returned function; `evals` and `out` are read / written in place at every call."""
         ptr, kind = _ptr(evals)
-        n = evals.size if isinstance(evals, np.ndarray) else evals.numel()
+        n = self._n_evals(evals)
         cols = np.ascontiguousarray(cols, dtype=np.uint32)
-        coeffs_c = np.ascontiguousarray(coeffs, dtype=np.int64) if coeffs is not None else None
+        coeffs_c = _ints(coeffs) if coeffs is not None else None
         q0 = np.ascontiguousarray(q0_mont, dtype=np.uint64) if q0_mont is not None else None
         optr, okind = _ptr(out)
         fn = lib().zip_commit_open
@@ -575,9 +591,9 @@ class ZipContext:
         """The proximity rows alone.  coeffs [num_rows], or [T, num_rows] on a ctx set to T > 1 proximity tests (and
         num_rows > 1); the result is then [T, row_len, m_limbs]."""
         ptr, kind = _ptr(evals)
-        coeffs = np.ascontiguousarray(coeffs, dtype=np.int64)
+        coeffs = _ints(coeffs)
         t = self.proximity_tests if self.num_rows > 1 else 1
-        assert coeffs.size == t * self.rows_local
+        assert coeffs.size == t * self.rows_local * self.n_limbs
         shape = (self.row_len, self.m_limbs) if t == 1 else (t, self.row_len, self.m_limbs)
         res = out if out is not None else np.zeros(shape, dtype=np.uint64)
         optr, okind = _ptr(res)
@@ -601,7 +617,7 @@ class ZipContext:
         [T, num_rows] on a ctx set to T > 1 proximity tests."""
         roots_c = np.ascontiguousarray(roots, dtype=np.uint8)
         cols_c = np.ascontiguousarray(cols, dtype=np.uint32)
-        coeffs_c = None if coeffs is None else np.ascontiguousarray(coeffs, dtype=np.int64)
+        coeffs_c = None if coeffs is None else _ints(coeffs)
         q0 = None if q0_mont is None else np.ascontiguousarray(q0_mont, dtype=np.uint64)
         q1 = None if q1_mont is None else np.ascontiguousarray(q1_mont, dtype=np.uint64)
         ev = np.ascontiguousarray(eval_mont, dtype=np.uint64)
@@ -709,6 +725,15 @@ class ZipContext:
         out = np.zeros((v.shape[0], field.limbs), dtype=np.uint64)
         self._check(lib().zip_field_map_int256(self._h, v.ctypes.data, v.shape[0], C.byref(field), out.ctypes.data),
                     "zip_field_map_int256")
+        return out
+
+    def field_map_int(self, values, value_limbs, field: ZipField):
+        """zip_field_map_int: phi of [n, value_limbs] uint64 limbs, value_limbs 2 (the two-limb witness map) or 8 (the
+        verifier's map of a two-limb ctx's column entries) -> [n, field.limbs] Montgomery limbs."""
+        v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, value_limbs)
+        out = np.zeros((v.shape[0], field.limbs), dtype=np.uint64)
+        self._check(lib().zip_field_map_int(self._h, v.ctypes.data, v.shape[0], value_limbs, C.byref(field), out.ctypes.data),
+                    "zip_field_map_int")
         return out
 
     def proof_len(self, n_cols, field_limbs):
@@ -1020,7 +1045,7 @@ class Commitment:
         c = self.ctx
         ptr, kind = _ptr(evals)
         cols = np.ascontiguousarray(cols, dtype=np.uint32)
-        coeffs_c = np.ascontiguousarray(coeffs, dtype=np.int64) if coeffs is not None else None
+        coeffs_c = _ints(coeffs) if coeffs is not None else None
         cp = coeffs_c.ctypes.data if coeffs_c is not None else None
         q0 = np.ascontiguousarray(q0_mont, dtype=np.uint64) if q0_mont is not None else None
         total = c.proof_len(cols.size, field.limbs)

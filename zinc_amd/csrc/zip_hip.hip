@@ -38,6 +38,7 @@
 #include "kernels_spartan.cuh"
 #include "kernels_spartan_batch.cuh"
 #include "kernels_prime.cuh"
+#include "kernels_two_limb.cuh"
 #include "rccl_dyn.h"
 
 using namespace zipk;
@@ -2860,6 +2861,536 @@ int32_t launch_batch_combine_fields_fl(zip_ctx *ctx, const BatchCombineArgs &a, 
 }
 }  // namespace
 
+// ------------------------------------------------------------------ INT_LIMBS = 2 (kernels_two_limb.cuh)
+// The single-context PCS path of a ctx created with (n_limbs, k_limbs, m_limbs) = (2, 8, 16).  The exported calls branch
+// here before they reach any one-limb dispatcher.  Everything runs on ctx->stream, one launch after the other: a two-limb
+// commit always materialises every row entry (Int<8>, the reference's layout) and every tree, there is no hint, no
+// speculation and no chunk pipeline, so a handle is complete the moment the stream has drained (c->done stays null).
+namespace {
+
+bool two_limb(const zip_ctx *ctx) { return ctx->p.n_limbs == 2; }
+
+// The paths that are not built for such a ctx answer ZIP_ERR_UNSUPPORTED before anything reaches the device
+int32_t refuse_two_limb(zip_ctx *ctx, const char *what) {
+    if (two_limb(ctx)) return fail(ctx, ZIP_ERR_UNSUPPORTED, "%s is not built for a two-limb ctx (n_limbs = 2)", what);
+    return ZIP_OK;
+}
+
+// field_from_int128's qm: 2^(64 FL) - q when the modulus has its top bit set and that value is below 2^128 (only then
+// can it be <= |w| for a 128-bit w), else 0
+u128 tl_quirk_mod(const HostField &hf) {
+    if (!(hf.modulus[hf.fl - 1] >> 63)) return 0;
+    uint64_t m[8] = {0};
+    sub_limbs(m, hf.modulus, hf.fl);
+    for (uint32_t i = 2; i < hf.fl; i++)
+        if (m[i]) return 0;
+    return ((u128)m[1] << 64) | m[0];
+}
+
+// R^(i+2) mod q, i = 0 .. ceil(8 / FL) - 1: what field_from_int512 multiplies chunk i of a 512-bit magnitude by
+template <int FL>
+Phi8Consts<FL> tl_phi8_consts(const HostField &hf) {
+    Phi8Consts<FL> pc;
+    uint64_t x[8] = {0};
+    memcpy(x, hf.r2, 8 * FL);
+    for (int c = 0; c < Phi8Consts<FL>::N; c++) {
+        if (c)
+            for (int i = 0; i < 64 * FL; i++) dbl_mod(x, hf.modulus, FL);
+        for (int i = 0; i < FL; i++) pc.p[c][i] = x[i];
+    }
+    return pc;
+}
+
+int32_t tl_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, zip_mem_kind evals_kind, int32_t with_merkle,
+                  uint8_t *roots_out, zip_commitment **out) {
+    if (!ctx || !out) return ZIP_ERR_NULL;
+    *out = nullptr;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    const uint32_t R = ctx->rows_local, C = ctx->p.row_len, cw = ctx->p.codeword_len;
+    if (n_evals != (size_t)R * C)
+        return fail(ctx, ZIP_ERR_SHAPE,
+                    "Polynomial has an incorrect number of evaluations (%zu) for the expected matrix size (%zu)",
+                    n_evals, (size_t)R * C);
+    if (!evals) return fail(ctx, ZIP_ERR_NULL, "evals is NULL");
+    zip_commitment *c = new (std::nothrow) zip_commitment();
+    if (!c) return ZIP_ERR_ALLOC;
+    c->ctx = ctx;
+    int32_t rc = ZIP_OK;
+    do {
+        c->rows_bytes = (size_t)R * cw * 64;
+        if ((rc = pool_alloc(ctx, c->rows_bytes, (void **)&c->rows))) break;
+        if (with_merkle) {
+            c->layers_bytes = (size_t)R * 2 * cw * 32;
+            c->roots_bytes = (size_t)R * 32;
+            if ((rc = pool_alloc(ctx, c->layers_bytes, (void **)&c->layers))) break;
+            if ((rc = pool_alloc(ctx, c->roots_bytes, (void **)&c->roots))) break;
+        }
+        const uint64_t *evals_d = reinterpret_cast<const uint64_t *>(evals);
+        if (evals_kind == ZIP_MEM_HOST) {
+            c->evals_bytes = n_evals * 16;
+            if ((rc = pool_alloc(ctx, c->evals_bytes, (void **)&c->evals))) break;
+            if ((rc = copy_h2d_bounced(ctx, c->evals, evals, c->evals_bytes, ctx->stream))) break;
+            evals_d = reinterpret_cast<const uint64_t *>(c->evals);
+        }
+        // Workgroups of the launch: at most four per CU (16 of the CU's 32 wave slots), and no more than keep the t1
+        // scratch rows (cw * 24 bytes each) of all of them within 128 MiB, half the Infinity Cache: 1024 workgroups up to
+        // cw 4096, 682 at cw 8192, 85 at cw 65536.  Whether fewer, L2-sized sets of rows would be faster was not measured.
+        const uint64_t scratch_cap = ((uint64_t)128 << 20) / ((uint64_t)cw * kTlLane * 8);
+        const uint32_t G = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)R, (uint64_t)ctx->num_cus * 4u, scratch_cap}));
+        Scratch t1(ctx);
+        if ((rc = t1.get((size_t)G * cw * kTlLane * 8))) break;
+        TlEncodeArgs a{};
+        a.evals = evals_d;
+        a.perm1 = ctx->perm1_d;
+        a.perm2 = ctx->perm2_d;
+        a.t1 = t1.as<uint64_t>();
+        a.rows = c->rows;
+        a.layers = c->layers;
+        a.num_rows = R;
+        a.row_len = C;
+        a.cw = cw;
+        {
+            LaunchTimer t(ctx, "tl_encode_rows_kernel");
+            if (with_merkle) hipLaunchKernelGGL(tl_encode_rows_kernel<true>, dim3(G), dim3(256), 0, ctx->stream, a);
+            else hipLaunchKernelGGL(tl_encode_rows_kernel<false>, dim3(G), dim3(256), 0, ctx->stream, a);
+            hipError_t e = hipGetLastError();
+            if (e != hipSuccess) { rc = fail(ctx, ZIP_ERR_HIP, "tl_encode_rows_kernel: %s", hipGetErrorString(e)); break; }
+        }
+        if (with_merkle && (rc = merkle_upper_levels(ctx, ctx->stream, c->layers, c->roots, R, cw, 0, ctx->depth))) break;
+        if (with_merkle && roots_out) {
+            if ((rc = deliver(ctx, roots_out, ZIP_MEM_HOST, c->roots, c->roots_bytes))) break;
+        } else if (evals_kind == ZIP_MEM_HOST) {
+            hipError_t e = stream_wait(ctx->stream);
+            if (e != hipSuccess) { rc = fail(ctx, ZIP_ERR_HIP, "two-limb commit: %s", hipGetErrorString(e)); break; }
+        }
+    } while (0);
+    if (rc) {
+        const std::string keep = ctx->last_error;
+        (void)stream_wait(ctx->stream);  // nothing may still write the blocks when they return to the pool
+        zip_commitment_free(c);
+        ctx->last_error = keep;
+        return rc;
+    }
+    *out = c;
+    return ZIP_OK;
+}
+
+struct TlCombineOut {
+    uint64_t *uprime = nullptr;     // device, [row_len][16]
+    uint64_t *row_limbs = nullptr;  // device, [row_len][FL]
+    uint8_t *row_be = nullptr;      // device, big-endian stream bytes
+};
+
+template <int FL>
+int32_t tl_run_combine_fl(zip_ctx *ctx, TlCombineArgs a, const HostField *hf, bool do_int, bool do_field, const TlCombineOut &o) {
+    const uint32_t R = a.num_rows, C = a.row_len;
+    const uint32_t bx = (C + 63) / 64;
+    const uint32_t by = std::max(1u, std::min((R + 3) / 4, 2048u / std::min(bx, 2048u)));
+    Scratch parts(ctx);
+    int32_t rc = parts.get((size_t)by * C * (kTlAcc + FL) * 8);
+    if (rc) return rc;
+    a.part_int = parts.as<uint64_t>();
+    a.part_f = a.part_int + (size_t)by * C * kTlAcc;
+    FieldDev<FL> fd{};
+    if (do_field) {
+        fd = to_dev<FL>(*hf);
+        const u128 qm = tl_quirk_mod(*hf);
+        a.qm_lo = (uint64_t)qm;
+        a.qm_hi = (uint64_t)(qm >> 64);
+    }
+    const dim3 grid(bx, by), block(256);
+    {
+        LaunchTimer t(ctx, "tl_combine_kernel");
+        if (do_int && do_field) hipLaunchKernelGGL((tl_combine_kernel<FL, true, true>), grid, block, 0, ctx->stream, a, fd);
+        else if (do_int) hipLaunchKernelGGL((tl_combine_kernel<FL, true, false>), grid, block, 0, ctx->stream, a, fd);
+        else hipLaunchKernelGGL((tl_combine_kernel<FL, false, true>), grid, block, 0, ctx->stream, a, fd);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    LaunchTimer t(ctx, "tl_combine_finalize_kernel");
+    hipLaunchKernelGGL(tl_combine_finalize_kernel<FL>, dim3((C + 255) / 256), dim3(256), 0, ctx->stream, a.part_int, a.part_f, by, C,
+                       do_int ? o.uprime : nullptr, do_field ? o.row_limbs : nullptr, do_field ? o.row_be : nullptr, fd);
+    HIP_TRY(ctx, hipGetLastError());
+    return ZIP_OK;
+}
+
+// Both row combinations of a two-limb witness in one pass (either may be switched off).  Device pointers throughout.
+int32_t tl_run_combine(zip_ctx *ctx, const uint64_t *evals_d, const uint64_t *coeffs_dv, const uint64_t *q0_dv, const HostField *hf,
+                       bool do_int, bool do_field, const TlCombineOut &o) {
+    if (!do_int && !do_field) return ZIP_OK;
+    TlCombineArgs a{};
+    a.evals = evals_d;
+    a.coeffs = coeffs_dv;
+    a.q0 = q0_dv;
+    a.num_rows = ctx->rows_local;
+    a.row_len = ctx->p.row_len;
+    return with_fl(do_field ? hf->fl : 4u,
+                   [&](auto FL) { return tl_run_combine_fl<decltype(FL)::value>(ctx, a, hf, do_int, do_field, o); });
+}
+
+int32_t tl_open_testing(zip_ctx *ctx, const int64_t *evals, zip_mem_kind evals_kind, const int64_t *coeffs, uint64_t *uprime_out,
+                        zip_mem_kind out_kind) {
+    Scratch ev(ctx), res(ctx), small(ctx);
+    const int64_t *evals_d;
+    int32_t rc;
+    if ((rc = stage_evals(ctx, evals, evals_kind, (size_t)ctx->rows_local * ctx->p.row_len * 2, ev, &evals_d))) return rc;
+    const size_t bytes = (size_t)ctx->p.row_len * ctx->p.m_limbs * 8;
+    TlCombineOut o;
+    o.uprime = uprime_out;
+    if (out_kind != ZIP_MEM_DEVICE) {
+        if ((rc = res.get(bytes))) return rc;
+        o.uprime = res.as<uint64_t>();
+    }
+    SmallInputs si;
+    si.src[0] = coeffs;
+    si.bytes[0] = (size_t)ctx->rows_local * 16;
+    unsigned char *sb;
+    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
+    if ((rc = tl_run_combine(ctx, reinterpret_cast<const uint64_t *>(evals_d), reinterpret_cast<const uint64_t *>(sb + si.off[0]),
+                             nullptr, nullptr, true, false, o)))
+        return rc;
+    if (out_kind == ZIP_MEM_HOST) return deliver(ctx, uprime_out, ZIP_MEM_HOST, o.uprime, bytes);
+    HIP_TRY(ctx, stream_wait(ctx->stream));  // coeffs were read from host memory
+    return ZIP_OK;
+}
+
+// row_out != null: the evaluation row (Montgomery limbs); value_out != null: <row, q1>, the witness MLE at the point
+int32_t tl_open_eval(zip_ctx *ctx, const int64_t *evals, zip_mem_kind evals_kind, const uint64_t *q0_mont, const uint64_t *q1_mont,
+                     const zip_field *field, uint64_t *row_out, zip_mem_kind out_kind, uint64_t *value_out) {
+    HostField hf;
+    int32_t rc;
+    if ((rc = make_field(ctx, field, &hf))) return rc;
+    const uint32_t R = ctx->rows_local, C = ctx->p.row_len;
+    const bool single = ctx->p.num_rows == 1;
+    if (!single && !q0_mont) return fail(ctx, ZIP_ERR_NULL, "q0_mont is NULL");
+    if (value_out && C > 1 && !q1_mont) return fail(ctx, ZIP_ERR_NULL, "q1_mont is NULL");
+    Scratch ev(ctx), res(ctx), small(ctx), dot(ctx);
+    const int64_t *evals_d;
+    if ((rc = stage_evals(ctx, evals, evals_kind, (size_t)R * C * 2, ev, &evals_d))) return rc;
+    const size_t bytes = (size_t)C * hf.fl * 8;
+    TlCombineOut o;
+    o.row_limbs = row_out;
+    if (!row_out || out_kind != ZIP_MEM_DEVICE) {
+        if ((rc = res.get(bytes))) return rc;
+        o.row_limbs = res.as<uint64_t>();
+    }
+    // one row: the evaluation row is map_to_field(evals) = 1_mont (x) phi(w) (open_z.rs:84-88)
+    SmallInputs si;
+    si.src[1] = single ? hf.r : q0_mont;
+    si.bytes[1] = (size_t)R * hf.fl * 8;
+    if (value_out) {
+        si.src[3] = C > 1 ? (const void *)q1_mont : (const void *)hf.r;  // a one-column matrix evaluates to its entry
+        si.bytes[3] = (size_t)C * hf.fl * 8;
+    }
+    unsigned char *sb;
+    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
+    if ((rc = tl_run_combine(ctx, reinterpret_cast<const uint64_t *>(evals_d), nullptr, reinterpret_cast<const uint64_t *>(sb + si.off[1]),
+                             &hf, false, true, o)))
+        return rc;
+    if (value_out) {
+        if ((rc = dot.get(64))) return rc;
+        {
+            LaunchTimer t(ctx, "field_dot_kernel");
+            const uint64_t *q1d = reinterpret_cast<const uint64_t *>(sb + si.off[3]);
+            with_fl(hf.fl, [&](auto FL) {
+                constexpr int N = decltype(FL)::value;
+                hipLaunchKernelGGL(field_dot_kernel<N>, dim3(1), dim3(1024), 0, ctx->stream, o.row_limbs, q1d, C, dot.as<uint64_t>(),
+                                   to_dev<N>(hf));
+            });
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        return deliver(ctx, value_out, ZIP_MEM_HOST, dot.ptr, (size_t)hf.fl * 8);
+    }
+    if (out_kind == ZIP_MEM_HOST) return deliver(ctx, row_out, ZIP_MEM_HOST, o.row_limbs, bytes);
+    HIP_TRY(ctx, stream_wait(ctx->stream));
+    return ZIP_OK;
+}
+
+int32_t tl_launch_open_columns(zip_commitment *c, const uint32_t *cols_dv, uint32_t n_cols, uint8_t *out_d) {
+    zip_ctx *ctx = c->ctx;
+    if (!n_cols) return ZIP_OK;
+    TlOpenColsArgs a{};
+    a.rows = c->rows;
+    a.layers = c->layers;
+    a.cols = cols_dv;
+    a.out = out_d;
+    a.num_rows = ctx->rows_local;
+    a.cw = ctx->p.codeword_len;
+    a.depth = ctx->depth;
+    a.n_cols = n_cols;
+    const uint64_t total = (uint64_t)n_cols * a.num_rows * (a.depth + 2);
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, (uint64_t)ctx->num_cus * 64);
+    LaunchTimer t(ctx, "tl_open_columns_kernel");
+    hipLaunchKernelGGL(tl_open_columns_kernel, dim3(blocks), dim3(256), 0, ctx->stream, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return ZIP_OK;
+}
+
+int32_t tl_open_columns(zip_commitment *c, const uint32_t *cols, uint32_t n_cols, uint8_t *wire_out, zip_mem_kind out_kind) {
+    zip_ctx *ctx = c->ctx;
+    if (!c->layers) return fail(ctx, ZIP_ERR_INVALID_PARAM, "commitment has no Merkle trees (commit_no_merkle)");
+    const size_t bytes = (size_t)n_cols * column_bytes(ctx);
+    Scratch res(ctx), small(ctx);
+    uint8_t *out_d = wire_out;
+    int32_t rc;
+    if (out_kind == ZIP_MEM_HOST) {
+        if ((rc = res.get(bytes))) return rc;
+        out_d = res.as<uint8_t>();
+    }
+    if ((rc = check_cols(ctx, cols, n_cols))) return rc;
+    SmallInputs si;
+    si.src[0] = cols;
+    si.bytes[0] = (size_t)n_cols * 4;
+    unsigned char *sb;
+    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
+    if ((rc = tl_launch_open_columns(c, reinterpret_cast<const uint32_t *>(sb), n_cols, out_d))) return rc;
+    if (out_kind == ZIP_MEM_HOST) return deliver(ctx, wire_out, ZIP_MEM_HOST, out_d, bytes);
+    HIP_TRY(ctx, stream_wait(ctx->stream));  // cols were read from host memory
+    return ZIP_OK;
+}
+
+// The whole stream of MultilinearZip::open into out_d (device): [u' if num_rows > 1][openings][evaluation row].
+// Synchronises: the small host inputs have been consumed on return.
+int32_t tl_open_device(zip_commitment *c, const uint64_t *evals_d, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols,
+                       const uint64_t *q0_mont, const HostField &hf, uint8_t *out_d) {
+    zip_ctx *ctx = c->ctx;
+    const bool single = ctx->p.num_rows == 1;
+    const size_t u_bytes = uprime_bytes(ctx), col_bytes = (size_t)n_cols * column_bytes(ctx);
+    Scratch small(ctx);
+    SmallInputs si;
+    if (!single) {
+        si.src[0] = coeffs;
+        si.bytes[0] = (size_t)ctx->rows_local * 16;
+    }
+    si.src[1] = single ? hf.r : q0_mont;
+    si.bytes[1] = (size_t)ctx->rows_local * hf.fl * 8;
+    si.src[2] = cols;
+    si.bytes[2] = (size_t)n_cols * 4;
+    unsigned char *sb;
+    int32_t rc;
+    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
+    TlCombineOut o;
+    o.uprime = single ? nullptr : reinterpret_cast<uint64_t *>(out_d);
+    o.row_be = out_d + u_bytes + col_bytes;
+    if ((rc = tl_run_combine(ctx, evals_d, reinterpret_cast<const uint64_t *>(sb + si.off[0]),
+                             reinterpret_cast<const uint64_t *>(sb + si.off[1]), &hf, !single, true, o)))
+        return rc;
+    if ((rc = tl_launch_open_columns(c, reinterpret_cast<const uint32_t *>(sb + si.off[2]), n_cols, out_d + u_bytes))) return rc;
+    HIP_TRY(ctx, stream_wait(ctx->stream));
+    return ZIP_OK;
+}
+
+int32_t tl_open(zip_commitment *c, const int64_t *evals, zip_mem_kind evals_kind, const int64_t *coeffs, const uint32_t *cols,
+                uint32_t n_cols, const uint64_t *q0_mont, const zip_field *field, uint8_t *proof_out, zip_mem_kind out_kind) {
+    zip_ctx *ctx = c->ctx;
+    if (!c->layers) return fail(ctx, ZIP_ERR_INVALID_PARAM, "commitment has no Merkle trees (commit_no_merkle)");
+    HostField hf;
+    int32_t rc;
+    if ((rc = make_field(ctx, field, &hf))) return rc;
+    if (ctx->p.num_rows > 1 && (!coeffs || !q0_mont)) return fail(ctx, ZIP_ERR_NULL, "coeffs / q0_mont is NULL");
+    Scratch ev(ctx), res(ctx);
+    const int64_t *evals_d = c->evals;  // witness retained by a host-side commit
+    if (evals) {
+        if ((rc = stage_evals(ctx, evals, evals_kind, (size_t)ctx->rows_local * ctx->p.row_len * 2, ev, &evals_d))) return rc;
+    } else if (!evals_d) {
+        return fail(ctx, ZIP_ERR_NULL, "evals is NULL and the commitment retains no witness");
+    }
+    const size_t total = zip_proof_len(ctx, n_cols, hf.fl);
+    uint8_t *out_d = proof_out;
+    if (out_kind == ZIP_MEM_HOST) {
+        if ((rc = res.get(total))) return rc;
+        out_d = res.as<uint8_t>();
+    }
+    if ((rc = check_cols(ctx, cols, n_cols))) return rc;
+    if ((rc = tl_open_device(c, reinterpret_cast<const uint64_t *>(evals_d), coeffs, cols, n_cols, q0_mont, hf, out_d))) return rc;
+    if (out_kind == ZIP_MEM_HOST) return deliver(ctx, proof_out, ZIP_MEM_HOST, out_d, total);
+    return ZIP_OK;
+}
+
+int32_t tl_commit_open(zip_ctx *ctx, const int64_t *evals, size_t n_evals, zip_mem_kind evals_kind, const int64_t *coeffs,
+                       const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont, const zip_field *field, uint8_t *roots_out,
+                       uint8_t *proof_out, zip_mem_kind out_kind, zip_commitment **out) {
+    HostField hf;
+    int32_t rc;
+    if ((rc = make_field(ctx, field, &hf))) return rc;
+    if (ctx->p.num_rows > 1 && (!coeffs || !q0_mont)) return fail(ctx, ZIP_ERR_NULL, "coeffs / q0_mont is NULL");
+    if ((rc = check_cols(ctx, cols, n_cols))) return rc;
+    const size_t total = zip_proof_len(ctx, n_cols, hf.fl);
+    Scratch res(ctx);
+    uint8_t *out_d = proof_out;
+    if (out_kind == ZIP_MEM_HOST) {
+        if ((rc = res.get(total))) return rc;
+        out_d = res.as<uint8_t>();
+    }
+    zip_commitment *c = nullptr;
+    if ((rc = tl_commit(ctx, evals, n_evals, evals_kind, 1, roots_out, &c))) return rc;
+    const uint64_t *evals_d = reinterpret_cast<const uint64_t *>(c->evals ? c->evals : evals);
+    rc = tl_open_device(c, evals_d, coeffs, cols, n_cols, q0_mont, hf, out_d);
+    if (!rc && out_kind == ZIP_MEM_HOST) rc = deliver(ctx, proof_out, ZIP_MEM_HOST, out_d, total);
+    if (rc || !out) {
+        const std::string keep = ctx->last_error;
+        zip_commitment_free(c);
+        ctx->last_error = keep;
+        return rc;
+    }
+    *out = c;
+    return ZIP_OK;
+}
+
+template <int FL>
+int32_t tl_run_verify_fl(zip_ctx *ctx, const uint8_t *proof_d, const uint64_t *coeffs_d, const uint64_t *q0_d, const uint32_t *cols_d,
+                         const uint64_t *q1_d, const uint32_t *roots_d, uint32_t n_cols, const HostField &hf,
+                         std::vector<uint32_t> &flags, std::vector<uint32_t> &bad, std::vector<uint32_t> &malformed, VerifyHead *cnt) {
+    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len;
+    constexpr int M = 16;
+    const bool single = R == 1;
+    const size_t u_bytes = uprime_bytes(ctx), cols_bytes = (size_t)n_cols * column_bytes(ctx);
+    Scratch enc_u(ctx), enc_f(ctx), tmp(ctx), row(ctx), misc(ctx);
+    int32_t rc;
+    if ((rc = enc_u.get((size_t)cw * M * 8))) return rc;
+    if ((rc = enc_f.get((size_t)cw * FL * 8))) return rc;
+    if ((rc = tmp.get((size_t)cw * M * 8))) return rc;
+    if ((rc = row.get((size_t)C * FL * 8))) return rc;
+    const size_t misc_bytes = sizeof(VerifyHead) + (size_t)3 * n_cols * 4;
+    if ((rc = misc.get(misc_bytes))) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(misc.ptr, 0, misc_bytes, ctx->stream));
+    VerifyHead *cnt_d = misc.as<VerifyHead>();
+    uint32_t *flags_d = reinterpret_cast<uint32_t *>(cnt_d + 1), *bad_d = flags_d + n_cols, *mal_d = bad_d + n_cols;
+    const FieldDev<FL> fd = to_dev<FL>(hf);
+    // encode_wide(u') over Int<16>, prefixes formed in 17 limbs (verify_z.rs:75-77)
+    if (!single) {
+        FieldDev<M> unused{};
+        if ((rc = launch_encode_row<M, false>(ctx, reinterpret_cast<const uint64_t *>(proof_d), tmp.as<uint64_t>(), enc_u.as<uint64_t>(),
+                                              unused, &cnt_d->overflow)))
+            return rc;
+    }
+    {
+        LaunchTimer t(ctx, "decode_field_row_kernel");
+        hipLaunchKernelGGL(decode_field_row_kernel<FL>, dim3((C + 255) / 256), dim3(256), 0, ctx->stream, proof_d + u_bytes + cols_bytes,
+                           C, row.as<uint64_t>(), &cnt_d->noncanonical, fd);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if ((rc = launch_encode_row<FL, true>(ctx, row.as<uint64_t>(), tmp.as<uint64_t>(), enc_f.as<uint64_t>(), fd, nullptr))) return rc;
+    if (C > 1) {  // q_1 of a one-column matrix is empty (pcs/utils.rs:253-276): <row, q1> is 0, nothing is staged for it
+        LaunchTimer t(ctx, "field_dot_kernel");
+        hipLaunchKernelGGL(field_dot_kernel<FL>, dim3(1), dim3(1024), 0, ctx->stream, row.as<uint64_t>(), q1_d, C, cnt_d->dot, fd);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    if (n_cols) {
+        TlVerifyColsArgs a{};
+        a.wire = proof_d + u_bytes;
+        a.cols = cols_d;
+        a.coeffs = single ? nullptr : coeffs_d;
+        a.q0 = single ? nullptr : q0_d;
+        a.roots = roots_d;
+        a.enc_int = single ? nullptr : enc_u.as<uint64_t>();
+        a.enc_f = enc_f.as<uint64_t>();
+        a.num_rows = R;
+        a.depth = ctx->depth;
+        a.n_cols = n_cols;
+        a.flags = flags_d;
+        a.bad_merkle = bad_d;
+        a.malformed = mal_d;
+        LaunchTimer t(ctx, "tl_verify_columns_kernel");
+        hipLaunchKernelGGL(tl_verify_columns_kernel<FL>, dim3(n_cols), dim3(256), 0, ctx->stream, a, fd, tl_phi8_consts<FL>(hf));
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    std::vector<unsigned char> host(misc_bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), misc.ptr, misc_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, stream_wait(ctx->stream));
+    memcpy(cnt, host.data(), sizeof(VerifyHead));
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(host.data() + sizeof(VerifyHead));
+    flags.assign(w, w + n_cols);
+    bad.assign(w + n_cols, w + 2 * n_cols);
+    malformed.assign(w + 2 * n_cols, w + 3 * n_cols);
+    return ZIP_OK;
+}
+
+// zip_verify for a two-limb ctx: the same facts, the same verdict order (verify_verdict)
+int32_t tl_verify(zip_ctx *ctx, const uint8_t *roots, const uint8_t *proof, zip_mem_kind proof_kind, size_t proof_len,
+                  const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont, const uint64_t *q1_mont,
+                  const uint64_t *eval_mont, const zip_field *field, zip_verify_report *report) {
+    HostField hf;
+    int32_t rc;
+    if ((rc = check_verify_args(ctx, coeffs, cols, n_cols, q0_mont, q1_mont, field, &hf))) return rc;
+    const size_t need = zip_proof_len(ctx, n_cols, hf.fl);
+    if (proof_len < need) {
+        report->verdict = ZIP_VERIFY_MALFORMED;
+        return ZIP_OK;
+    }
+    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len;
+    const bool single = R == 1;
+    Scratch pbuf(ctx), small(ctx);
+    const uint8_t *proof_d = proof;
+    if (proof_kind == ZIP_MEM_HOST) {
+        if ((rc = pbuf.get(need))) return rc;
+        if ((rc = copy_h2d_bounced(ctx, pbuf.ptr, proof, need, ctx->stream))) return rc;
+        proof_d = pbuf.as<uint8_t>();
+    }
+    SmallInputs si;
+    si.src[0] = coeffs;  si.bytes[0] = single ? 0 : (size_t)R * 16;
+    si.src[1] = q0_mont; si.bytes[1] = single ? 0 : (size_t)R * hf.fl * 8;
+    si.src[2] = cols;    si.bytes[2] = (size_t)n_cols * 4;
+    si.src[3] = q1_mont; si.bytes[3] = C > 1 ? (size_t)C * hf.fl * 8 : 0;
+    si.src[4] = roots;   si.bytes[4] = (size_t)R * 32;
+    unsigned char *sb;
+    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
+    std::vector<uint32_t> flags, bad, malformed;
+    VerifyHead cnt{};
+    if ((rc = with_fl(hf.fl, [&](auto FL) {
+             return tl_run_verify_fl<decltype(FL)::value>(
+                 ctx, proof_d, reinterpret_cast<const uint64_t *>(sb + si.off[0]), reinterpret_cast<const uint64_t *>(sb + si.off[1]),
+                 reinterpret_cast<const uint32_t *>(sb + si.off[2]), reinterpret_cast<const uint64_t *>(sb + si.off[3]),
+                 reinterpret_cast<const uint32_t *>(sb + si.off[4]), n_cols, hf, flags, bad, malformed, &cnt);
+         })))
+        return rc;
+    VerifyFacts x{};
+    x.overflow = cnt.overflow != 0;
+    x.first = x.first_q0 = kNoOpening;
+    for (uint32_t i = 0; i < n_cols; i++) {
+        report->bad_merkle_paths += bad[i];
+        report->malformed_paths += malformed[i];
+        const uint32_t why = opening_fails(flags[i], malformed[i], bad[i]);
+        if (why && x.first == kNoOpening) {
+            x.first = i;
+            x.first_why = why;
+        }
+        if ((flags[i] & 2u) && x.first_q0 == kNoOpening) x.first_q0 = i;
+    }
+    const uint64_t zero[4] = {0, 0, 0, 0};
+    x.eval_differs = memcmp(C > 1 ? cnt.dot : zero, eval_mont, 8 * hf.fl) != 0;
+    x.noncanonical = cnt.noncanonical != 0;
+    verify_verdict(x, *report);
+    return ZIP_OK;
+}
+
+int32_t tl_field_map_int(zip_ctx *ctx, const uint64_t *values, uint32_t n, uint32_t value_limbs, const zip_field *field, uint64_t *out) {
+    HostField hf;
+    int32_t rc;
+    if ((rc = make_field(ctx, field, &hf))) return rc;
+    Scratch in(ctx), res(ctx);
+    const size_t in_bytes = (size_t)n * value_limbs * 8;
+    if ((rc = in.get(in_bytes + 16))) return rc;
+    if ((rc = res.get((size_t)n * hf.fl * 8 + 16))) return rc;
+    if (!n) return ZIP_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(in.ptr, values, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const dim3 grid((n + 255) / 256), block(256);
+    const u128 qm = tl_quirk_mod(hf);
+    with_fl(hf.fl, [&](auto FL) {
+        constexpr int N = decltype(FL)::value;
+        if (value_limbs == 2)
+            hipLaunchKernelGGL(tl_field_map_int2_kernel<N>, grid, block, 0, ctx->stream, in.as<uint64_t>(), n, res.as<uint64_t>(),
+                               to_dev<N>(hf), (uint64_t)qm, (uint64_t)(qm >> 64));
+        else
+            hipLaunchKernelGGL(tl_field_map_int8_kernel<N>, grid, block, 0, ctx->stream, in.as<uint64_t>(), n, res.as<uint64_t>(),
+                               to_dev<N>(hf), tl_phi8_consts<N>(hf));
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    return deliver(ctx, out, ZIP_MEM_HOST, res.ptr, (size_t)n * hf.fl * 8);
+}
+
+}  // namespace
+
 extern "C" {
 
 int32_t zip_abi_version(void) { return ZIP_HIP_ABI_VERSION; }
@@ -2911,7 +3442,10 @@ int32_t zip_ctx_create(const zip_params *p, zip_ctx **out) {
     if (!p || !out) return ZIP_ERR_NULL;
     *out = nullptr;
     // ---- geometry checks (no GPU needed) ----
-    if (p->n_limbs != 1 || p->k_limbs != 4 || p->m_limbs != 8) return ZIP_ERR_UNSUPPORTED;
+    // Int<1> witnesses (N, K, M = 1, 4, 8) or Int<2> witnesses (2, 8, 16); a two-limb ctx has no row shards
+    const bool two = p->n_limbs == 2 && p->k_limbs == 8 && p->m_limbs == 16;
+    if (!two && (p->n_limbs != 1 || p->k_limbs != 4 || p->m_limbs != 8)) return ZIP_ERR_UNSUPPORTED;
+    if (two && (p->row_begin != 0 || (p->row_count != 0 && p->row_count != p->num_rows))) return ZIP_ERR_UNSUPPORTED;
     if (!is_pow2(p->row_len) || !is_pow2(p->rep) || !is_pow2(p->num_rows)) return ZIP_ERR_INVALID_PARAM;
     if ((uint64_t)p->row_len * p->rep != p->codeword_len) return ZIP_ERR_INVALID_PARAM;
     if (p->num_vars > 40 || (uint64_t)p->row_len * p->num_rows != (1ull << p->num_vars)) return ZIP_ERR_INVALID_PARAM;
@@ -2948,6 +3482,7 @@ int32_t zip_ctx_create(const zip_params *p, zip_ctx **out) {
     ctx->device = p->device;
     ctx->depth = ilog2(p->codeword_len);  // codeword_len.next_power_of_two().ilog2(), commit.rs:67
     ctx->rows_local = rows_local;
+    if (two) ctx->speculate = 0;  // a two-limb commit stores everything: nothing to hint (zip_ctx_set_speculation keeps it off)
     int32_t rc = ZIP_OK;
     do {
         if (hipSetDevice(ctx->device) != hipSuccess) { rc = ZIP_ERR_NO_DEVICE; break; }
@@ -3417,6 +3952,7 @@ static int32_t launch_witness_digest(zip_ctx *ctx, const int64_t *evals_d, size_
 int32_t zip_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, zip_mem_kind evals_kind,
                    int32_t with_merkle, uint8_t *roots_out, zip_commitment **out) {
     if (!ctx || !out) return ZIP_ERR_NULL;
+    if (two_limb(ctx)) return tl_commit(ctx, evals, n_evals, evals_kind, with_merkle, roots_out, out);
     std::shared_ptr<HintPlan> plan;
     {
         std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
@@ -3446,6 +3982,7 @@ int32_t zip_commit(zip_ctx *ctx, const int64_t *evals, size_t n_evals, zip_mem_k
 int32_t zip_ctx_set_speculation(zip_ctx *ctx, int32_t on) {
     if (!ctx) return ZIP_ERR_NULL;
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (two_limb(ctx)) return ZIP_OK;  // stays off: such a commit has no hinted form
     ctx->speculate = on ? 2 : 0;
     return ZIP_OK;
 }
@@ -3455,6 +3992,7 @@ int32_t zip_ctx_set_proximity_tests(zip_ctx *ctx, uint32_t n_tests) {
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
     if (n_tests < 1 || n_tests > 8)
         return fail(ctx, ZIP_ERR_UNSUPPORTED, "num_proximity_testing %u is outside the supported range 1 .. 8", n_tests);
+    if (n_tests > 1 && two_limb(ctx)) return refuse_two_limb(ctx, "more than one proximity test");
     if (n_tests > 1 && ctx->rows_local != ctx->p.num_rows)
         return fail(ctx, ZIP_ERR_UNSUPPORTED, "a row-sharded ctx serves one proximity test (got %u)", n_tests);
     ctx->n_tests = n_tests;
@@ -3470,6 +4008,8 @@ int32_t zip_commit_hinted(zip_ctx *ctx, const int64_t *evals, size_t n_evals, zi
         std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
         if (int32_t rc = check_cols(ctx, cols, n_cols)) return rc;
     }
+    // (a two-limb commit ignores the hint: it stores every entry and every node)
+    if (two_limb(ctx)) return tl_commit(ctx, evals, n_evals, evals_kind, 1, roots_out, out);
     static const uint32_t none = 0;
     return commit_impl(ctx, evals, n_evals, evals_kind, 1, cols ? cols : &none, n_cols, roots_out, out);
 }
@@ -3663,7 +4203,7 @@ int32_t zip_commitment_upload(zip_ctx *ctx, const uint64_t *rows, const uint8_t 
     c->ctx = ctx;
     int32_t rc = ZIP_OK;
     do {
-        c->rows_bytes = (size_t)R * cw * 32;
+        c->rows_bytes = (size_t)R * cw * 8 * ctx->p.k_limbs;  // Int<4> entries, Int<8> on a two-limb ctx
         if ((rc = pool_alloc(ctx, c->rows_bytes, (void **)&c->rows))) break;
         hipError_t e = hipMemcpyAsync(c->rows, rows, c->rows_bytes, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess && layers) {
@@ -3698,6 +4238,7 @@ int32_t zip_open_testing(zip_ctx *ctx, const int64_t *evals, zip_mem_kind evals_
     if (!ctx || !coeffs || !uprime_out) return ZIP_ERR_NULL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (two_limb(ctx)) return tl_open_testing(ctx, evals, evals_kind, coeffs, uprime_out, out_kind);
     Scratch ev(ctx), res(ctx);
     const int64_t *evals_d;
     int32_t rc;
@@ -3733,6 +4274,7 @@ int32_t zip_open_columns(zip_commitment *c, const uint32_t *cols, uint32_t n_col
     zip_ctx *ctx = c->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (two_limb(ctx)) return tl_open_columns(c, cols, n_cols, wire_out, out_kind);
     if (!c->layers) return fail(ctx, ZIP_ERR_INVALID_PARAM, "commitment has no Merkle trees (commit_no_merkle)");
     const size_t bytes = (size_t)n_cols * column_bytes(ctx);
     Scratch res(ctx);
@@ -3761,6 +4303,7 @@ int32_t zip_open_eval(zip_ctx *ctx, const int64_t *evals, zip_mem_kind evals_kin
     if (!ctx || !row_out) return ZIP_ERR_NULL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (two_limb(ctx)) return tl_open_eval(ctx, evals, evals_kind, q0_mont, nullptr, field, row_out, out_kind, nullptr);
     HostField hf;
     int32_t rc;
     if ((rc = make_field(ctx, field, &hf))) return rc;
@@ -3917,6 +4460,7 @@ int32_t zip_open(zip_commitment *c, const int64_t *evals, zip_mem_kind evals_kin
     zip_ctx *ctx = c->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (two_limb(ctx)) return tl_open(c, evals, evals_kind, coeffs, cols, n_cols, q0_mont, field, proof_out, out_kind);
     if (ctx->rows_local != ctx->p.num_rows)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_open needs an unsharded ctx; use the per-phase calls on a row shard");
     if (!c->layers) return fail(ctx, ZIP_ERR_INVALID_PARAM, "commitment has no Merkle trees (commit_no_merkle)");
@@ -3957,6 +4501,7 @@ int32_t zip_open_shard(zip_commitment *c, const int64_t *evals_d, const int64_t 
     zip_ctx *ctx = c->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (int32_t r = refuse_two_limb(ctx, "zip_open_shard")) return r;
     if (!c->layers) return fail(ctx, ZIP_ERR_INVALID_PARAM, "commitment has no Merkle trees (commit_no_merkle)");
     HostField hf;
     int32_t rc;
@@ -3998,6 +4543,8 @@ int32_t zip_commit_open(zip_ctx *ctx, const int64_t *evals, size_t n_evals, zip_
     if (out) *out = nullptr;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (two_limb(ctx))
+        return tl_commit_open(ctx, evals, n_evals, evals_kind, coeffs, cols, n_cols, q0_mont, field, roots_out, proof_out, out_kind, out);
     if (ctx->rows_local != ctx->p.num_rows)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_commit_open needs an unsharded ctx");
     HostField hf;
@@ -4051,6 +4598,7 @@ int32_t zip_commit_open_begin(zip_ctx *ctx, const int64_t *evals_d, size_t n_eva
     *out = nullptr;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (int32_t r = refuse_two_limb(ctx, "zip_commit_open_begin")) return r;
     if (ctx->rows_local != ctx->p.num_rows) return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_commit_open_begin needs an unsharded ctx");
     HostField hf;
     int32_t rc;
@@ -4164,6 +4712,7 @@ static int32_t batch_commit_impl(zip_ctx *ctx, const int64_t *evals, size_t n_ev
     *out = nullptr;
     if (codes && (!perms1 || !perms2)) return ZIP_ERR_NULL;
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (int32_t r = refuse_two_limb(ctx, codes ? "zip_batch_commit_codes" : "zip_batch_commit")) return r;
     const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len;
     if (n_polys == 0 || n_polys > 65535)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "a batch holds 1 .. 65535 polynomials (got %u)", n_polys);
@@ -4623,6 +5172,7 @@ void zip_mctx_destroy(zip_mctx *m) {
 int32_t zip_mctx_create(const zip_params *p, int32_t n_devices, const int32_t *devices, zip_mctx **out) {
     if (!p || !out || !devices) return ZIP_ERR_NULL;
     *out = nullptr;
+    if (p->n_limbs == 2 && p->k_limbs == 8 && p->m_limbs == 16) return ZIP_ERR_UNSUPPORTED;  // a two-limb ctx has no row shards
     if (n_devices < 1 || (uint32_t)n_devices > p->num_rows || n_devices > 64) return ZIP_ERR_INVALID_PARAM;
     zip_mctx *m = new (std::nothrow) zip_mctx();
     if (!m) return ZIP_ERR_ALLOC;
@@ -4979,6 +5529,8 @@ int32_t zip_verify(zip_ctx *ctx, const uint8_t *roots, const uint8_t *proof, zip
     memset(report, 0, sizeof *report);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (two_limb(ctx))
+        return tl_verify(ctx, roots, proof, proof_kind, proof_len, coeffs, cols, n_cols, q0_mont, q1_mont, eval_mont, field, report);
     if (ctx->rows_local != ctx->p.num_rows)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_verify needs an unsharded ctx");
     HostField hf;
@@ -5028,6 +5580,7 @@ int32_t zip_batch_verify(zip_ctx *ctx, uint32_t n_polys, const uint8_t *roots, c
                          const uint64_t *q1_mont, const uint64_t *evals_mont, const zip_field *field, zip_verify_report *reports) {
     if (!ctx || !roots || !proofs || !reports || !evals_mont || (n_cols && !cols)) return ZIP_ERR_NULL;
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (int32_t r = refuse_two_limb(ctx, "zip_batch_verify")) return r;
     const uint32_t R = ctx->p.num_rows, cw = ctx->p.codeword_len;
     if (n_polys == 0 || n_polys > 65535)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "a batch holds 1 .. 65535 polynomials (got %u)", n_polys);
@@ -5068,6 +5621,7 @@ int32_t zip_batch_verify_codes(zip_ctx *ctx, uint32_t n_polys, const uint32_t *p
     if (!ctx || !roots || !proofs || !proof_lens || !reports || !evals_mont || (n_cols && !cols)) return ZIP_ERR_NULL;
     if (!perms1 || !perms2) return ZIP_ERR_NULL;
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (int32_t r = refuse_two_limb(ctx, "zip_batch_verify_codes")) return r;
     const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, cw = ctx->p.codeword_len;
     if (n_polys == 0 || n_polys > 65535)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "a batch holds 1 .. 65535 polynomials (got %u)", n_polys);
@@ -5202,6 +5756,7 @@ int32_t zip_mle_eval(zip_ctx *ctx, const int64_t *evals, zip_mem_kind evals_kind
     if (!ctx || !value_out) return ZIP_ERR_NULL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (two_limb(ctx)) return tl_open_eval(ctx, evals, evals_kind, q0_mont, q1_mont, field, nullptr, ZIP_MEM_HOST, value_out);
     if (ctx->rows_local != ctx->p.num_rows)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_mle_eval needs an unsharded ctx");
     HostField hf;
@@ -5260,6 +5815,17 @@ int32_t zip_field_map_int256(zip_ctx *ctx, const uint64_t *values, uint32_t n, c
     return deliver(ctx, out, ZIP_MEM_HOST, res.ptr, (size_t)n * hf.fl * 8);
 }
 
+// Diagnostic beside zip_field_map_int256: phi of Int<2> (the two-limb witness map) and Int<8> (the verifier's map of a
+// two-limb ctx's column entries) values, on any ctx
+int32_t zip_field_map_int(zip_ctx *ctx, const uint64_t *values, uint32_t n, uint32_t value_limbs, const zip_field *field, uint64_t *out) {
+    if (!ctx || !values || !out) return ZIP_ERR_NULL;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (value_limbs != 2 && value_limbs != 8)
+        return fail(ctx, ZIP_ERR_UNSUPPORTED, "zip_field_map_int maps Int<2> and Int<8> values (got %u limbs)", value_limbs);
+    return tl_field_map_int(ctx, values, n, value_limbs, field, out);
+}
+
 int32_t zip_open_stream(zip_commitment *c, const int64_t *evals, zip_mem_kind evals_kind, const int64_t *coeffs,
                         const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont, const zip_field *field,
                         zip_proof_sink sink, void *user, size_t chunk_bytes) {
@@ -5267,6 +5833,7 @@ int32_t zip_open_stream(zip_commitment *c, const int64_t *evals, zip_mem_kind ev
     zip_ctx *ctx = c->ctx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (int32_t r = refuse_two_limb(ctx, "zip_open_stream")) return r;
     if (ctx->rows_local != ctx->p.num_rows)
         return fail(ctx, ZIP_ERR_INVALID_PARAM, "zip_open_stream needs an unsharded ctx");
     if (!c->layers) return fail(ctx, ZIP_ERR_INVALID_PARAM, "commitment has no Merkle trees (commit_no_merkle)");
@@ -6231,6 +6798,7 @@ int32_t zip_sum_partials(zip_ctx *ctx, const uint64_t *uparts, const uint64_t *f
     if (!ctx) return ZIP_ERR_NULL;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    if (int32_t r = refuse_two_limb(ctx, "zip_sum_partials")) return r;  // (the partials of row shards, which such a ctx has not)
     if ((uparts && !uprime_out) || (fparts && !row_out)) return ZIP_ERR_NULL;
     HostField hf;
     hf.fl = 4;
