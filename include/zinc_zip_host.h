@@ -55,6 +55,22 @@ int32_t zinc_transcript_import(zinc_transcript *t, const uint64_t *st, const uin
 int32_t zinc_get_prime(zinc_transcript *t, uint32_t limbs, int32_t device, uint64_t *prime_out, uint32_t *candidates_tried_out);
 int32_t zinc_draw_random_field(const int64_t *public_input, size_t l, zinc_transcript *t, uint32_t limbs, int32_t device,
                                uint64_t *modulus_out);
+/* The same for the n members of a batch of proofs, each on its own transcript.  From the line profiles/prime_batch.md sets
+ * on (per limb count; ZIP_HIP_PRIME_MIN_BATCH=n, n >= 2, moves it) the draws are ONE zip_get_prime_batch call, chains and
+ * tests on the device; below it, for one member and with ZIP_HIP_BATCH=0 they are the loop over zinc_get_prime.  Both give
+ * the same bytes and the same errors.
+ *   zinc_get_prime_batch              primes_out n * limbs limbs, member-major; candidates_tried_out n entries or NULL
+ *   zinc_draw_random_field_batch      member i absorbs public_inputs[i][0 .. lens[i]) first; moduli_out n * limbs limbs
+ *   zinc_verifier_check_field_batch   the check of Verifier::verify (:53-57) per member: same_out[i] = 1 when the field
+ *                                     drawn at limbs[i] limbs is moduli[4 i ..]; every transcript is left where
+ *                                     zinc_verifier_verify_checked's check leaves it.  The members of one limb count are
+ *                                     one zinc_draw_random_field_batch. */
+int32_t zinc_get_prime_batch(zinc_transcript *const *transcripts, uint32_t n, uint32_t limbs, int32_t device, uint64_t *primes_out,
+                             uint32_t *candidates_tried_out);
+int32_t zinc_draw_random_field_batch(const int64_t *const *public_inputs, const size_t *lens, zinc_transcript *const *transcripts,
+                                     uint32_t n, uint32_t limbs, int32_t device, uint64_t *moduli_out);
+int32_t zinc_verifier_check_field_batch(const int64_t *const *public_inputs, const size_t *lens, zinc_transcript *const *transcripts,
+                                        uint32_t n, const uint64_t *moduli, const uint32_t *limbs, int32_t device, uint8_t *same_out);
 
 /* field helpers (src/field/config.rs, src/conversion.rs, src/sumcheck/utils.rs) */
 int32_t zinc_field_constants(const uint64_t *modulus, uint32_t limbs, uint64_t *r, uint64_t *r2, uint64_t *inv);
@@ -348,6 +364,17 @@ int32_t zinc_verifier_verify_batch(const zinc_linear_code_spec *spec, const zip_
                                    const uint8_t *const *roots, const size_t *n_roots, const uint64_t *v,
                                    const uint8_t *const *pcs_proofs, const size_t *pcs_proof_lens, int32_t *results_out,
                                    char *messages_out, size_t message_cap);
+/* The same with the field check of Verifier::verify first (ZincVerifier::verify_batch_checked):
+ * zinc_verifier_check_field_batch over all members, then zinc_verifier_verify_batch over those that passed.  A member
+ * that failed the check has ZINC_ERR_FIELD_CONFIG in results_out and its transcript where the check left it. */
+int32_t zinc_verifier_verify_batch_checked(const int64_t *const *public_inputs, const size_t *public_input_lens,
+                                           const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t,
+                                           uint32_t s, uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c,
+                                           uint32_t n_instances, zinc_transcript *const *transcripts, const uint64_t *moduli,
+                                           const uint32_t *limbs, int32_t device, const uint64_t *msgs1, const uint64_t *msgs2,
+                                           const uint64_t *v_s, const uint8_t *const *roots, const size_t *n_roots, const uint64_t *v,
+                                           const uint8_t *const *pcs_proofs, const size_t *pcs_proof_lens, int32_t *results_out,
+                                           char *messages_out, size_t message_cap);
 
 /* ZincVerifier (src/zinc/verifier.rs): SpartanVerifier::verify (:105-139), and with with_pcs != 0 also
  * verify_pcs_proof (:221-273: RaaCode::new from the transcript, MultilinearZip::verify, the matrix MLEs at

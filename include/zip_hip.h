@@ -52,7 +52,8 @@ extern "C" {
  * members have their own code and field, beside the shared-code batch that is unchanged.  So are zip_batch_verify_codes,
  * zip_batch_verify_codes_counts and zip_ccs_batch_eval_matrices: the verifier's side of such a batch.  So is
  * zip_field_map_int, and so is the admission of (n_limbs, k_limbs, m_limbs) = (2, 8, 16) by zip_ctx_create: a triple that
- * was refused is now served, every call on a (1, 4, 8) ctx means what it meant.) */
+ * was refused is now served, every call on a (1, 4, 8) ctx means what it meant.  So are zip_get_prime_batch and
+ * zip_prime_batch_counts: the fields of a whole batch in one launch set, beside zip_get_prime that is unchanged.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -688,6 +689,38 @@ int32_t zip_prime_test_base2(int32_t device, const uint64_t *candidates, uint32_
 int32_t zip_get_prime(int32_t device, zip_keccak_state *transcript, uint32_t limbs, uint64_t *prime_out,
                       uint32_t *candidates_tried_out);
 void zip_prime_launch_counts(uint64_t *launches, uint64_t *candidates_tested);
+
+/* zip_get_prime_batch: get_prime::<RandomField<limbs>> on n INDEPENDENT transcripts -- the fields of a whole batch of
+ * proofs (zip_ccs_batch_*, zip_sumcheck_prove_batch, zip_batch_commit_codes, zip_batch_verify_codes: each member lives in
+ * the field drawn from its own transcript).  Member i gets exactly what zip_get_prime(device, &transcripts[i], limbs, ...)
+ * gives on its own: the same prime, the same 1-based winner position, the same sponge afterwards (the winner's state,
+ * pending bytes and buflen; nothing of the candidates hashed beyond the winner).
+ * Here the candidate chains run on the device too, one member per lane: a call proceeds in rounds of w candidates per
+ * member still without a prime -- chain, test (the kernel of zip_prime_test_base2), a per-member reduction, and a replay
+ * that walks each finished member's sponge to its winner.  The kernel launches of a call depend on the rounds its LONGEST
+ * chain needs, not on n; one host synchronisation per round; one copy of the sponges up and one copy of primes, positions
+ * and sponges back.
+ *   transcripts           HOST, n entries, in/out
+ *   primes_out            HOST, n * limbs little-endian limbs, member-major
+ *   candidates_tried_out  HOST, n entries; may be NULL
+ * Errors, answered before any device is looked for and in this order:
+ *   ZIP_ERR_NULL           transcripts or primes_out is NULL
+ *   ZIP_ERR_INVALID_PARAM  limbs not in {2, 3, 4}
+ *   ZIP_ERR_INVALID_PARAM  n == 0 or n > 65535
+ *   ZIP_ERR_INVALID_PARAM  a member with buflen >= 136
+ * ZIP_ERR_UNSUPPORTED: some member has no probable prime among its first 65536 candidates (one line on stderr).
+ * On EVERY non-zero return all n transcripts are byte-for-byte unchanged and zip_prime_batch_counts has not moved.
+ * ZIP_HIP_PRIME_BATCH_WINDOW=w (1 .. 1024, default 64) sets the candidates per member and round; read per call, anything
+ * else keeps the default.  zip_get_prime, zip_prime_test_base2, zip_prime_launch_counts and ZIP_HIP_PRIME_BATCH are
+ * untouched: a batch call moves its own counters only.
+ * Not part of this: members of differing limb counts in one call, more than one device per call.
+ *
+ * zip_prime_batch_counts: process-wide, monotonic -- successful zip_get_prime_batch calls, the members they served and
+ * the kernel launches they made (four per round).  Any pointer may be NULL.
+ * Additive: the ABI version stays 3. */
+int32_t zip_get_prime_batch(int32_t device, zip_keccak_state *transcripts, uint32_t n, uint32_t limbs, uint64_t *primes_out,
+                            uint32_t *candidates_tried_out);
+void zip_prime_batch_counts(uint64_t *calls, uint64_t *members, uint64_t *kernel_launches);
 
 /* ---- the field loops of SpartanProver::prove around its sumchecks (BASELINE configs[4]) ---------
  * A zip_ccs holds the constraint matrices of a CCS (Statement_Z.constraints, src/ccs/ccs_z.rs:155-158,

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "zip_batch_verify", "zip_batch_verify_calls", "zip_batch_verify_codes", "zip_batch_verify_codes_counts",
     "zip_batch_commit_codes", "zip_batch_open_eval_fields", "zip_batch_open_fields", "zip_batch_codes_counts",
     "zip_prime_test_base2", "zip_get_prime", "zip_prime_launch_counts",
+    "zip_get_prime_batch", "zip_prime_batch_counts",
 )
 
 
@@ -261,6 +262,10 @@ def lib():
     L.zip_get_prime.restype = C.c_int32
     L.zip_prime_launch_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.zip_prime_launch_counts.restype = None
+    L.zip_get_prime_batch.argtypes = [C.c_int32, C.POINTER(KeccakState), C.c_uint32, C.c_uint32, u64p, C.POINTER(C.c_uint32)]
+    L.zip_get_prime_batch.restype = C.c_int32
+    L.zip_prime_batch_counts.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.zip_prime_batch_counts.restype = None
     L.zip_sumcheck_last_error.argtypes = [vp]
     L.zip_sumcheck_last_error.restype = C.c_char_p
     L.zip_sumcheck_free.argtypes = [vp]
@@ -1182,6 +1187,32 @@ def prime_launch_counts():
     a, b = C.c_uint64(0), C.c_uint64(0)
     lib().zip_prime_launch_counts(C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+def get_prime_batch(states, limbs: int, device: int = 0):
+    """zip_get_prime_batch: get_prime on every transcript of `states` (a sequence of KeccakState) in one launch set; each
+    state is updated in place to what the reference's loop leaves.  -> (primes [n, limbs] uint64, little-endian limbs;
+    tried [n] uint32, each winner's 1-based position in its chain)."""
+    n = len(states)
+    arr = (KeccakState * max(n, 1))()
+    for i, s in enumerate(states):
+        C.memmove(C.byref(arr[i]), C.byref(s), C.sizeof(KeccakState))
+    primes = np.zeros((n, limbs), dtype=np.uint64)
+    tried = np.zeros(n, dtype=np.uint32)
+    rc = lib().zip_get_prime_batch(device, arr, n, limbs, primes.ctypes.data if n else None,
+                                   tried.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc != ZIP_OK:
+        raise ZipError(rc, "zip_get_prime_batch")
+    for i, s in enumerate(states):
+        C.memmove(C.byref(s), C.byref(arr[i]), C.sizeof(KeccakState))
+    return primes, tried
+
+
+def prime_batch_counts():
+    """(successful zip_get_prime_batch calls, members they served, kernel launches they made) in this process so far"""
+    a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    lib().zip_prime_batch_counts(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
 
 
 class Sumcheck:

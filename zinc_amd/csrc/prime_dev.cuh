@@ -189,6 +189,74 @@ inline void prime_next_candidate(TrSponge &sp, uint64_t (&cand)[FL]) {
     }
 }
 
+// The same step word-wise, for the device and the host alike (prime_chain_batch_kernel, kernels_prime_batch.cuh: one
+// member of a batch per lane, `buflen` differs per lane).  No byte addressing and no variable index into st / blk: the
+// rate words a step touches are picked by comparison over the 17 words, as prime_bit picks a limb.
+//   1. the clone absorbs the counter 0: four zero bytes change no pending word, they only move buflen -- across the
+//      rate boundary from 132 on, where the clone's block is absorbed first;
+//   2./3. finalize (tr_finalize_word) and one permutation: d;
+//   4. the first 8 FL digest bytes go to byte offset buflen: with q = buflen / 8 and s = 8 (buflen % 8), word q + k of
+//      the (two-block) rate gets d[k] << s | d[k - 1] >> (64 - s), k = 0 .. FL; words 17 .. 17 + FL are words 0 .. FL
+//      of the next block (136 = 17 * 8: the block boundary is a word boundary);
+//   5./6. the candidate big-endian, minus 1 if even.
+template <int FL>
+ZK_HD void prime_next_candidate_words(TrSponge &sp, uint64_t (&cand)[FL]) {
+    uint64_t d[25];
+    uint32_t cl = sp.buflen + 4;
+    if (cl >= kKeccakRate) {  // the clone's block fills: st ^ blk permuted, nothing pending but zero bytes
+#pragma unroll
+        for (uint32_t w = 0; w < 25; w++) d[w] = w < kKeccakRateWords ? sp.st[w] ^ sp.blk[w] : sp.st[w];
+        keccak_f1600(d);
+        cl -= kKeccakRate;
+        d[0] ^= (uint64_t)0x01 << (8 * cl);  // cl <= 3: the pad's first byte is in word 0
+        d[kKeccakRateWords - 1] ^= (uint64_t)0x80 << 56;
+    } else {
+#pragma unroll
+        for (uint32_t w = 0; w < 25; w++) d[w] = tr_finalize_word(sp.st, sp.blk, cl, w);
+    }
+    keccak_f1600(d);
+
+    const uint32_t q = sp.buflen / 8, s = 8 * (sp.buflen % 8);
+    uint64_t piece[FL + 1];  // piece[k] belongs to word q + k
+#pragma unroll
+    for (int k = 0; k <= FL; k++) {
+        const uint64_t lo = k < FL ? d[k] << s : 0;
+        const uint64_t hi = k > 0 ? (d[k - 1] >> 1) >> (63 - s) : 0;  // d[k - 1] >> (64 - s), 0 for s == 0
+        piece[k] = lo | hi;
+    }
+    uint64_t next[FL + 1];  // words 0 .. FL of the block after this one
+#pragma unroll
+    for (int i = 0; i <= FL; i++) next[i] = 0;
+#pragma unroll
+    for (int k = 0; k <= FL; k++) {
+#pragma unroll
+        for (uint32_t w = 0; w < kKeccakRateWords; w++)
+            if (w == q + (uint32_t)k) sp.blk[w] |= piece[k];
+#pragma unroll
+        for (int i = 0; i <= FL; i++)
+            if (kKeccakRateWords + (uint32_t)i == q + (uint32_t)k) next[i] |= piece[k];
+    }
+    sp.buflen += 8 * FL;
+    if (sp.buflen >= kKeccakRate) {
+#pragma unroll
+        for (uint32_t w = 0; w < kKeccakRateWords; w++) {
+            sp.st[w] ^= sp.blk[w];
+            sp.blk[w] = w <= (uint32_t)FL ? next[w] : 0;
+        }
+        keccak_f1600(sp.st);
+        sp.buflen -= kKeccakRate;
+    }
+
+#pragma unroll
+    for (int k = 0; k < FL; k++) cand[FL - 1 - k] = keccak_bswap64(d[k]);
+    if (!(cand[0] & 1)) {
+        uint64_t one[FL];
+#pragma unroll
+        for (int i = 0; i < FL; i++) one[i] = i == 0 ? 1 : 0;
+        tr_sub<FL>(cand, one);
+    }
+}
+
 // ZIP_HIP_PRIME_BATCH: candidates per launch, 1 .. max.  Anything else -- unset, empty, not all digits, out of range --
 // leaves the default.
 inline uint32_t prime_batch_knob(const char *text, uint32_t def, uint32_t max) {

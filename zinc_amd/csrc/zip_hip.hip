@@ -38,6 +38,7 @@
 #include "kernels_spartan.cuh"
 #include "kernels_spartan_batch.cuh"
 #include "kernels_prime.cuh"
+#include "kernels_prime_batch.cuh"
 #include "kernels_two_limb.cuh"
 #include "rccl_dyn.h"
 
@@ -2491,6 +2492,8 @@ struct PrimeDev {
     std::mutex mu;  // one call at a time per device
     hipStream_t stream = nullptr;
     unsigned char *host = nullptr, *dev = nullptr;
+    unsigned char *batch_dev = nullptr;  // zip_get_prime_batch: grown to the largest call so far, up to kPrimeBatchKeepBytes
+    size_t batch_bytes = 0;
 };
 PrimeDev g_prime[kMaxDevices];
 // Process-wide (zip_prime_launch_counts): launches of prime_test_base2_kernel and the candidates they tested
@@ -2532,9 +2535,11 @@ void prime_dev_release(int device) {  // (the device is current)
     std::lock_guard<std::mutex> g(pd.mu);
     if (pd.stream) (void)hipStreamSynchronize(pd.stream);
     if (pd.dev) (void)hipFree(pd.dev);
+    if (pd.batch_dev) (void)hipFree(pd.batch_dev);
     if (pd.host) (void)hipHostFree(pd.host);
     if (pd.stream) (void)hipStreamDestroy(pd.stream);
-    pd.dev = pd.host = nullptr;
+    pd.dev = pd.host = pd.batch_dev = nullptr;
+    pd.batch_bytes = 0;
     pd.stream = nullptr;
 }
 
@@ -2614,6 +2619,118 @@ int32_t get_prime_fl(PrimeDev &pd, zip_keccak_state *transcript, uint32_t batch,
     fprintf(stderr, "zip_get_prime: no probable prime among the first %u candidates of %d limbs; giving up\n",
             kPrimeMaxCandidates, FL);
     return ZIP_ERR_UNSUPPORTED;
+}
+
+// ---- zip_get_prime_batch: get_prime on n independent transcripts, the candidate chains on the device ---------------------
+// (kernels_prime_batch.cuh.)  A round is w candidates per live member and four launches: chain, test, reduce, replay;
+// then the number of members still live comes back -- the one host synchronisation of the round.  The launches of a call
+// therefore follow the rounds of its longest chain, not n.  One copy of the sponges up, one copy of [winners' sponges |
+// primes | positions] back.  One device block per call: [A | B | result | candidates | live lists, steps, counts |
+// verdicts]; a block of up to kPrimeBatchKeepBytes stays with the device for the next call, a larger one is freed.
+constexpr uint32_t kPrimeBatchDefaultWindow = 64, kPrimeBatchMaxWindow = 1024, kPrimeBatchMaxMembers = 65535;
+constexpr size_t kPrimeBatchKeepBytes = (size_t)64 << 20;
+// Process-wide (zip_prime_batch_counts): successful calls, their members, and the kernel launches they made
+std::atomic<uint64_t> g_prime_batch_calls{0}, g_prime_batch_members{0}, g_prime_batch_launches{0};
+
+template <int FL>
+int32_t get_prime_batch_fl(PrimeDev &pd, zip_keccak_state *transcripts, uint32_t n, uint32_t w, uint64_t *primes_out,
+                           uint32_t *tried_out) {
+    const size_t N = n, sponge_words = (size_t)kPrimeSpongeWords * N;
+    // (every piece a multiple of 8 bytes)
+    const size_t result_words = sponge_words + N * FL + (N + 1) / 2;
+    const size_t cand_words = N * w * FL, list_words = (N + 1) / 2;
+    const size_t at_b = sponge_words, at_result = 2 * sponge_words, at_cands = at_result + result_words,
+                 at_live0 = at_cands + cand_words, at_live1 = at_live0 + list_words, at_steps = at_live1 + list_words,
+                 at_counts = at_steps + list_words, at_verdicts = at_counts + 1;
+    const size_t bytes = at_verdicts * 8 + N * w;
+    unsigned char *block = pd.batch_dev;
+    const bool own = bytes > pd.batch_bytes && bytes > kPrimeBatchKeepBytes;  // too large to keep: this call's alone
+    if (bytes > pd.batch_bytes) {
+        if (hipMalloc((void **)&block, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return ZIP_ERR_ALLOC;
+        }
+        if (!own) {
+            if (pd.batch_dev) (void)hipFree(pd.batch_dev);
+            pd.batch_dev = block;
+            pd.batch_bytes = bytes;
+        }
+    }
+    struct Release {
+        unsigned char *p;
+        ~Release() { if (p) (void)hipFree(p); }
+    } release{own ? block : nullptr};
+    uint64_t *base = reinterpret_cast<uint64_t *>(block);
+    uint64_t *sp_a = base, *sp_b = base + at_b, *result = base + at_result, *cands = base + at_cands;
+    uint64_t *primes_d = result + sponge_words;
+    uint32_t *tried_d = reinterpret_cast<uint32_t *>(primes_d + N * FL);
+    uint32_t *lists[2] = {reinterpret_cast<uint32_t *>(base + at_live0), reinterpret_cast<uint32_t *>(base + at_live1)};
+    uint32_t *steps = reinterpret_cast<uint32_t *>(base + at_steps), *counts = reinterpret_cast<uint32_t *>(base + at_counts);
+    uint8_t *verdicts = block + at_verdicts * 8;
+
+    std::vector<uint64_t> up(sponge_words), down(result_words);
+    for (size_t m = 0; m < N; m++) {
+        const zip_keccak_state &t = transcripts[m];
+        uint64_t blk[kKeccakRateWords] = {0};
+        memcpy(blk, t.buf, t.buflen);  // little-endian host; zero beyond buflen
+        for (uint32_t i = 0; i < 25; i++) up[(size_t)i * N + m] = t.st[i];
+        for (uint32_t i = 0; i < kKeccakRateWords; i++) up[(size_t)(25 + i) * N + m] = blk[i];
+        up[(size_t)(kPrimeSpongeWords - 1) * N + m] = t.buflen;
+    }
+    if (hipMemcpyAsync(sp_a, up.data(), sponge_words * 8, hipMemcpyHostToDevice, pd.stream) != hipSuccess)
+        return prime_fail_drained(pd);
+
+    uint32_t *n_live_h = reinterpret_cast<uint32_t *>(pd.host);  // pinned; the slots of zip_get_prime are idle under pd.mu
+    uint64_t launches = 0;
+    uint32_t n_live = n, done = 0;
+    const uint32_t *live = nullptr;  // round 0: member j is lane j
+    for (uint32_t round = 0; n_live && done < kPrimeMaxCandidates; round++) {
+        const uint32_t wr = std::min(w, kPrimeMaxCandidates - done);
+        uint32_t *live_next = lists[round & 1], *n_next = counts + (round & 1);
+        const dim3 members((n_live + kPrimeThreads - 1) / kPrimeThreads), wave(kPrimeThreads);
+        const uint32_t n_cands = n_live * wr;  // <= 65535 * 1024
+        if (hipMemsetAsync(n_next, 0, sizeof(uint32_t), pd.stream) != hipSuccess) return prime_fail_drained(pd);
+        hipLaunchKernelGGL(prime_chain_batch_kernel<FL>, members, wave, 0, pd.stream, (const uint64_t *)sp_a, sp_b, n, live, n_live,
+                           (const uint32_t *)nullptr, wr, cands);
+        hipLaunchKernelGGL(prime_test_base2_kernel<FL>, dim3((n_cands + kPrimeThreads - 1) / kPrimeThreads), wave, 0, pd.stream,
+                           (const uint64_t *)cands, n_cands, verdicts);
+        hipLaunchKernelGGL(prime_reduce_batch_kernel<FL>, members, wave, 0, pd.stream, (const uint64_t *)cands,
+                           (const uint8_t *)verdicts, n, live, n_live, wr, done, primes_d, tried_d, steps, live_next, n_next);
+        hipLaunchKernelGGL(prime_chain_batch_kernel<FL>, members, wave, 0, pd.stream, (const uint64_t *)sp_a, result, n, live, n_live,
+                           (const uint32_t *)steps, wr, (uint64_t *)nullptr);
+        if (hipGetLastError() != hipSuccess) return prime_fail_drained(pd);
+        launches += 4;
+        if (hipMemcpyAsync(n_live_h, n_next, sizeof(uint32_t), hipMemcpyDeviceToHost, pd.stream) != hipSuccess ||
+            stream_wait(pd.stream) != hipSuccess)
+            return prime_fail_drained(pd);
+        n_live = std::min(*n_live_h, n_live);
+        live = live_next;
+        std::swap(sp_a, sp_b);  // the members still live go on from where this round's chain ended
+        done += wr;
+    }
+    if (n_live) {
+        fprintf(stderr, "zip_get_prime_batch: %u of %u members have no probable prime among their first %u candidates of %d limbs; giving up\n",
+                n_live, n, kPrimeMaxCandidates, FL);
+        return ZIP_ERR_UNSUPPORTED;
+    }
+    if (hipMemcpyAsync(down.data(), result, result_words * 8, hipMemcpyDeviceToHost, pd.stream) != hipSuccess ||
+        stream_wait(pd.stream) != hipSuccess)
+        return prime_fail_drained(pd);
+    const uint32_t *tried_h = reinterpret_cast<const uint32_t *>(down.data() + sponge_words + N * FL);
+    for (size_t m = 0; m < N; m++) {
+        zip_keccak_state &t = transcripts[m];
+        uint64_t blk[kKeccakRateWords];
+        for (uint32_t i = 0; i < 25; i++) t.st[i] = down[(size_t)i * N + m];
+        for (uint32_t i = 0; i < kKeccakRateWords; i++) blk[i] = down[(size_t)(25 + i) * N + m];
+        memcpy(t.buf, blk, sizeof t.buf);  // zero beyond buflen
+        t.buflen = (uint32_t)down[(size_t)(kPrimeSpongeWords - 1) * N + m];
+        if (tried_out) tried_out[m] = tried_h[m];
+    }
+    memcpy(primes_out, down.data() + sponge_words, N * FL * 8);
+    g_prime_batch_calls++;
+    g_prime_batch_members += n;
+    g_prime_batch_launches += launches;
+    return ZIP_OK;
 }
 
 // ------------------------------------------------------------------ Spartan pieces
@@ -6253,6 +6370,31 @@ int32_t zip_get_prime(int32_t device, zip_keccak_state *transcript, uint32_t lim
 void zip_prime_launch_counts(uint64_t *launches, uint64_t *candidates_tested) {
     if (launches) *launches = g_prime_launches.load();
     if (candidates_tested) *candidates_tested = g_prime_candidates.load();
+}
+
+int32_t zip_get_prime_batch(int32_t device, zip_keccak_state *transcripts, uint32_t n, uint32_t limbs, uint64_t *primes_out,
+                            uint32_t *candidates_tried_out) {
+    if (!transcripts || !primes_out) return ZIP_ERR_NULL;
+    if (limbs < 2 || limbs > 4) return ZIP_ERR_INVALID_PARAM;
+    if (n == 0 || n > kPrimeBatchMaxMembers) return ZIP_ERR_INVALID_PARAM;
+    for (uint32_t i = 0; i < n; i++)
+        if (transcripts[i].buflen >= kKeccakRate) return ZIP_ERR_INVALID_PARAM;
+    if (device < 0 || device >= kMaxDevices) return ZIP_ERR_NO_DEVICE;
+    PrimeDev &pd = g_prime[device];
+    std::lock_guard<std::mutex> g(pd.mu);
+    CurrentDeviceGuard restore;
+    if (int32_t rc = prime_dev_ready(pd, device)) return rc;
+    // (per call: the tests flip it)
+    const uint32_t w = prime_batch_knob(getenv("ZIP_HIP_PRIME_BATCH_WINDOW"), kPrimeBatchDefaultWindow, kPrimeBatchMaxWindow);
+    return with_fl(limbs, [&](auto FL) {
+        return get_prime_batch_fl<decltype(FL)::value>(pd, transcripts, n, w, primes_out, candidates_tried_out);
+    });
+}
+
+void zip_prime_batch_counts(uint64_t *calls, uint64_t *members, uint64_t *kernel_launches) {
+    if (calls) *calls = g_prime_batch_calls.load();
+    if (members) *members = g_prime_batch_members.load();
+    if (kernel_launches) *kernel_launches = g_prime_batch_launches.load();
 }
 
 const char *zip_sumcheck_last_error(const zip_sumcheck *s) { return s && s->ctx ? s->ctx->last_error.c_str() : ""; }

@@ -104,6 +104,50 @@ int32_t zinc_draw_random_field(const int64_t *public_input, size_t l, zinc_trans
         for (uint32_t i = 0; i < limbs; i++) modulus_out[i] = f.modulus[i];
     });
 }
+int32_t zinc_get_prime_batch(zinc_transcript *const *transcripts, uint32_t n, uint32_t limbs, int32_t device, uint64_t *primes_out,
+                             uint32_t *candidates_tried_out) {
+    if (!transcripts || !primes_out) return ZINC_ERR_NULL;
+    for (uint32_t i = 0; i < n; i++)
+        if (!transcripts[i]) return ZINC_ERR_NULL;
+    return guarded([&] {
+        std::vector<KeccakTranscript *> tr(n);
+        for (uint32_t i = 0; i < n; i++) tr[i] = &transcripts[i]->t;
+        const std::vector<Limbs> p = prime_gen::get_prime_batch(tr, limbs, device, candidates_tried_out);
+        for (uint32_t i = 0; i < n; i++)
+            for (uint32_t j = 0; j < limbs; j++) primes_out[(size_t)i * limbs + j] = p[i][j];
+    });
+}
+int32_t zinc_draw_random_field_batch(const int64_t *const *public_inputs, const size_t *lens, zinc_transcript *const *transcripts,
+                                     uint32_t n, uint32_t limbs, int32_t device, uint64_t *moduli_out) {
+    if (!public_inputs || !lens || !transcripts || !moduli_out) return ZINC_ERR_NULL;
+    for (uint32_t i = 0; i < n; i++)
+        if (!transcripts[i] || (lens[i] && !public_inputs[i])) return ZINC_ERR_NULL;
+    return guarded([&] {
+        std::vector<KeccakTranscript *> tr(n);
+        for (uint32_t i = 0; i < n; i++) tr[i] = &transcripts[i]->t;
+        const std::vector<FieldConfig> f = draw_random_field_batch(std::vector<const int64_t *>(public_inputs, public_inputs + n),
+                                                                   std::vector<size_t>(lens, lens + n), tr, limbs, device);
+        for (uint32_t i = 0; i < n; i++)
+            for (uint32_t j = 0; j < limbs; j++) moduli_out[(size_t)i * limbs + j] = f[i].modulus[j];
+    });
+}
+int32_t zinc_verifier_check_field_batch(const int64_t *const *public_inputs, const size_t *lens, zinc_transcript *const *transcripts,
+                                        uint32_t n, const uint64_t *moduli, const uint32_t *limbs, int32_t device, uint8_t *same_out) {
+    if (!public_inputs || !lens || !transcripts || !moduli || !limbs || !same_out) return ZINC_ERR_NULL;
+    for (uint32_t i = 0; i < n; i++)
+        if (!transcripts[i] || (lens[i] && !public_inputs[i])) return ZINC_ERR_NULL;
+    return guarded([&] {
+        std::vector<KeccakTranscript *> tr(n);
+        std::vector<FieldConfig> f;
+        for (uint32_t i = 0; i < n; i++) {
+            tr[i] = &transcripts[i]->t;
+            f.push_back(FieldConfig::make(moduli + (size_t)i * 4, limbs[i]));
+        }
+        const std::vector<bool> same = zinc::ZincVerifier({}, device).check_field_batch(
+            std::vector<const int64_t *>(public_inputs, public_inputs + n), std::vector<size_t>(lens, lens + n), tr, f);
+        for (uint32_t i = 0; i < n; i++) same_out[i] = same[i] ? 1 : 0;
+    });
+}
 
 int32_t zinc_field_constants(const uint64_t *modulus, uint32_t limbs, uint64_t *r, uint64_t *r2, uint64_t *inv) {
     return guarded([&] {
@@ -756,13 +800,17 @@ int32_t zinc_prover_pcs_step_batch(const zinc_linear_code_spec *spec, uint32_t s
     });
 }
 
-int32_t zinc_verifier_verify_batch(const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
-                                   uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c, uint32_t n_instances,
-                                   zinc_transcript *const *transcripts, const uint64_t *moduli, const uint32_t *limbs,
-                                   int32_t device, const uint64_t *msgs1, const uint64_t *msgs2, const uint64_t *v_s,
-                                   const uint8_t *const *roots, const size_t *n_roots, const uint64_t *v,
-                                   const uint8_t *const *pcs_proofs, const size_t *pcs_proof_lens, int32_t *results_out,
-                                   char *messages_out, size_t message_cap) {
+}  // extern "C"
+namespace {
+// zinc_verifier_verify_batch (public_inputs == nullptr) and zinc_verifier_verify_batch_checked
+int32_t verify_batch_impl(const int64_t *const *public_inputs, const size_t *public_input_lens,
+                          const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                          uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c, uint32_t n_instances,
+                          zinc_transcript *const *transcripts, const uint64_t *moduli, const uint32_t *limbs,
+                          int32_t device, const uint64_t *msgs1, const uint64_t *msgs2, const uint64_t *v_s,
+                          const uint8_t *const *roots, const size_t *n_roots, const uint64_t *v,
+                          const uint8_t *const *pcs_proofs, const size_t *pcs_proof_lens, int32_t *results_out,
+                          char *messages_out, size_t message_cap) {
     if (!constraints || !s_masks || !c || !transcripts || !moduli || !limbs || !msgs1 || !msgs2 || !v_s || !roots || !n_roots || !v ||
         !pcs_proofs || !pcs_proof_lens || !results_out || (messages_out && !message_cap))
         return ZINC_ERR_NULL;
@@ -806,12 +854,21 @@ int32_t zinc_verifier_verify_batch(const zinc_linear_code_spec *spec, const zip_
             proofs[i] = {&sp[i], &comms[i], &vs[i], pcs_proofs[i], pcs_proof_lens[i]};  // the proof bytes are read in place
             tr[i] = &transcripts[i]->t;
         }
-        const auto outcomes = zinc::ZincVerifier(spec_of(spec), device).verify_batch(constraints, ccs, proofs, tr, f);
+        const zinc::ZincVerifier verifier(spec_of(spec), device);
+        std::vector<zinc::ZincVerifier::BatchOutcome> outcomes;
+        if (public_inputs) {
+            const std::vector<const int64_t *> x(public_inputs, public_inputs + n_instances);
+            const std::vector<size_t> l(public_input_lens, public_input_lens + n_instances);
+            outcomes = verifier.verify_batch_checked(constraints, ccs, x, l, proofs, tr, f);
+        } else {
+            outcomes = verifier.verify_batch(constraints, ccs, proofs, tr, f);
+        }
         for (uint32_t i = 0; i < n_instances; i++) {
             const auto &o = outcomes[i];
             using O = zinc::ZincVerifier::BatchOutcome;
             results_out[i] = o.kind == O::Accepted  ? ZINC_OK
                              : o.kind == O::Spartan ? ZINC_ERR_SPARTAN
+                             : o.kind == O::FieldConfig ? ZINC_ERR_FIELD_CONFIG
                              : o.zip_kind == ZipError::InvalidPcsParam ? ZINC_ERR_INVALID_PARAM
                                                                        : ZINC_ERR_INVALID_OPEN;
             if (messages_out) {
@@ -822,6 +879,34 @@ int32_t zinc_verifier_verify_batch(const zinc_linear_code_spec *spec, const zip_
             }
         }
     });
+}
+}  // namespace
+extern "C" {
+
+int32_t zinc_verifier_verify_batch(const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t, uint32_t s,
+                                   uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c, uint32_t n_instances,
+                                   zinc_transcript *const *transcripts, const uint64_t *moduli, const uint32_t *limbs,
+                                   int32_t device, const uint64_t *msgs1, const uint64_t *msgs2, const uint64_t *v_s,
+                                   const uint8_t *const *roots, const size_t *n_roots, const uint64_t *v,
+                                   const uint8_t *const *pcs_proofs, const size_t *pcs_proof_lens, int32_t *results_out,
+                                   char *messages_out, size_t message_cap) {
+    return verify_batch_impl(nullptr, nullptr, spec, constraints, t, s, d, q, s_masks, c, n_instances, transcripts, moduli, limbs, device,
+                             msgs1, msgs2, v_s, roots, n_roots, v, pcs_proofs, pcs_proof_lens, results_out, messages_out, message_cap);
+}
+int32_t zinc_verifier_verify_batch_checked(const int64_t *const *public_inputs, const size_t *public_input_lens,
+                                           const zinc_linear_code_spec *spec, const zip_sparse_matrix *constraints, uint32_t t,
+                                           uint32_t s, uint32_t d, uint32_t q, const uint32_t *s_masks, const int64_t *c,
+                                           uint32_t n_instances, zinc_transcript *const *transcripts, const uint64_t *moduli,
+                                           const uint32_t *limbs, int32_t device, const uint64_t *msgs1, const uint64_t *msgs2,
+                                           const uint64_t *v_s, const uint8_t *const *roots, const size_t *n_roots, const uint64_t *v,
+                                           const uint8_t *const *pcs_proofs, const size_t *pcs_proof_lens, int32_t *results_out,
+                                           char *messages_out, size_t message_cap) {
+    if (!public_inputs || !public_input_lens) return ZINC_ERR_NULL;
+    for (uint32_t i = 0; i < n_instances; i++)
+        if (public_input_lens[i] && !public_inputs[i]) return ZINC_ERR_NULL;
+    return verify_batch_impl(public_inputs, public_input_lens, spec, constraints, t, s, d, q, s_masks, c, n_instances, transcripts,
+                             moduli, limbs, device, msgs1, msgs2, v_s, roots, n_roots, v, pcs_proofs, pcs_proof_lens, results_out,
+                             messages_out, message_cap);
 }
 
 int32_t zinc_verifier_verify(const zip_sparse_matrix *constraints, uint32_t t, uint32_t s, uint32_t d, uint32_t q,

@@ -2207,6 +2207,141 @@ FieldConfig draw_random_field(const int64_t *public_input, size_t l, KeccakTrans
     return FieldConfig::make(prime.data(), limbs);
 }
 
+namespace {
+// From how many members on get_prime_batch makes ONE zip_get_prime_batch call instead of the loop over zip_get_prime: per
+// limb count the smallest measured n at which the batch beat the loop by more than the loop's own run-to-run spread
+// (tools/prime_batch_times.py, profiles/prime_batch.md: n = 2, 4, 16, 64, 256).  At 2, 4 and 16 members the loop is
+// faster at every limb count (a batch call costs its longest chain, 4 .. 13 ms, however few the members); 64 members win
+// 1.6x / 1.7x / 2.9x at 2 / 3 / 4 limbs and 256 win 4.6x / 6.0x / 7.7x.  Counts between 16 and 64 were not measured and
+// loop.  ZIP_HIP_PRIME_MIN_BATCH=n (n >= 2, read per call) puts the line at n for every limb count: how the tests reach
+// the batch below the line.
+size_t min_prime_batch(uint32_t limbs) {
+    if (const char *e = std::getenv("ZIP_HIP_PRIME_MIN_BATCH")) {
+        const long n = std::atol(e);
+        if (n >= 2) return (size_t)n;
+    }
+    (void)limbs;  // the same line at 2, 3 and 4 limbs
+    return 64;
+}
+void absorb_public_input(KeccakTranscript &transcript, const int64_t *public_input, size_t l) {
+    for (size_t i = 0; i < l; i++) {  // cast_slice(input.as_words()): the one word of an Int<1>, little-endian
+        uint8_t b[8];
+        const uint64_t w = (uint64_t)public_input[i];
+        for (int j = 0; j < 8; j++) b[j] = (uint8_t)(w >> (8 * j));
+        transcript.absorb(b, 8);
+    }
+}
+}  // namespace
+
+std::vector<Limbs> prime_gen::get_prime_batch(const std::vector<KeccakTranscript *> &transcripts, uint32_t limbs, int device,
+                                              uint32_t *candidates_tried) {
+    if (limbs < 2 || limbs > 4) throw ZipError(ZipError::InvalidPcsParam, "get_prime: FIELD_LIMBS must be 2, 3 or 4");
+    const size_t B = transcripts.size();
+    for (KeccakTranscript *t : transcripts)
+        if (!t) throw std::logic_error("get_prime_batch: a NULL transcript");
+    std::vector<Limbs> primes(B, Limbs{});
+    if (!zip::batch_path_enabled() || B < 2 || B > 65535 || B < min_prime_batch(limbs)) {
+        for (size_t i = 0; i < B; i++) primes[i] = get_prime(*transcripts[i], limbs, device, candidates_tried ? candidates_tried + i : nullptr);
+        return primes;
+    }
+    std::vector<zip_keccak_state> k(B);
+    for (size_t i = 0; i < B; i++) transcripts[i]->export_state(&k[i]);
+    std::vector<uint64_t> words(B * limbs);
+    const int32_t rc = zip_get_prime_batch(device, k.data(), (uint32_t)B, limbs, words.data(), candidates_tried);
+    if (rc) throw ZipError(ZipError::Device, std::string("zip_get_prime_batch: ") + zip_strerror(rc));
+    for (size_t i = 0; i < B; i++) {
+        transcripts[i]->import_state(k[i]);
+        std::copy(words.begin() + i * limbs, words.begin() + (i + 1) * limbs, primes[i].begin());
+    }
+    return primes;
+}
+
+std::vector<FieldConfig> draw_random_field_batch(const std::vector<const int64_t *> &public_inputs, const std::vector<size_t> &lens,
+                                                 const std::vector<KeccakTranscript *> &transcripts, uint32_t limbs, int device) {
+    const size_t B = transcripts.size();
+    if (public_inputs.size() != B || lens.size() != B)
+        throw std::logic_error("draw_random_field_batch: one public input and one transcript per member");
+    if (limbs < 2 || limbs > 4) throw ZipError(ZipError::InvalidPcsParam, "get_prime: FIELD_LIMBS must be 2, 3 or 4");
+    for (size_t i = 0; i < B; i++)
+        if (!transcripts[i] || (lens[i] && !public_inputs[i])) throw std::logic_error("draw_random_field_batch: a NULL transcript or public input");
+    for (size_t i = 0; i < B; i++) absorb_public_input(*transcripts[i], public_inputs[i], lens[i]);
+    const std::vector<Limbs> primes = prime_gen::get_prime_batch(transcripts, limbs, device);
+    std::vector<FieldConfig> out;
+    out.reserve(B);
+    for (size_t i = 0; i < B; i++) out.push_back(FieldConfig::make(primes[i].data(), limbs));
+    return out;
+}
+
+std::vector<bool> ZincVerifier::check_field_batch(const std::vector<const int64_t *> &public_inputs, const std::vector<size_t> &lens,
+                                                  const std::vector<KeccakTranscript *> &transcripts,
+                                                  const std::vector<FieldConfig> &configs) const {
+    const size_t B = transcripts.size();
+    if (public_inputs.size() != B || lens.size() != B || configs.size() != B)
+        throw std::logic_error("check_field_batch: one public input, one transcript and one field per member");
+    for (size_t i = 0; i < B; i++)  // before any transcript is touched
+        if (configs[i].limbs < 2 || configs[i].limbs > 4) throw ZipError(ZipError::InvalidPcsParam, "get_prime: FIELD_LIMBS must be 2, 3 or 4");
+    std::vector<bool> same(B, false);
+    for (uint32_t limbs = 2; limbs <= 4; limbs++) {  // the members of one limb count are one draw
+        std::vector<size_t> who;
+        std::vector<const int64_t *> x;
+        std::vector<size_t> l;
+        std::vector<KeccakTranscript *> tr;
+        for (size_t i = 0; i < B; i++)
+            if (configs[i].limbs == limbs) {
+                who.push_back(i);
+                x.push_back(public_inputs[i]);
+                l.push_back(lens[i]);
+                tr.push_back(transcripts[i]);
+            }
+        if (who.empty()) continue;
+        const std::vector<FieldConfig> drawn = draw_random_field_batch(x, l, tr, limbs, device_);  // :53-57
+        for (size_t j = 0; j < who.size(); j++) same[who[j]] = drawn[j].modulus == configs[who[j]].modulus;
+    }
+    return same;
+}
+
+std::vector<ZincVerifier::BatchOutcome> ZincVerifier::verify_batch_checked(
+    const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs, const std::vector<const int64_t *> &public_inputs,
+    const std::vector<size_t> &lens, const std::vector<const ZincProof *> &proofs, const std::vector<KeccakTranscript *> &transcripts,
+    const std::vector<FieldConfig> &configs) const {
+    std::vector<BatchProof> views(proofs.size());
+    for (size_t i = 0; i < proofs.size(); i++) {
+        if (!proofs[i]) throw std::logic_error("verify_batch: a NULL proof");
+        const zip::ZipProof &zp = proofs[i]->zip_proof;
+        views[i] = {&proofs[i]->spartan_proof, &zp.z_comm, &zp.v, zp.pcs_proof.data(), zp.pcs_proof.size()};
+    }
+    return verify_batch_checked(matrices, ccs, public_inputs, lens, views, transcripts, configs);
+}
+
+std::vector<ZincVerifier::BatchOutcome> ZincVerifier::verify_batch_checked(
+    const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs, const std::vector<const int64_t *> &public_inputs,
+    const std::vector<size_t> &lens, const std::vector<BatchProof> &proofs, const std::vector<KeccakTranscript *> &transcripts,
+    const std::vector<FieldConfig> &configs) const {
+    const size_t B = proofs.size();
+    if (transcripts.size() != B) throw std::logic_error("verify_batch: one transcript and one field per proof");
+    const std::vector<bool> same = check_field_batch(public_inputs, lens, transcripts, configs);
+    std::vector<BatchProof> p;
+    std::vector<KeccakTranscript *> tr;
+    std::vector<FieldConfig> f;
+    std::vector<size_t> who;
+    for (size_t i = 0; i < B; i++)
+        if (same[i]) {
+            who.push_back(i);
+            p.push_back(proofs[i]);
+            tr.push_back(transcripts[i]);
+            f.push_back(configs[i]);
+        }
+    std::vector<BatchOutcome> out(B);
+    for (size_t i = 0; i < B; i++)
+        if (!same[i]) {
+            out[i].kind = BatchOutcome::FieldConfig;
+            out[i].message = "the field drawn from the public input and the transcript is not the given field configuration";
+        }
+    const std::vector<BatchOutcome> passed = verify_batch(matrices, ccs, p, tr, f);
+    for (size_t j = 0; j < who.size(); j++) out[who[j]] = passed[j];
+    return out;
+}
+
 void ZincVerifier::check_field(const int64_t *public_input, size_t l, KeccakTranscript &transcript,
                                const FieldConfig &config) const {
     const FieldConfig drawn = draw_random_field(public_input, l, transcript, config.limbs, device_);  // :53-57

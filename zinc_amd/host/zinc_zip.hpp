@@ -152,11 +152,23 @@ class KeccakTranscript {
 // the device call fails -- there is no host path for the tests.
 namespace prime_gen {
 Limbs get_prime(KeccakTranscript &transcript, uint32_t limbs, int device = 0, uint32_t *candidates_tried = nullptr);
+// get_prime on every transcript of a batch (the fields of many small proofs): ONE zip_get_prime_batch call, chains and
+// tests on the device, from min_prime_batch(limbs) members on (zinc_zip.cpp, from profiles/prime_batch.md;
+// ZIP_HIP_PRIME_MIN_BATCH=n, n >= 2, read per call, moves the line).  Below it, with ZIP_HIP_BATCH=0 and for one
+// member: the loop over get_prime.  Both paths give the same primes, positions, transcripts and errors.
+// candidates_tried (may be null): one entry per member.
+std::vector<Limbs> get_prime_batch(const std::vector<KeccakTranscript *> &transcripts, uint32_t limbs, int device = 0,
+                                   uint32_t *candidates_tried = nullptr);
 }
 // draw_random_field (src/zinc/utils.rs:161-171) with I = Int<1>: every public input is absorbed as its 8 little-endian
 // bytes (:165-167), then FieldConfig::new(get_prime(transcript)).
 FieldConfig draw_random_field(const int64_t *public_input, size_t l, KeccakTranscript &transcript, uint32_t limbs,
                               int device = 0);
+// draw_random_field for every member of a batch: member i absorbs public_inputs[i][0 .. lens[i]) on transcripts[i] as
+// draw_random_field does, then ONE prime_gen::get_prime_batch over all of them.
+std::vector<FieldConfig> draw_random_field_batch(const std::vector<const int64_t *> &public_inputs, const std::vector<size_t> &lens,
+                                                 const std::vector<KeccakTranscript *> &transcripts, uint32_t limbs,
+                                                 int device = 0);
 // ZincError::FieldConfigError (src/zinc/errors.rs): the field the verifier draws is not the one it was handed
 struct FieldConfigError : std::runtime_error {
     explicit FieldConfigError(const std::string &what) : std::runtime_error(what) {}
@@ -568,6 +580,7 @@ struct VerificationPoints {
 // ZincVerifier (src/zinc/verifier.rs).  The sumcheck verifiers are O(s * d) field operations on the host; the
 // Zip verifier and the evaluation of the matrix MLEs at (r_x, r_y) run on the device.  The draw_random_field check
 // of Verifier::verify (:53-57) is verify_checked's; verify itself takes the field it is handed.
+// For B proofs: verify_batch, check_field_batch and verify_batch_checked.
 class ZincVerifier {
   public:
     explicit ZincVerifier(zip::LinearCodeSpec spec = {}, int device = 0) : lc_spec_(spec), device_(device) {}
@@ -611,7 +624,8 @@ class ZincVerifier {
     // std::logic_error is a shape the reference panics on: thrown for the first member that has it, before any device
     // work.  (An encode_wide overflow inside a proof stream, the one panic the device finds, is thrown when that member's
     // turn comes, as the loop throws it; the batched path has then moved the later members' transcripts already.)
-    // Not part of this: the field check of verify_checked (check_field per member, which callers run first).
+    // Not part of this: the field check of verify_checked -- that is check_field_batch, and verify_batch_checked runs
+    // the two one after the other.
     struct BatchProof {  // one ZincProof, its bytes borrowed
         const SpartanProof *spartan_proof = nullptr;
         const zip::MultilinearZipCommitment *z_comm = nullptr;
@@ -620,7 +634,8 @@ class ZincVerifier {
         size_t pcs_proof_len = 0;
     };
     struct BatchOutcome {
-        enum Kind { Accepted, Spartan, Zip } kind = Accepted;
+        // (FieldConfig: verify_batch_checked alone -- the member's drawn field is not the one handed over)
+        enum Kind { Accepted, Spartan, Zip, FieldConfig } kind = Accepted;
         ZipError::Kind zip_kind = ZipError::InvalidPcsOpen;  // kind == Zip: InvalidPcsOpen, Transcript or InvalidPcsParam
         std::string message;                                 // what() of what verify would have thrown for this proof alone
         bool accepted() const { return kind == Accepted; }
@@ -631,6 +646,25 @@ class ZincVerifier {
     std::vector<BatchOutcome> verify_batch(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs, const std::vector<const ZincProof *> &proofs,
                                            const std::vector<KeccakTranscript *> &transcripts,
                                            const std::vector<FieldConfig> &configs) const;
+
+    // check_field for every member of a batch: result[i] = the field drawn from public_inputs[i] on transcripts[i], at
+    // configs[i].limbs limbs, IS configs[i].  Every transcript is left where check_field leaves it, for the members that
+    // fail as well.  The members of one limb count are one draw_random_field_batch.
+    std::vector<bool> check_field_batch(const std::vector<const int64_t *> &public_inputs, const std::vector<size_t> &lens,
+                                        const std::vector<KeccakTranscript *> &transcripts,
+                                        const std::vector<zinc::FieldConfig> &configs) const;
+    // verify_checked for every member: check_field_batch, then verify_batch over the members that passed.  A member
+    // that failed the field check has kind FieldConfig and its transcript where check_field left it.
+    std::vector<BatchOutcome> verify_batch_checked(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs,
+                                                   const std::vector<const int64_t *> &public_inputs, const std::vector<size_t> &lens,
+                                                   const std::vector<BatchProof> &proofs,
+                                                   const std::vector<KeccakTranscript *> &transcripts,
+                                                   const std::vector<zinc::FieldConfig> &configs) const;
+    std::vector<BatchOutcome> verify_batch_checked(const zip_sparse_matrix *matrices, const ccs::CCS_Z &ccs,
+                                                   const std::vector<const int64_t *> &public_inputs, const std::vector<size_t> &lens,
+                                                   const std::vector<const ZincProof *> &proofs,
+                                                   const std::vector<KeccakTranscript *> &transcripts,
+                                                   const std::vector<zinc::FieldConfig> &configs) const;
 
   private:
     zip::LinearCodeSpec lc_spec_;

@@ -32,6 +32,8 @@ EXPORTED_SYMBOLS = (
     "zinc_zip_batch_commit", "zinc_zip_batch_open", "zinc_zip_batch_open_challenges",
     "zinc_zip_batch_verify", "zinc_zip_batch_verify_challenges",
     "zinc_get_prime", "zinc_draw_random_field", "zinc_verifier_verify_checked",
+    "zinc_get_prime_batch", "zinc_draw_random_field_batch", "zinc_verifier_check_field_batch",
+    "zinc_verifier_verify_batch_checked",
 )
 
 
@@ -101,6 +103,9 @@ def lib():
         L.zinc_transcript_import.argtypes = [vp, vp, vp, C.c_uint32]
         L.zinc_get_prime.argtypes = [vp, C.c_uint32, C.c_int32, vp, C.POINTER(C.c_uint32)]
         L.zinc_draw_random_field.argtypes = [vp, C.c_size_t, vp, C.c_uint32, C.c_int32, vp]
+        L.zinc_get_prime_batch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int32, vp, vp]
+        L.zinc_draw_random_field_batch.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_int32, vp]
+        L.zinc_verifier_check_field_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, C.c_int32, vp]
         L.zinc_field_constants.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.zinc_field_mul.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.zinc_map_to_field_i64.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp]
@@ -160,6 +165,7 @@ def lib():
                                               C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
         L.zinc_verifier_verify_batch.argtypes = [C.POINTER(LinearCodeSpec), vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
                                                  C.c_uint32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
+        L.zinc_verifier_verify_batch_checked.argtypes = [vp, vp] + L.zinc_verifier_verify_batch.argtypes
         L.zinc_prover_pcs_step_batch.argtypes = [C.POINTER(LinearCodeSpec), C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_int32, vp]
         L.zinc_prover_prepare.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_int32, C.POINTER(vp)]
         L.zinc_prepared_ccs_free.argtypes = [vp]
@@ -307,6 +313,41 @@ def draw_random_field(public_input, transcript: KeccakTranscript, limbs: int, de
     _check(lib().zinc_draw_random_field(x.ctypes.data if x.size else None, x.size, transcript._h, limbs, device,
                                         out.ctypes.data))
     return FieldConfig(sum(int(w) << (64 * i) for i, w in enumerate(out)), limbs)
+
+
+def _public_inputs(public_inputs):
+    """-> (kept arrays, the pointer array, the length array) of one int64 public input per member"""
+    xs = [np.ascontiguousarray(x, dtype=np.int64).reshape(-1) for x in public_inputs]
+    n = max(len(xs), 1)
+    ptrs = (C.c_void_p * n)(*[x.ctypes.data if x.size else None for x in xs])
+    lens = (C.c_size_t * n)(*[x.size for x in xs])
+    return xs, ptrs, lens
+
+
+def get_prime_batch(transcripts, limbs: int, device: int = 0, want_tried: bool = False):
+    """get_prime for every transcript of a batch (prime_gen::get_prime_batch): from the line profiles/prime_batch.md sets
+    on (ZIP_HIP_PRIME_MIN_BATCH=n moves it) ONE zip_get_prime_batch call, the candidate chains and the tests on the device;
+    below it, and with ZIP_HIP_BATCH=0, the loop over get_prime -- the same primes and transcripts either way.
+    -> the primes as Python ints; want_tried: -> (primes, the winners' 1-based positions)."""
+    n = len(transcripts)
+    trs = (C.c_void_p * max(n, 1))(*[t._h for t in transcripts])
+    out = np.zeros((max(n, 1), limbs), np.uint64)
+    tried = np.zeros(max(n, 1), np.uint32)
+    _check(lib().zinc_get_prime_batch(trs, n, limbs, device, out.ctypes.data, tried.ctypes.data))
+    primes = [sum(int(w) << (64 * i) for i, w in enumerate(out[k])) for k in range(n)]
+    return (primes, [int(x) for x in tried[:n]]) if want_tried else primes
+
+
+def draw_random_field_batch(public_inputs, transcripts, limbs: int, device: int = 0):
+    """draw_random_field for every member of a batch: member i absorbs public_inputs[i] on transcripts[i], then one
+    get_prime_batch over all of them -> a FieldConfig per member."""
+    n = len(transcripts)
+    assert len(public_inputs) == n
+    _keep, ptrs, lens = _public_inputs(public_inputs)
+    trs = (C.c_void_p * max(n, 1))(*[t._h for t in transcripts])
+    out = np.zeros((max(n, 1), limbs), np.uint64)
+    _check(lib().zinc_draw_random_field_batch(ptrs, lens, trs, n, limbs, device, out.ctypes.data))
+    return [FieldConfig(sum(int(w) << (64 * i) for i, w in enumerate(out[k])), limbs) for k in range(n)]
 
 
 def kat_seed_from_u64(seed: int, n_words: int):
@@ -899,7 +940,31 @@ class ZincVerifier:
         is taken as handed."""
         return self._run(matrices, s, d, S, c, proof, transcript, field, True, prepared, public_input)
 
-    def verify_batch(self, matrices, s, d, S, c, proofs, transcripts, fields):
+    def check_field_batch(self, public_inputs, transcripts, fields):
+        """The field check of Verifier::verify (:53-57) for every member of a batch (ZincVerifier::check_field_batch) ->
+        a list of bools: the field drawn from public_inputs[i] on transcripts[i], at fields[i].limbs limbs, is fields[i].
+        Nothing is raised for a member that fails; every transcript is left where the check of `verify` leaves it."""
+        n = len(transcripts)
+        assert len(public_inputs) == n and len(fields) == n
+        _keep, ptrs, lens = _public_inputs(public_inputs)
+        trs = (C.c_void_p * max(n, 1))(*[t._h for t in transcripts])
+        limbs = np.array([f.limbs for f in fields] or [0], dtype=np.uint32)
+        moduli = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        for i, f in enumerate(fields):
+            moduli[i, :f.limbs] = np.asarray(f._m, dtype=np.uint64)[:f.limbs]
+        same = np.zeros(max(n, 1), np.uint8)
+        _check(lib().zinc_verifier_check_field_batch(ptrs, lens, trs, n, moduli.ctypes.data, limbs.ctypes.data, self.device,
+                                                     same.ctypes.data))
+        return [bool(x) for x in same[:n]]
+
+    def verify_batch_checked(self, matrices, s, d, S, c, proofs, transcripts, fields, public_inputs):
+        """verify_batch with the field check first (ZincVerifier::verify_batch_checked): check_field_batch over all
+        members, verify_batch over those that passed.  A member that failed the check has a FieldConfigError in the
+        returned list and its transcript where the check left it."""
+        assert len(public_inputs) == len(proofs)
+        return self.verify_batch(matrices, s, d, S, c, proofs, transcripts, fields, _checked_inputs=public_inputs)
+
+    def verify_batch(self, matrices, s, d, S, c, proofs, transcripts, fields, _checked_inputs=None):
         """verify for B proofs of ONE circuit (the dicts prove_batch returns), proofs[i] on transcripts[i] in fields[i]
         (ZincVerifier::verify_batch) -> a list with None per accepted proof and, not raised, the exception object verify
         would have raised for that proof alone (SpartanError / InvalidPcsOpen) otherwise.  Every transcript ends where
@@ -938,9 +1003,14 @@ class ZincVerifier:
         results = np.zeros(n, dtype=np.int32)
         cap = 256
         messages = C.create_string_buffer(n * cap)
-        _check(lib().zinc_verifier_verify_batch(_spec_ptr(self.spec), arr, t, s, d, len(S), masks.ctypes.data, cv.ctypes.data, B, trs,
-                                                moduli.ctypes.data, limbs.ctypes.data, self.device, m1.ctypes.data, m2.ctypes.data,
-                                                vs.ctypes.data, rp, rn, v.ctypes.data, pp, pl, results.ctypes.data, messages, cap))
+        args = (_spec_ptr(self.spec), arr, t, s, d, len(S), masks.ctypes.data, cv.ctypes.data, B, trs, moduli.ctypes.data,
+                limbs.ctypes.data, self.device, m1.ctypes.data, m2.ctypes.data, vs.ctypes.data, rp, rn, v.ctypes.data, pp, pl,
+                results.ctypes.data, messages, cap)
+        if _checked_inputs is None:
+            _check(lib().zinc_verifier_verify_batch(*args))
+        else:
+            _keep_x, xp, xl = _public_inputs(_checked_inputs)
+            _check(lib().zinc_verifier_verify_batch_checked(xp, xl, *args))
         raw = messages.raw
         return [_error(int(results[i]), raw[i * cap:(i + 1) * cap].split(b"\0", 1)[0].decode()) for i in range(B)]
 
