@@ -204,8 +204,8 @@ def field_map_values(modulus, fl, width, n=512, seed=11):
 # An honest proof with everything both verifiers need, and the byte offsets of its parts
 # ---------------------------------------------------------------------------------------------------------------------
 class Instance:
-    def __init__(self, num_vars, modulus, fl, seed=5):
-        self.z = z = Zip2(num_vars)
+    def __init__(self, num_vars, modulus, fl, seed=5, geometry=None, rep=2, n_cols=N_COLS):
+        self.z = z = Zip2(num_vars, geometry=geometry, rep=rep, n_cols=n_cols)
         self.modulus, self.fl = modulus, fl
         self.f = f = orc.make_field(modulus, fl)
         self.evals = witness(z, "random", seed)
@@ -316,9 +316,10 @@ class Instance:
 
 
 @functools.lru_cache(maxsize=None)
-def instance(num_vars, modulus, fl):
-    """The shared honest proofs of the verifier tests, built once per process and never modified."""
-    return Instance(num_vars, modulus, fl)
+def instance(num_vars, modulus, fl, geometry=None, rep=2, n_cols=N_COLS):
+    """The shared honest proofs of the verifier tests, built once per process and never modified.  geometry =
+    (row_len, num_rows, codeword_len) with its rep: a slice of a real geometry instead of the whole shape of num_vars."""
+    return Instance(num_vars, modulus, fl, geometry=geometry, rep=rep, n_cols=n_cols)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -378,3 +379,66 @@ def overflow_case(inst):
     c = inst.C - 1
     return (f"u' = 2^1022 at {c}", lambda p, ro, ev: (inst.with_u_prime(p, [(1 << 1022) if j == c else 0 for j in range(inst.C)]), ro, ev),
             dict(verdict=OVERFLOW, column=0))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The verifier shapes of the regime tests (tests/test_gpu_two_limb_regimes.py on the device, and
+# tests/test_two_limb_regimes_host.py, which holds the model to the oracle on the same shapes and cases first):
+# (num_vars, modulus, fl, (row_len, num_rows, codeword_len), rep)
+# ---------------------------------------------------------------------------------------------------------------------
+# 2048 rows: every thread of tl_verify_columns_kernel walks 8 of them
+REGIME_MANY_ROWS = [(13, BENCH_MODULUS, 4, (4, 2048, 8), 2), (13, TEST_MODULUS_2, 2, (4, 2048, 8), 2)]
+# codewords of 2048 / 4096 / 65536: encode_wide(u') over Int<16> by 1024 threads that own 2 / 4 / 64 positions each
+REGIME_WIDE_CODEWORDS = [(11, BENCH_MODULUS, 4, (1024, 2, 2048), 2), (11, MOD_3LIMB, 3, (1024, 2, 2048), 2),
+                         (12, BENCH_MODULUS, 4, (1024, 4, 4096), 4), (15, BENCH_MODULUS, 4, (16384, 2, 65536), 4)]
+
+
+def regime_instance(num_vars, modulus, fl, geometry, rep):
+    inst = instance(num_vars, modulus, fl, geometry, rep)
+    assert (inst.C, inst.R, inst.cw) == geometry
+    return inst
+
+
+def below_overflow_case(inst):
+    """overflow_case's companion: u' = 2^1000 e_c.  No prefix sum of either pass leaves Int<16> (2^1000 rep cw < 2^1023
+    for every codeword a ctx admits), so the encoding is formed and the openings simply do not match it."""
+    c = inst.C - 1
+    return (f"u' = 2^1000 at {c}", lambda p, ro, ev: (inst.with_u_prime(p, [(1 << 1000) if j == c else 0 for j in range(inst.C)]), ro, ev),
+            dict(verdict=PROXIMITY_TESTING, column=0))
+
+
+def fill_512_case(inst, seed=9):
+    """Every column entry of every opening filled with 512 random bits, -2^511 and 2^511 - 1 planted at the first and
+    the last row of the first opening: the sums of num_rows 128 x 512-bit products and the 512-bit reductions."""
+    def mutate(proof, roots, ev):
+        p = proof.copy()
+        rng = np.random.default_rng(seed)
+        for k in range(inst.n_cols):
+            p[inst.val_at(k, 0): inst.val_at(k, 0) + 64 * inst.R] = np.frombuffer(rng.bytes(64 * inst.R), dtype=np.uint8)
+        inst.set_value(p, 0, 0, -(1 << 511))
+        inst.set_value(p, 0, inst.R - 1, (1 << 511) - 1)
+        return p, roots, ev
+    return ("entries that fill all 512 bits", mutate,
+            dict(verdict=PROXIMITY_TESTING, column=0, bad_merkle_paths=inst.n_cols * inst.R, malformed_paths=0))
+
+
+def many_rows_cases(inst):
+    """The catalogue at 2048 rows, and three tampers that no thread meets at its first row: row 256 is the first row of
+    a second iteration, row 2047 the last row of the last one, row 1300 lies in the sixth."""
+    i = inst
+    assert i.R == 2048 and i.n_cols > 9 and i.d >= 2
+    out = tamper_cases(i) + [overflow_case(i)]
+    out.append(("value[5,2047] bit 0", _flip_bit(i.val_at(5, 2047), 0), dict(verdict=PROXIMITY_TESTING, column=5)))
+    out.append(("value[7,256] bit 0", _flip_bit(i.val_at(7, 256), 0), dict(verdict=PROXIMITY_TESTING, column=7)))
+    out.append(("path[9,1300] level 1", _flip_bit(i.node_at(9, 1300, 1) + 17, 2), dict(verdict=MERKLE, column=9, bad_merkle_paths=1)))
+    out.append(fill_512_case(i))
+    return out
+
+
+def wide_codeword_cases(inst):
+    """What encode_wide(u') decides at a codeword of 1024 and more: both u' flips of the catalogue, the overflow and its
+    companion one bit lower, and one value and one evaluation-row tamper (the rest of the verdict order) beside them."""
+    i = inst
+    picked = [c for c in tamper_cases(i) if c[0].startswith(("u'[", "value[0,0] bit 0", "evaluation row["))]
+    assert len(picked) == 4, [c[0] for c in picked]
+    return picked + [overflow_case(i), below_overflow_case(i)]
