@@ -53,7 +53,9 @@ extern "C" {
  * zip_batch_verify_codes_counts and zip_ccs_batch_eval_matrices: the verifier's side of such a batch.  So is
  * zip_field_map_int, and so is the admission of (n_limbs, k_limbs, m_limbs) = (2, 8, 16) by zip_ctx_create: a triple that
  * was refused is now served, every call on a (1, 4, 8) ctx means what it meant.  So are zip_get_prime_batch and
- * zip_prime_batch_counts: the fields of a whole batch in one launch set, beside zip_get_prime that is unchanged.) */
+ * zip_prime_batch_counts: the fields of a whole batch in one launch set, beside zip_get_prime that is unchanged.  So are
+ * zip_batch_open_each and zip_batch_open_each_counts: the streams of a batch open delivered one by one, beside
+ * zip_batch_open and zip_batch_open_fields that are unchanged.) */
 
 /* status codes */
 #define ZIP_OK 0
@@ -387,8 +389,8 @@ int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols
  * anything reaches the device.
  *
  * zip_batch_codes_counts: process-wide, monotonic, kept like zip_batch_verify_calls: zip_batch_commit_codes calls that
- * reached the device, the members they committed, and calls of the two _fields entry points that reached the device.
- * Any pointer may be NULL.
+ * reached the device, the members they committed, and calls of the two _fields entry points that reached the device
+ * (zip_batch_open_each is zip_batch_open_fields with another delivery and counts as one).  Any pointer may be NULL.
  *
  * The verifier's side of this family, zip_batch_verify_codes, is declared with zip_batch_verify below.
  *
@@ -402,6 +404,38 @@ int32_t zip_batch_open_fields(zip_batch *b, const int64_t *coeffs, const uint32_
                               const uint64_t *q0_mont, const zip_field *const *fields, uint8_t *proofs_out,
                               zip_mem_kind out_kind);
 void zip_batch_codes_counts(uint64_t *commits, uint64_t *members, uint64_t *field_opens);
+
+/* ---- a batch open that delivers every stream to a buffer of its own ---------------------
+ * zip_batch_open_fields writes n_polys streams into ONE block of n_polys * zip_proof_len bytes, on the device and (HOST
+ * output) on the host.  zip_batch_open_each writes stream i to proofs_out[i] and never holds more than two windows of
+ * streams at once: no device or host block grows with n_polys, and the first streams leave the device while later
+ * members are still being gathered.
+ *   coeffs, cols, n_cols, q0_mont, fields   exactly as for zip_batch_open_fields (a caller with one field passes the
+ *                same pointer n_polys times); the batch may come from either commit entry point
+ *   proofs_out   HOST array of n_polys pointers; proofs_out[i] receives zip_proof_len bytes, byte-identical to stream i
+ *                of zip_batch_open_fields with the same arguments (and so to zip_open of member i).  The destinations
+ *                need not be contiguous or in order; their ranges must not overlap
+ *   out_kind     of every destination.  HOST: any alignment, pageable or pinned (zip_host_register).  DEVICE: 8-byte
+ *                aligned, the alignment a stream has inside zip_batch_open_fields' block
+ *   window_bytes HOST output only: members leave in windows of W = max(1, window_bytes / zip_proof_len) consecutive
+ *                members (0 = 64 MiB, zip_open_stream's default).  The library stages at most two windows on the device
+ *                (two slots from the ctx's pool, reused): while window w is copied out on the ctx's second stream, window
+ *                w + 1 is combined and gathered.  Each stream goes from its slot straight to proofs_out[i]: a pinned
+ *                destination by one asynchronous copy, a pageable one through the library's bounce buffers.
+ * DEVICE output has no staging and no windows (window_bytes is ignored): the kernels write through a device table of
+ * the destinations.  The call returns when every byte has landed (DEVICE: as zip_batch_open_fields does).
+ * Errors, all before anything reaches the device, in zip_batch_open_fields' order with these additions: ZIP_ERR_NULL
+ * also for proofs_out and any proofs_out[i]; after the column indices, ZIP_ERR_INVALID_PARAM for a DEVICE destination that
+ * is not 8-byte aligned and for two destinations whose zip_proof_len-byte ranges overlap.  A ctx set to more than one
+ * proximity test is refused (ZIP_ERR_UNSUPPORTED) as by the other batch opens.  Batch and ctx stay usable after any error.
+ *
+ * zip_batch_open_each_counts: process-wide, kept like zip_batch_codes_counts: calls that reached the device, the members
+ * and the windows of those calls (monotonic; a DEVICE call is one window), and the bytes of device staging the most
+ * recent such call asked its pool for (0 for DEVICE output).  Any pointer may be NULL. */
+int32_t zip_batch_open_each(zip_batch *b, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols,
+                            const uint64_t *q0_mont, const zip_field *const *fields, uint8_t *const *proofs_out,
+                            zip_mem_kind out_kind, size_t window_bytes);
+void zip_batch_open_each_counts(uint64_t *calls, uint64_t *members, uint64_t *windows, uint64_t *last_staging_bytes);
 
 /* ---- streaming proof writer -------------------------------
  * zip_open with the stream delivered to `sink` in order, piece by piece (u', then groups of opened

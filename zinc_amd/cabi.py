@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "zip_batch_commit_codes", "zip_batch_open_eval_fields", "zip_batch_open_fields", "zip_batch_codes_counts",
     "zip_prime_test_base2", "zip_get_prime", "zip_prime_launch_counts",
     "zip_get_prime_batch", "zip_prime_batch_counts",
+    "zip_batch_open_each", "zip_batch_open_each_counts",
 )
 
 
@@ -315,6 +316,10 @@ def lib():
     L.zip_batch_open_fields.argtypes = [vp, i64p, u32p, C.c_uint32, u64p, vp, u8p, C.c_int]
     L.zip_batch_codes_counts.argtypes = [C.POINTER(C.c_uint64)] * 3
     L.zip_batch_codes_counts.restype = None
+    L.zip_batch_open_each.argtypes = [vp, i64p, u32p, C.c_uint32, u64p, vp, vp, C.c_int, C.c_size_t]
+    L.zip_batch_open_each.restype = C.c_int32
+    L.zip_batch_open_each_counts.argtypes = [C.POINTER(C.c_uint64)] * 4
+    L.zip_batch_open_each_counts.restype = None
     for fn in ("zip_batch_commit", "zip_batch_member", "zip_batch_open_eval", "zip_batch_open", "zip_batch_commit_codes",
                "zip_batch_open_eval_fields", "zip_batch_open_fields"):
         getattr(L, fn).restype = C.c_int32
@@ -961,6 +966,39 @@ class Batch:
         c._check(rc, "zip_batch_open_fields")
         return res
 
+    def open_each(self, coeffs, cols, q0_mont, fields, outs=None, out_kind=MEM_HOST, window_bytes=0):
+        """zip_batch_open_each: open_fields with stream i delivered to outs[i] -> the list of streams.  outs: one uint8
+        buffer of proof_len bytes per polynomial (numpy arrays, or torch tensors on the device for out_kind=MEM_DEVICE; an
+        int entry is taken as a raw address, None stays NULL); left out, fresh buffers of `out_kind`.  HOST streams leave
+        the device in windows of max(1, window_bytes // proof_len) polynomials (0: 64 MiB)."""
+        c = self.ctx
+        limbs = fields[0].limbs
+        cols = np.ascontiguousarray(cols, dtype=np.uint32).reshape(len(self), -1) if cols is not None else None
+        coeffs_c = np.ascontiguousarray(coeffs, dtype=np.int64) if coeffs is not None else None
+        q0 = np.ascontiguousarray(q0_mont, dtype=np.uint64) if q0_mont is not None else None
+        n_cols = cols.shape[1] if cols is not None else 0
+        if outs is None:
+            n = c.proof_len(n_cols, limbs)
+            if out_kind == MEM_DEVICE:
+                import torch
+
+                # (empty, not zeros: a fill on torch's stream could land after the library's writes on the ctx's)
+                outs = [torch.empty(n, dtype=torch.uint8, device=f"cuda:{c.device}") for _ in range(len(self))]
+            else:
+                outs = [np.zeros(n, dtype=np.uint8) for _ in range(len(self))]
+        if len(outs) != len(self):
+            raise ValueError(f"open_each: {len(outs)} destinations for {len(self)} polynomials")
+        table = (C.c_void_p * max(len(outs), 1))()
+        for i, o in enumerate(outs):
+            table[i] = o if o is None or isinstance(o, int) else _ptr(o)[0]
+        arr = self._field_ptrs(fields)
+        rc = lib().zip_batch_open_each(self._h, coeffs_c.ctypes.data if coeffs_c is not None else None,
+                                       cols.ctypes.data if cols is not None and n_cols else None, n_cols,
+                                       q0.ctypes.data if q0 is not None else None, C.cast(arr, C.c_void_p),
+                                       C.cast(table, C.c_void_p), out_kind, window_bytes)
+        c._check(rc, "zip_batch_open_each")
+        return outs
+
 
 class Commitment:
     """Device-resident MultilinearZipData (+ roots) behind a zip_commitment handle."""
@@ -1095,6 +1133,14 @@ def batch_codes_counts():
     a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
     lib().zip_batch_codes_counts(C.byref(a), C.byref(b), C.byref(c))
     return a.value, b.value, c.value
+
+
+def batch_open_each_counts():
+    """zip_batch_open_each_counts: (calls that reached the device, their members, their windows, device staging bytes of the
+    last such call) in this process so far"""
+    v = [C.c_uint64() for _ in range(4)]
+    lib().zip_batch_open_each_counts(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
 
 
 def sumcheck_launch_counts():

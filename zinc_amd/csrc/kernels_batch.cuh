@@ -42,11 +42,31 @@ constexpr uint32_t kBatchCombineThreads = 64;
 // (one modulus: zip_batch_open), or decided per member at run time, quirk_mod == 0 meaning none (batch_combine_fields_kernel)
 enum BatchQuirk { kQuirkNone = 0, kQuirkAlways = 1, kQuirkPerMember = 2 };
 
-// polynomial blockIdx.y in the field f (quirk_mod: its 2^(64 FL) - q where that fits 64 bits, see BatchQuirk)
-template <int FL, bool DO_INT, int QUIRK>
-__device__ __forceinline__ void batch_combine_body(const BatchCombineArgs &a, const FieldDev<FL> &f, uint64_t quirk_mod) {
+// A launch over the members [first, first + grid) of a batch (zip_batch_open_each): block position p reads the inputs of
+// member first + p.  Its stream goes to slot position p (dst == nullptr: base + p * stride, as in the launches over the
+// whole batch) or to dst[first + p], a device table with one stream base per member of the batch; the evaluation row
+// then sits row_be_at bytes into the stream, u' at its start.  Everything here is wave-uniform.
+struct BatchEachArgs {
+    uint32_t first;
+    uint8_t *const *dst;
+    size_t row_be_at;
+};
+
+// member m's entry of the table, through the scalar cache (the table was uploaded before the launch)
+__device__ __forceinline__ uint8_t *batch_each_stream(const BatchEachArgs &e, uint32_t m) {
+    const auto *tab = (const __attribute__((address_space(4))) uint64_t *)(uintptr_t)e.dst;
+    return reinterpret_cast<uint8_t *>((uintptr_t)tab[m]);
+}
+
+// polynomial blockIdx.y in the field f (quirk_mod: its 2^(64 FL) - q where that fits 64 bits, see BatchQuirk).
+// EACH: polynomial e.first + blockIdx.y, written where BatchEachArgs says
+template <int FL, bool DO_INT, int QUIRK, bool EACH = false>
+__device__ __forceinline__ void batch_combine_body(const BatchCombineArgs &a, const FieldDev<FL> &f, uint64_t quirk_mod,
+                                                   const BatchEachArgs &e = BatchEachArgs{}) {
     const uint32_t col = blockIdx.x * kBatchCombineThreads + threadIdx.x;
-    const uint32_t b = blockIdx.y;
+    const uint32_t ob = blockIdx.y;                    // the position among this launch's outputs
+    const uint32_t b = EACH ? e.first + ob : ob;       // the polynomial
+    const bool to_table = EACH && e.dst != nullptr;
     const uint32_t R = a.num_rows;
     constexpr uint64_t kBias = 1ull << 63;
 
@@ -107,7 +127,7 @@ __device__ __forceinline__ void batch_combine_body(const BatchCombineArgs &a, co
     for (; r < R; r++, p += a.row_len) one_row(*p, r);
     if (!live) return;
 
-    if (DO_INT && a.uprime) {
+    if (DO_INT && (a.uprime || to_table)) {
         // sum c w = P - 2^63 (W + sum c') + rows 2^126   (mod 2^192: the value fits)
         uint64_t s[3], ws[2], t[3];
         P.template pack<3>(s);
@@ -121,7 +141,8 @@ __device__ __forceinline__ void batch_combine_body(const BatchCombineArgs &a, co
         uint64_t u[3] = {0, (uint64_t)(R & 3u) << 62, (uint64_t)(R >> 2)};
         add_n<3>(s, u);
         const uint64_t sign = (uint64_t)((int64_t)s[2] >> 63);
-        uint64_t *dst = reinterpret_cast<uint64_t *>(a.uprime + (size_t)b * a.out_stride) + (size_t)col * a.m_limbs;
+        uint8_t *stream = to_table ? batch_each_stream(e, b) : a.uprime + (size_t)ob * a.out_stride;
+        uint64_t *dst = reinterpret_cast<uint64_t *>(stream) + (size_t)col * a.m_limbs;
         for (uint32_t i = 0; i < a.m_limbs; i++) dst[i] = i < 3 ? s[i] : sign;  // write_integer, pcs_transcript.rs:115-123
     }
     {
@@ -138,12 +159,13 @@ __device__ __forceinline__ void batch_combine_body(const BatchCombineArgs &a, co
         if (!geq_n<FL>(ra, rb)) add_n<FL>(ra, f.modulus);  // (wraps mod 2^(64 FL) when q has no spare bit; fine)
         sub_n<FL>(ra, rb);
         if (a.row_limbs) {
-            uint64_t *dst = a.row_limbs + ((size_t)b * a.row_len + col) * FL;
+            uint64_t *dst = a.row_limbs + ((size_t)ob * a.row_len + col) * FL;
 #pragma unroll
             for (int i = 0; i < FL; i++) dst[i] = ra[i];
         }
-        if (a.row_be) {  // BigInt::to_bytes_be of the Montgomery value, pcs_transcript.rs:107-113
-            uint64_t *dst = reinterpret_cast<uint64_t *>(a.row_be + (size_t)b * a.out_stride) + (size_t)col * FL;
+        if (a.row_be || to_table) {  // BigInt::to_bytes_be of the Montgomery value, pcs_transcript.rs:107-113
+            uint8_t *stream = to_table ? batch_each_stream(e, b) + e.row_be_at : a.row_be + (size_t)ob * a.out_stride;
+            uint64_t *dst = reinterpret_cast<uint64_t *>(stream) + (size_t)col * FL;
 #pragma unroll
             for (int i = 0; i < FL; i++) dst[i] = __builtin_bswap64(ra[FL - 1 - i]);
         }
@@ -172,12 +194,22 @@ batch_combine_fields_kernel(BatchCombineArgs a, const BatchFieldInst<FL> *__rest
     batch_combine_body<FL, DO_INT, kQuirkPerMember>(a, m.f, m.quirk_mod);
 }
 
+// batch_combine_fields_kernel over the members [e.first, e.first + gridDim.y) (zip_batch_open_each)
+template <int FL, bool DO_INT>
+__global__ void __launch_bounds__(kBatchCombineThreads)
+batch_combine_each_kernel(BatchCombineArgs a, const BatchFieldInst<FL> *__restrict__ inst, BatchEachArgs e) {
+    const BatchFieldInst<FL> &m = inst[e.first + blockIdx.y];
+    batch_combine_body<FL, DO_INT, kQuirkPerMember, true>(a, m.f, m.quirk_mod, e);
+}
+
 // ---------------------------------------------------------------------------
 // Batched column openings: open_columns_kernel (natural layout, LDS image of the path records) with the polynomial
 // as blockIdx.z.  Polynomial b owns rows [b num_rows, (b + 1) num_rows) of the batch's row entries and trees, reads
 // cols[b][.] and writes into proof stream b.  A stream starts at a multiple of 8 bytes, not of 16: the values go out
 // as 16-byte stores to 8-byte-aligned addresses and the records take the 8-byte path where they must.
 // Grid (n_cols, row blocks, n_polys); dynamic LDS rows_per_block * (8 + 32 depth) bytes.
+// (batch_open_columns_each_kernel below is a copy of this kernel with another member index and stream base: a fix to
+// the gather here is a fix there too.)
 // ---------------------------------------------------------------------------
 struct BatchOpenColsArgs {
     const uint64_t *rows;    // [n_polys * num_rows][cw][2]   16-byte entries (w0, w1, w2, sign)
@@ -236,6 +268,78 @@ __global__ void __launch_bounds__(256) batch_open_columns_kernel(BatchOpenColsAr
             oc_u128_a8 v;
             v.x = half ? ss : ((uint64_t)e.y << 32) | e.x;
             v.y = half ? ss : ((uint64_t)e.w << 32) | e.z;
+            *reinterpret_cast<oc_u128_a8 *>(base + (size_t)(r0 + rsub) * 8 * K + half * 16) = v;
+        }
+    }
+    __syncthreads();
+    // ---- phase 2: stream the image out ----
+    unsigned char *recs = base + (size_t)a.num_rows * 8 * K + (size_t)r0 * rec_bytes;
+    const uint32_t total = nrows * rec_bytes;
+    if ((reinterpret_cast<uintptr_t>(recs) & 15) == 0) {
+        const uint32_t n16 = total / 16;
+        for (uint32_t i = threadIdx.x; i < n16; i += 256)
+            reinterpret_cast<uint4 *>(recs)[i] = reinterpret_cast<const uint4 *>(img)[i];
+        if (threadIdx.x == 0 && (total & 15))
+            reinterpret_cast<uint64_t *>(recs)[n16 * 2] = reinterpret_cast<const uint64_t *>(img)[n16 * 2];
+    } else {
+        for (uint32_t i = threadIdx.x; i < total / 8; i += 256)
+            reinterpret_cast<uint64_t *>(recs)[i] = reinterpret_cast<const uint64_t *>(img)[i];
+    }
+}
+
+// batch_open_columns_kernel over the members [e.first, e.first + gridDim.z) (zip_batch_open_each): polynomial
+// e.first + blockIdx.z, its stream at slot position blockIdx.z or at its entry of e.dst (BatchEachArgs).  The LDS image
+// and the stores are the ones above; only where the polynomial's inputs and its stream are found differs -- a sibling
+// and not a shared body, because the kernel above keeps its code to the instruction.
+template <int SLOTS>
+__global__ void __launch_bounds__(256) batch_open_columns_each_kernel(BatchOpenColsArgs a, BatchEachArgs e) {
+    extern __shared__ __align__(16) unsigned char img[];
+    constexpr uint32_t K = 4;
+    constexpr uint32_t RPP = 256 / SLOTS;
+    const uint32_t ci = blockIdx.x, ob = blockIdx.z;
+    const uint32_t b = e.first + ob;
+    const uint32_t col = a.cols[(size_t)b * a.n_cols + ci];
+    const uint32_t d = a.depth, cw2 = 2u * a.cw;
+    const uint32_t rec_bytes = 8 + 32 * d;
+    const size_t col_bytes = (size_t)a.num_rows * (8 * K + rec_bytes);
+    uint8_t *stream = e.dst ? batch_each_stream(e, b) : a.out + (size_t)ob * a.stream_bytes;
+    uint8_t *base = stream + a.openings_at + (size_t)ci * col_bytes;
+    const uint32_t r0 = blockIdx.y * a.rows_per_block;
+    const uint32_t r1 = min(r0 + a.rows_per_block, a.num_rows);
+    const uint32_t nrows = r1 - r0;
+    const size_t g0 = (size_t)b * a.num_rows + r0;  // the block's first row among the batch's rows
+
+    // ---- phase 1: sibling hashes into the LDS image (lane roles as in open_columns_kernel) ----
+    {
+        const uint32_t h = threadIdx.x & (SLOTS - 1), rsub = threadIdx.x / SLOTS;
+        const uint32_t lvl = h >> 1;
+        const uint32_t node = cw2 - (cw2 >> lvl) + ((col >> lvl) ^ 1u);
+        const uint64_t *src = a.layers + ((g0 + rsub) * cw2 + node) * 4 + (h & 1) * 2;
+        const size_t src_step = (size_t)RPP * cw2 * 4;
+        unsigned char *dst = img + (size_t)rsub * rec_bytes + 8 + (size_t)h * 16;
+        const uint32_t dst_step = RPP * rec_bytes;
+        if (h < 2 * d) {
+#pragma unroll 4
+            for (uint32_t rr = rsub; rr < nrows; rr += RPP, src += src_step, dst += dst_step) {
+                const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(src);
+                reinterpret_cast<uint64_t *>(dst)[0] = v.x;
+                reinterpret_cast<uint64_t *>(dst)[1] = v.y;
+            }
+        } else if (h == 2 * d) {
+            const uint64_t hdr = __builtin_bswap64((uint64_t)d);
+            for (uint32_t rr = rsub; rr < nrows; rr += RPP)
+                *reinterpret_cast<uint64_t *>(img + (size_t)rr * rec_bytes) = hdr;
+        }
+    }
+    // ---- column values: the Int<4> of a 16-byte entry is (w0, w1 | w2, sign | sign x 4) ----
+    {
+        const uint32_t half = threadIdx.x & 1, rsub = threadIdx.x >> 1;
+        if (rsub < nrows) {
+            const uint4 ent = *reinterpret_cast<const uint4 *>(a.rows + ((g0 + rsub) * a.cw + col) * 2);
+            const uint64_t ss = ((uint64_t)ent.w << 32) | ent.w;
+            oc_u128_a8 v;
+            v.x = half ? ss : ((uint64_t)ent.y << 32) | ent.x;
+            v.y = half ? ss : ((uint64_t)ent.w << 32) | ent.z;
             *reinterpret_cast<oc_u128_a8 *>(base + (size_t)(r0 + rsub) * 8 * K + half * 16) = v;
         }
     }

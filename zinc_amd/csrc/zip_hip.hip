@@ -2976,6 +2976,29 @@ int32_t launch_batch_combine_fields_fl(zip_ctx *ctx, const BatchCombineArgs &a, 
     HIP_TRY(ctx, hipGetLastError());
     return ZIP_OK;
 }
+
+// zip_batch_open_each: the two launches over the members [e.first, e.first + n) of a batch, into a staging slot or
+// through the table of destinations (BatchEachArgs)
+template <int FL>
+int32_t launch_batch_combine_each_fl(zip_ctx *ctx, const BatchCombineArgs &a, uint32_t n, bool do_int, const void *inst_d,
+                                     const BatchEachArgs &e) {
+    const dim3 grid((a.row_len + kBatchCombineThreads - 1) / kBatchCombineThreads, n), block(kBatchCombineThreads);
+    const BatchFieldInst<FL> *inst = static_cast<const BatchFieldInst<FL> *>(inst_d);
+    LaunchTimer t(ctx, "batch_combine_each_kernel", ctx->stream);
+    if (do_int) hipLaunchKernelGGL((batch_combine_each_kernel<FL, true>), grid, block, 0, ctx->stream, a, inst, e);
+    else hipLaunchKernelGGL((batch_combine_each_kernel<FL, false>), grid, block, 0, ctx->stream, a, inst, e);
+    HIP_TRY(ctx, hipGetLastError());
+    return ZIP_OK;
+}
+int32_t launch_batch_open_columns_each(zip_ctx *ctx, const BatchOpenColsArgs &g, uint32_t n, const BatchEachArgs &e) {
+    // (cw <= 16384: 2 * depth + 1 <= 29 lanes per row; an image of 32 records is at most 14.6 KB)
+    const size_t lds = (size_t)g.rows_per_block * (8 + 32 * (size_t)g.depth);
+    const dim3 grid(g.n_cols, (g.num_rows + g.rows_per_block - 1) / g.rows_per_block, n), block(256);
+    LaunchTimer t(ctx, "batch_open_columns_each_kernel", ctx->stream);
+    hipLaunchKernelGGL(batch_open_columns_each_kernel<32>, grid, block, lds, ctx->stream, g, e);
+    HIP_TRY(ctx, hipGetLastError());
+    return ZIP_OK;
+}
 }  // namespace
 
 // ------------------------------------------------------------------ INT_LIMBS = 2 (kernels_two_limb.cuh)
@@ -5179,6 +5202,171 @@ int32_t zip_batch_open(zip_batch *b, const int64_t *coeffs, const uint32_t *cols
 int32_t zip_batch_open_fields(zip_batch *b, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont,
                               const zip_field *const *fields, uint8_t *proofs_out, zip_mem_kind out_kind) {
     return batch_open_impl(b, coeffs, cols, n_cols, q0_mont, nullptr, fields, true, proofs_out, out_kind);
+}
+
+// ---- zip_batch_open_each: zip_batch_open_fields with every stream delivered to a destination of its own ----
+// HOST destinations: the members leave in windows of W; two staging slots of W streams, the gather of window w + 1 on
+// ctx->stream beside the copies of window w on s_upper (zip_open_stream's pattern).  DEVICE destinations: one launch
+// pair that writes through a device table of the destinations, no staging.
+// Process-wide (zip_batch_open_each_counts): calls that reached the device, their members and windows, and the staging
+// bytes of the last of them
+static std::atomic<uint64_t> g_open_each_calls{0}, g_open_each_members{0}, g_open_each_windows{0}, g_open_each_staging{0};
+
+int32_t zip_batch_open_each(zip_batch *b, const int64_t *coeffs, const uint32_t *cols, uint32_t n_cols, const uint64_t *q0_mont,
+                            const zip_field *const *fields, uint8_t *const *proofs_out, zip_mem_kind out_kind, size_t window_bytes) {
+    if (!b || !proofs_out || (n_cols && !cols)) return ZIP_ERR_NULL;
+    zip_ctx *ctx = b->ctx;
+    std::lock_guard<std::recursive_mutex> api_lock(ctx->api_mu);
+    const uint32_t R = ctx->p.num_rows, C = ctx->p.row_len, B = b->n_polys;
+    for (uint32_t i = 0; i < B; i++)
+        if (!proofs_out[i]) return fail(ctx, ZIP_ERR_NULL, "proofs_out[%u] is NULL", i);
+    std::vector<HostField> hfs;
+    int32_t rc;
+    if ((rc = refuse_extra_tests(ctx, "zip_batch_open_each"))) return rc;
+    if ((rc = batch_member_fields(ctx, fields, B, &hfs))) return rc;
+    const HostField &hf = hfs[0];
+    const bool single = R == 1;
+    if (!single && (!coeffs || !q0_mont)) return fail(ctx, ZIP_ERR_NULL, "coeffs / q0_mont is NULL");
+    if ((uint64_t)B * n_cols > 0xFFFFFFFFull) return fail(ctx, ZIP_ERR_UNSUPPORTED, "%u x %u openings exceed 2^32", B, n_cols);
+    if ((rc = check_cols(ctx, cols, B * n_cols))) return rc;
+    const size_t len = zip_proof_len(ctx, n_cols, hf.fl);
+    {   // the destinations: aligned for the kernels' stores where they write them, and disjoint
+        std::vector<uintptr_t> at(B);
+        for (uint32_t i = 0; i < B; i++) {
+            at[i] = reinterpret_cast<uintptr_t>(proofs_out[i]);
+            if (out_kind == ZIP_MEM_DEVICE && (at[i] & 7))
+                return fail(ctx, ZIP_ERR_INVALID_PARAM, "proofs_out[%u] is a device address that is not 8-byte aligned", i);
+        }
+        std::sort(at.begin(), at.end());
+        for (uint32_t i = 1; i < B; i++)
+            if (at[i] - at[i - 1] < len) return fail(ctx, ZIP_ERR_INVALID_PARAM, "two destinations of %zu bytes overlap", len);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool to_host = out_kind == ZIP_MEM_HOST;
+    if (window_bytes == 0) window_bytes = (size_t)64 << 20;
+    const uint32_t W = to_host ? (uint32_t)std::min<size_t>(std::max<size_t>(window_bytes / len, 1), B) : B;
+    const uint32_t n_windows = (B + W - 1) / W, n_slots = !to_host ? 0u : n_windows > 1 ? 2u : 1u;
+    std::vector<unsigned char> inst_h;
+    std::vector<uint64_t> ones_h;
+    with_fl(hf.fl, [&](auto FL) { batch_fill_field_args<decltype(FL)::value>(hfs, &inst_h, &ones_h); });
+    const size_t u_bytes = single ? 0 : (size_t)C * ctx->p.m_limbs * 8;
+    const size_t col_bytes = (size_t)n_cols * column_bytes(ctx);
+    Scratch slot0(ctx), slot1(ctx), small(ctx);
+    if (n_slots > 0 && (rc = slot0.get((size_t)W * len))) return rc;
+    if (n_slots > 1 && (rc = slot1.get((size_t)W * len))) return rc;
+    uint8_t *slot[2] = {slot0.as<uint8_t>(), slot1.as<uint8_t>()};
+    SmallInputs si;
+    if (!single) {
+        si.src[0] = coeffs;
+        si.bytes[0] = (size_t)B * R * 8;
+    }
+    si.src[1] = single ? (const void *)ones_h.data() : (const void *)q0_mont;
+    si.bytes[1] = (size_t)B * R * hf.fl * 8;
+    si.src[2] = cols;
+    si.bytes[2] = (size_t)B * n_cols * 4;
+    si.src[3] = inst_h.data();
+    si.bytes[3] = inst_h.size();
+    if (!to_host) {
+        si.src[4] = proofs_out;
+        si.bytes[4] = (size_t)B * sizeof(uint8_t *);
+    }
+    unsigned char *sb;
+    if ((rc = stage_small(ctx, si, small, &sb))) return rc;
+    // the inputs are on their way: from here on the call has reached the device
+    g_batch_field_opens++;
+    g_open_each_calls++;
+    g_open_each_members += B;
+    g_open_each_windows += n_windows;
+    g_open_each_staging = (uint64_t)n_slots * W * len;
+    BatchCombineArgs a{};
+    a.evals = b->evals_d;
+    a.coeffs = single ? nullptr : reinterpret_cast<const int64_t *>(sb + si.off[0]);
+    a.q0 = reinterpret_cast<const uint64_t *>(sb + si.off[1]);
+    a.num_rows = R;
+    a.row_len = C;
+    a.m_limbs = ctx->p.m_limbs;
+    a.out_stride = len;
+    BatchOpenColsArgs g{};
+    g.rows = static_cast<const uint64_t *>(b->store->rows);
+    g.layers = static_cast<const uint64_t *>(b->store->layers);
+    g.cols = reinterpret_cast<const uint32_t *>(sb + si.off[2]);
+    g.stream_bytes = len;
+    g.openings_at = u_bytes;
+    g.n_cols = n_cols;
+    g.num_rows = R;
+    g.cw = ctx->p.codeword_len;
+    g.depth = ctx->depth;
+    g.rows_per_block = R < 32u ? R : 32u;
+    // members [first, first + cnt): u' and the evaluation row, then the column openings, to `out` (a slot) or the table
+    auto launch = [&](uint32_t first, uint32_t cnt, uint8_t *out) -> int32_t {
+        BatchEachArgs e{};
+        e.first = first;
+        if (out) {
+            a.uprime = single ? nullptr : out;
+            a.row_be = out + u_bytes + col_bytes;
+        } else {
+            e.dst = reinterpret_cast<uint8_t *const *>(sb + si.off[4]);
+            e.row_be_at = u_bytes + col_bytes;
+        }
+        int32_t r = with_fl(hf.fl, [&](auto FL) {
+            return launch_batch_combine_each_fl<decltype(FL)::value>(ctx, a, cnt, !single, sb + si.off[3], e);
+        });
+        if (r || !n_cols) return r;
+        g.out = out;
+        return launch_batch_open_columns_each(ctx, g, cnt, e);
+    };
+    if (!to_host) {
+        if ((rc = launch(0, B, nullptr))) return rc;
+        HIP_TRY(ctx, stream_wait(ctx->stream));  // coeffs, cols, q0 and the table were read from host memory
+        return ZIP_OK;
+    }
+    hipStream_t s_copy = ctx->s_upper;  // the copies of window w run beside the gather of window w + 1
+    hipEvent_t gathered[2] = {take_dep_event(ctx), take_dep_event(ctx)};
+    hipEvent_t copied[2] = {take_dep_event(ctx), take_dep_event(ctx)};
+    auto launch_window = [&](uint32_t w) -> int32_t {
+        const int s = (int)(w & 1);
+        const uint32_t first = w * W;
+        if (w >= 2) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, copied[s], 0));  // slot[s] has left the device
+        if (int32_t r = launch(first, std::min(W, B - first), slot[s])) return r;
+        HIP_TRY(ctx, hipEventRecord(gathered[s], ctx->stream));
+        return ZIP_OK;
+    };
+    auto copy_window = [&](uint32_t w) -> int32_t {
+        const int s = (int)(w & 1);
+        const uint32_t first = w * W, cnt = std::min(W, B - first);
+        for (uint32_t i = 0; i < cnt; i++) {
+            uint8_t *dst = proofs_out[first + i];
+            const uint8_t *src = slot[s] + (size_t)i * len;
+            if (host_range_is_pinned(dst, len)) HIP_TRY(ctx, hipMemcpyAsync(dst, src, len, hipMemcpyDeviceToHost, s_copy));
+            else if (int32_t r = copy_d2h_bounced(ctx, dst, src, len, s_copy)) return r;
+        }
+        HIP_TRY(ctx, hipEventRecord(copied[s], s_copy));
+        return ZIP_OK;
+    };
+    int32_t status = launch_window(0);
+    for (uint32_t w = 0; w < n_windows && status == ZIP_OK; w++) {
+        hipError_t e = hipStreamWaitEvent(s_copy, gathered[w & 1], 0);
+        if (e != hipSuccess) { status = fail(ctx, ZIP_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(e)); break; }
+        if (w + 1 < n_windows && (status = launch_window(w + 1))) break;
+        status = copy_window(w);
+    }
+    // every byte has landed, and nothing still reads the slots, before they return to the pool
+    hipError_t e1 = stream_wait(s_copy), e2 = stream_wait(ctx->stream);
+    for (int i = 0; i < 2; i++) {
+        ctx->dep_event_pool.push_back(gathered[i]);
+        ctx->dep_event_pool.push_back(copied[i]);
+    }
+    if (status) return status;
+    HIP_TRY(ctx, e1);
+    HIP_TRY(ctx, e2);
+    return ZIP_OK;
+}
+
+void zip_batch_open_each_counts(uint64_t *calls, uint64_t *members, uint64_t *windows, uint64_t *last_staging_bytes) {
+    if (calls) *calls = g_open_each_calls.load();
+    if (members) *members = g_open_each_members.load();
+    if (windows) *windows = g_open_each_windows.load();
+    if (last_staging_bytes) *last_staging_bytes = g_open_each_staging.load();
 }
 
 // =====================================================================================================

@@ -1220,7 +1220,7 @@ zip::ZipProof zip::commit_z_mle_and_prove_evaluation(const LinearCodeSpec &lc_sp
 
 // The same for B proofs whose z fill one geometry, each with its own main transcript (hence its own RAA code: :313)
 // and its own field: ONE zip_batch_commit_codes, ONE zip_batch_open_eval_fields, the walk of B fresh PcsTranscripts and
-// v_i = <row_i, q1_i> on the host, ONE zip_batch_open_fields.  What is shared is the geometry, and with it the ctx
+// v_i = <row_i, q1_i> on the host, ONE zip_batch_open_each that writes every stream into its ZipProof.  What is shared is the geometry, and with it the ctx
 // (streams, pools) and the witness block; per member are the permutations (read by the commit alone), the field, the
 // point, the challenges.  The caller has made sure of what the batch serves (one proximity test, codewords up to 8192,
 // one limb count); everything a member's own step would throw is thrown here at the same member, in the same order.
@@ -1303,18 +1303,18 @@ std::vector<zip::ZipProof> zip::commit_z_mle_and_prove_evaluation_batch(const Li
                                               coeffs.empty() ? nullptr : coeffs.data() + i * num_rows, cols.data() + i * n_cols);
     }
     timer.lap("batch: v + transcripts");
-    // 5. every proof stream in one call, cut into the ZipProofs
+    // 5. every proof stream in one call, each straight into its ZipProof (window by window: no block of B streams)
     const size_t len = zip_proof_len(ctx, n_cols, fl);
-    ByteStream streams;
-    streams.resize(B * len);
-    check(ctx, zip_batch_open_fields(raw, coeffs.empty() ? nullptr : coeffs.data(), cols.data(), n_cols, q0p, zfp.data(), streams.data(),
-                                     ZIP_MEM_HOST),
-          "zip_batch_open_fields");
+    std::vector<uint8_t *> dsts(B);
     for (size_t i = 0; i < B; i++) {
         out[i].z_comm.roots.resize(num_rows);
         std::memcpy(out[i].z_comm.roots.data(), roots.data() + i * (size_t)num_rows * 32, (size_t)num_rows * 32);
-        out[i].pcs_proof.assign(streams.begin() + i * len, streams.begin() + (i + 1) * len);
+        out[i].pcs_proof.resize(len);
+        dsts[i] = out[i].pcs_proof.data();
     }
+    check(ctx, zip_batch_open_each(raw, coeffs.empty() ? nullptr : coeffs.data(), cols.data(), n_cols, q0p, zfp.data(), dsts.data(),
+                                   ZIP_MEM_HOST, 0),
+          "zip_batch_open_each");
     timer.lap("batch: open");
     return out;
 }
@@ -1977,21 +1977,21 @@ std::vector<ZincProof> ZincProver::prove_batch(const zip_sparse_matrix *matrices
 }
 
 namespace {
-// From how many proofs on the PCS step is taken as one batch: where commit_codes + the two _fields opens beat the loop
-// over pcs_step by more than the loop's own spread (profiles/pcs_step_batch.md, 1000 openings, 4 limbs).  That is ONE
-// measured point: 256 proofs at 2^10 rows (1.41x).  The batch LOSES everywhere else it was measured -- B = 2, 3, 4, 8, 16
-// at 2^10 .. 2^16 (0.17x .. 0.89x; 1.11x at 2^10 x 16 is inside the loop's spread) and B = 256 at 2^12, 2^14, 2^16
-// (0.78x, 0.52x, 0.47x) -- so the loop stays there: a proof stream is 7.4 .. 84 MB at these sizes, and the batch moves all
-// of them through one device block and one host block before cutting them.  A size between the measured ones takes the
-// rule of the next larger one; above 2^10 rows there is no line.
+// From how many proofs on the PCS step is taken as one batch.  The rule is the profile's: where the batch beats the loop
+// over pcs_step by more than the loop's own spread.  profiles/pcs_step_batch.md measured the batch with the ONE-BLOCK
+// delivery (zip_batch_open_fields into a block of B streams, cut afterwards): it won once, 256 proofs at 2^10 rows
+// (1.41x), and lost everywhere else.  Step 5 now delivers per member (zip_batch_open_each), and that table no longer
+// describes what would run; a table of the new delivery has not been measured.  Until
+// one exists there is NO line: the default is the loop at every size, so no default path runs on an unmeasured number.
 // ZIP_HIP_PCS_MIN_BATCH=n (n >= 2, read per call) puts the line at n for every size: how tools/pcs_batch_times.py measures
-// the batch below the line.
+// the batch, and how the tests run it.
 size_t min_pcs_batch(size_t s_prime) {
     if (const char *e = std::getenv("ZIP_HIP_PCS_MIN_BATCH")) {
         const long n = std::atol(e);
         if (n >= 2) return (size_t)n;
     }
-    return s_prime <= 10 ? 256 : SIZE_MAX;
+    (void)s_prime;
+    return SIZE_MAX;
 }
 }  // namespace
 

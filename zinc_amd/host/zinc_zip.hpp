@@ -362,7 +362,7 @@ ZipProof commit_z_mle_and_prove_evaluation(const LinearCodeSpec &lc_spec, const 
                                            const FieldConfig &config, int device = 0);
 // The PCS step of B proofs whose z fill ONE geometry (m evaluations each) in one commit and one open: each proof's code
 // comes from its own main transcript, so the members share the geometry and nothing else -- zip_batch_commit_codes takes
-// the permutations per member, zip_batch_open_eval_fields / zip_batch_open_fields the fields.  Per proof the result, the
+// the permutations per member, zip_batch_open_eval_fields / zip_batch_open_each the fields.  Per proof the result, the
 // main transcript afterwards and whatever is thrown are those of commit_z_mle_and_prove_evaluation called member after
 // member.  The caller sees to what the device batch serves: one proximity test, codeword_len <= 8192, one limb count.
 struct PcsBatchMember {

@@ -850,8 +850,9 @@ class ZincProver:
 
     def prove_batch(self, matrices, s, d, S, c, xs, ws, transcripts, fields):
         """spartan_prove_batch, then the PCS step of every proof (ZincProver::pcs_step_batch): each proof draws its code
-        from its own transcript, and from the line profiles/pcs_step_batch.md sets on all of them are committed in one
-        zip_batch_commit_codes and opened in one pair of _fields calls; ZIP_HIP_BATCH=0, one proof, more than one proximity
+        from its own transcript, and from the line of min_pcs_batch on (none by default until the per-member delivery is
+        measured; ZIP_HIP_PCS_MIN_BATCH=n sets one) all of them are committed in one zip_batch_commit_codes and opened in
+        one zip_batch_open_eval_fields and one zip_batch_open_each; ZIP_HIP_BATCH=0, one proof, more than one proximity
         test and every other shape take the loop over the one-proof step, with the same bytes -> a list of the dicts
         prove returns."""
         return self._run_batch(matrices, s, d, S, c, xs, ws, transcripts, fields, True)
